@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: EM iterations/s of the Poisson-GPFA hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1] [--no-cpu-baseline] [--cpu-estimate]
-                    [--workload em|online|loo|dual|floor]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1] [--full [--no-cpu-baseline] [--cpu-estimate] [--lean]]
+                    [--workload em|online|loo|dual|floor] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up and K timed steps, and prints the result line.  `--full` adds everything else the benchmark
+measures: HIP events in the timed region for the roofline figures, the untimed extra iterations after it (per-kernel-family breakdown,
+the reference engine's default TNC driver, the settled-fit plateau; `--lean` leaves these out again), the other engines of
+`--workload floor` and the CPU baseline (`--no-cpu-baseline` leaves it out).
+
+`--dump-outputs DIR` (`--workload em`): after the timed steps, rank 0 writes what the last timed step returned to a caller as
+DIR/<name>.npy (float64): the parameters after its M-step (C, d, tau), the E-step's nll and its posterior means and per-bin
+covariances of this rank's trials - every trial's means where they fit, otherwise, like the covariances, a fixed seeded sample of
+trials (the sampled trial numbers go next to them), under 64 MB in all.  The inputs depend only on the arguments.
 
 A step is one full batch-EM iteration on synthetic spike counts already resident in HBM: warm-started Laplace
 E-step over every trial (batched inexact Newton with the shared-preconditioner PCG, posterior covariance blocks by
@@ -86,6 +96,30 @@ def synth_shard(q, p, T, R, seed, rank):
         X = np.einsum('kts,ks->kt', L, rng.standard_normal((p, T)))
         Ys.append(rng.poisson(np.exp(C @ X + d[:, None])).astype(np.uint8))
     return {'C': C, 'd': d, 'tau': tau}, Ys
+
+
+DUMP_POSTERIOR_BYTES = 56 * 10 ** 6     # --dump-outputs: posterior arrays of one run (with the parameters, the files stay under 64 MB)
+
+
+def dump_em_outputs(path, infRes, nll, params):
+    """--dump-outputs DIR: what the last timed EM iteration hands its caller, as float64 .npy files - the parameters its M-step returned
+    (C, d, tau), its E-step's nll and that E-step's posterior of this rank's trials: post_mean of every trial if the budget allows, else of a
+    fixed seeded sample of trials, and post_vsm of a fixed seeded sample of 16 trials (post_*_trials: the sampled positions in the trial list)."""
+    n = len(infRes['post_mean'])
+
+    def sample(k, seed):
+        return np.arange(n) if k >= n else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    idx_vsm = sample(16, 1)
+    per_vsm, per_mean = np.asarray(infRes['post_vsm'][0]).nbytes, np.asarray(infRes['post_mean'][0]).nbytes
+    idx_mean = sample(max(1, (DUMP_POSTERIOR_BYTES - len(idx_vsm) * per_vsm) // per_mean), 2)
+    if len(idx_mean) == n:
+        infRes.materialize(keys=('post_mean',))                          # one bulk download instead of n small ones
+    arrays = {'C': params['C'], 'd': params['d'], 'tau': params['tau'], 'nll': [nll],
+              'post_mean': np.stack([infRes['post_mean'][int(i)] for i in idx_mean]), 'post_mean_trials': idx_mean,
+              'post_vsm': np.stack([infRes['post_vsm'][int(i)] for i in idx_vsm]), 'post_vsm_trials': idx_vsm}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a, dtype=np.float64))
 
 
 class _Budget(Exception):
@@ -291,7 +325,7 @@ def run_loo(args, q, p, T, R):
            'config': {'workload': '%s leave-one-neuron-out prediction: %d neurons, %d latents, %d bins, %d trials = %d cold mode searches'
                                   % (args.config, q, p, T, R, R * q)},
            'seconds': dt, 'pred_err_mode': err}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         k = 4 if p * T <= 400 else 2
         out['cpu_baseline'] = cpu_baseline_loo(params, Ys[0], 10.0, y_pred[0], k)
         out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
@@ -376,7 +410,7 @@ def run_floor(args, q, p, T, R):
     params = {'C': C, 'd': d, 'tau': tau}
     sess, _ = _session.session_for(exp, p)
     res = {}
-    for name, mode in (('auto', 0), ('dense', 1), ('lowrank', 2)):
+    for name, mode in (('auto', 0), ('dense', 1), ('lowrank', 2)) if args.full else (('auto', 0),):
         sess.ctx.set_option('cov_mode', mode)
         par = {k: v.copy() for k, v in params.items()}
         optim, est, mst, plan = None, [], [], None
@@ -401,7 +435,7 @@ def run_floor(args, q, p, T, R):
            'config': {'workload': '%s floor: %d neurons, %d latents, %d bins, %d trials, all timescales %.0f ms (rank %d of n = %d): auto plan -> %s engine'
                                   % (args.config, q, p, T, R, args.tau_all * 1e3, int(a['lowrank_rtot']), n, a['engine'])},
            'engines': res,
-           'auto_plan_is_fastest': bool(a['ms_per_em_iteration'] <= 1.1 * min(v['ms_per_em_iteration'] for v in res.values() if v.get('engine'))),
+           'auto_plan_is_fastest': bool(a['ms_per_em_iteration'] <= 1.1 * min(v['ms_per_em_iteration'] for v in res.values() if v.get('engine'))) if args.full else None,
            'dense_engine_tflops': 0.72 * float(n) ** 3 * R / (float(np.mean(a['estep_ms'][args.warmup:])) * 1e-3) / 1e12 if a['engine'] == 'dense' else None}
     print(json.dumps(out))
 
@@ -448,7 +482,8 @@ def run_online(args, q, p, T, rank, world):
     tau_method = [args.tau_method]
     state = {'n': 0}
     nwt = {'ms': [], 'moved': []}
-    sess.ctx.set_option('time_newton', 1)
+    if args.full:
+        sess.ctx.set_option('time_newton', 1)
 
     def step():
         n = state['n']
@@ -463,7 +498,8 @@ def run_online(args, q, p, T, rank, world):
         est.append((t1 - t0) * 1e3); mst.append((t2 - t1) * 1e3); nlls.append(float(nll))
         pcgs.append(sess.ctx.info('last_pcg_iterations') / max(1, len(infRes.trial_idx)))
         idx_sum.append(int(np.sum(sub.batchTrIdx)))
-        nwt['ms'].append(sess.ctx.info('last_newton_solve_ms')); nwt['moved'].append(sess.ctx.info('last_newton_solve_bytes_moved'))
+        if args.full:
+            nwt['ms'].append(sess.ctx.info('last_newton_solve_ms')); nwt['moved'].append(sess.ctx.info('last_newton_solve_bytes_moved'))
         state['n'] = n + 1
     params_box, prior_box = [params], [prior]
 
@@ -471,23 +507,25 @@ def run_online(args, q, p, T, rank, world):
         sess.allreduce(np.zeros(1))
     for _ in range(args.warmup):
         step()
-    # HIP events around the largest kernel of the step (the fused product + mixing launch of the covariance phase) on every timed step: two events per E-step
-    sess.ctx.set_option('profile', 3)
+    # --full: HIP events around the largest kernel of the step (the fused product + mixing launch of the covariance phase) on every timed step: two events per E-step
+    if args.full:
+        sess.ctx.set_option('profile', 3)
     barrier()
     t_begin = time.time()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.time() - t_begin
-    ytm_ms, ytm_flops, ytm_launches = (sess.ctx.info('prof_mix_' + k) for k in ('ms', 'flops', 'launches'))
-    ytm_fused = sess.ctx.info('last_yt_mix_fused') == 1.0
-    sess.ctx.set_option('profile', 0)
+    if args.full:
+        ytm_ms, ytm_flops, ytm_launches = (sess.ctx.info('prof_mix_' + k) for k in ('ms', 'flops', 'launches'))
+        ytm_fused = sess.ctx.info('last_yt_mix_fused') == 1.0
+        sess.ctx.set_option('profile', 0)
     times = np.zeros(world)
     times[rank] = elapsed
     t_max = float(np.max(sess.allreduce(times)))
     # two more (untimed) iterations with the reference engine's default timescale driver (scipy TNC), for the record
     tnc_ms = None
-    if world == 1 and not args.lean and args.tau_method != 'TNC':
+    if world == 1 and args.full and not args.lean and args.tau_method != 'TNC':
         tau_method[0] = 'TNC'
         keep = (params_box[0], prior_box[0], state['n'])
         step(); step()
@@ -499,7 +537,6 @@ def run_online(args, q, p, T, rank, world):
     if rank != 0:
         return
     timed = slice(args.warmup, args.warmup + args.steps)
-    n_ms, n_moved = float(np.sum(nwt['ms'][timed])), float(np.sum(nwt['moved'][timed]))
     out = {'metric': 'EM iterations/sec', 'value': args.steps / t_max, 'unit': 'stochastic-EM iterations/s (minibatch %d of %d resident trials)' % (batch, Rres),
            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': t_max / args.steps * 1e3,
            'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
@@ -511,20 +548,24 @@ def run_online(args, q, p, T, rank, world):
            'estep_ms': [round(x, 1) for x in est], 'mstep_ms': [round(x, 1) for x in mst],
            'estep_ms_per_trial': float(np.mean(est[timed])) / (batch / world), 'pcg_iterations_per_trial': [round(x, 1) for x in pcgs],
            'nll': nlls, 'minibatch_index_checksums': idx_sum,
-           'lowrank_plan': sess.ctx.info('plan_lowrank'), 'lowrank_rtot': sess.ctx.info('lowrank_rtot'), 'chunk_trials': sess.ctx.info('chunk_trials'),
-           # the rate with the reference engine's default timescale driver (tauOptimMethod='TNC': p scipy optimisations, one batched device pass per round)
-           'mstep_ms_with_reference_default_tau_TNC': tnc_ms,
-           'value_reference_default_tau': None if tnc_ms is None else 1e3 / (float(np.mean(est[timed])) + tnc_ms),
-           # dominant kernel of the step, as in the batch workload: product + mixing of the covariance phase (HIP events on the context's stream around it)
-           'roofline': None if not (ytm_fused and ytm_ms > 0) else {
-               'bound': 'mfma', 'kernel': 'yt_mix_kernel (FP64 16x16x4 MFMA products + FP64 vector mixing in registers; writes the FP32 correction D and post_vsm)',
-               'achieved': ytm_flops / (ytm_ms * 1e-3) / 1e12, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-               'frac': ytm_flops / (ytm_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS, 'traffic': None,
-               'algorithmic_flops_per_launch': ytm_flops / max(ytm_launches, 1.0), 'launches': ytm_launches, 'avg_launch_ms': ytm_ms / max(ytm_launches, 1.0),
-               'kernel_share_of_step': ytm_ms * 1e-3 / t_max},
-           'roofline_newton': {'bound': 'hbm', 'bytes_moved': n_moved, 'ms': n_ms, 'achieved': n_moved / (n_ms * 1e-3) / 1e9 if n_ms > 0 else 0.0, 'peak': HBM_PEAK_GBS,
-                               'unit': 'GB/s', 'frac': n_moved / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0, 'ms_per_em_iteration': n_ms / args.steps}}
-    if not args.no_cpu_baseline and world == 1:
+           'lowrank_plan': sess.ctx.info('plan_lowrank'), 'lowrank_rtot': sess.ctx.info('lowrank_rtot'), 'chunk_trials': sess.ctx.info('chunk_trials')}
+    if args.full:
+        n_ms, n_moved = float(np.sum(nwt['ms'][timed])), float(np.sum(nwt['moved'][timed]))
+        out.update({
+            # the rate with the reference engine's default timescale driver (tauOptimMethod='TNC': p scipy optimisations, one batched device pass per round)
+            'mstep_ms_with_reference_default_tau_TNC': tnc_ms,
+            'value_reference_default_tau': None if tnc_ms is None else 1e3 / (float(np.mean(est[timed])) + tnc_ms),
+            # dominant kernel of the step, as in the batch workload: product + mixing of the covariance phase (HIP events on the context's stream around it)
+            'roofline': None if not (ytm_fused and ytm_ms > 0) else {
+                'bound': 'mfma', 'kernel': 'yt_mix_kernel (FP64 16x16x4 MFMA products + FP64 vector mixing in registers; writes the FP32 correction D and post_vsm)',
+                'achieved': ytm_flops / (ytm_ms * 1e-3) / 1e12, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                'frac': ytm_flops / (ytm_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS, 'traffic': None,
+                'algorithmic_flops_per_launch': ytm_flops / max(ytm_launches, 1.0), 'launches': ytm_launches, 'avg_launch_ms': ytm_ms / max(ytm_launches, 1.0),
+                'kernel_share_of_step': ytm_ms * 1e-3 / t_max},
+            'roofline_newton': {'bound': 'hbm', 'bytes_moved': n_moved, 'ms': n_ms, 'achieved': n_moved / (n_ms * 1e-3) / 1e9 if n_ms > 0 else 0.0, 'peak': HBM_PEAK_GBS,
+                                'unit': 'GB/s', 'frac': n_moved / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0, 'ms_per_em_iteration': n_ms / args.steps}
+        })
+    if args.full and not args.no_cpu_baseline and world == 1:
         # the reference's stochastic-EM iteration costs what a batch iteration over the minibatch costs (same E-step loop inference.py:94 over 1024
         # trials, the prior-regularised M-step on their posterior): the faithful CPU trial of the batch workload, scaled to the minibatch
         out['cpu_baseline'] = cpu_baseline(q, p, T, batch, true_params, Ys[0], 10.0, params, estimate=args.cpu_estimate, budget_s=args.cpu_budget)
@@ -626,7 +667,7 @@ def run_dual(args, q, p, T, R, rank, world):
     # engine - factorisation, inverse, Yt, the dual's neuron contractions - on the matrix cores in single precision ('mixed') or FP64, against the
     # dense matrix peak of that type, and the mixing pass over the Yt slab against HBM (bytes: its columns read once, written once)
     roof = None
-    if whole and fixed_point and not args.lean:
+    if whole and fixed_point and args.full and not args.lean:
         ctx.set_option('dual_f32', 1 if args.precision == 'mixed' else 0)
         ctx.set_option('profile', 1)
         ctx.dual_fixed_point(idx, None, want_rho=False)
@@ -683,7 +724,7 @@ def run_dual(args, q, p, T, R, rank, world):
                            'parallelism': 'trial-sharded x%d' % world})
         if roof:
             out.update(roof)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline_dual(q, p, T, true_params, tau, Ys[0], 10.0, budget_s=min(args.cpu_budget, 60.0))
             out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
             out['speedup_vs_cpu_baseline_note'] = 'ratio to an EXTRAPOLATED figure (see cpu_baseline.sample): it says the reference cannot run this configuration, nothing about kernel quality'
@@ -727,11 +768,17 @@ def main():
                     help='--workload dual: 0 (default) = whole E-steps to convergence; K > 0 = K lockstep L-BFGS iterations (unit of work)')
     ap.add_argument('--resident', type=int, default=8192, help="--workload online: trials resident in HBM (all ranks hold the counts)")
     ap.add_argument('--batch', type=int, default=1024, help="--workload online: minibatch size (split over the ranks)")
-    ap.add_argument('--lean', action='store_true', help='skip the extra untimed iterations (per-family event breakdown, TNC M-step, MFMA peak probe): for runs under rocprofv3')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: events for the roofline figures, the extra untimed iterations, the CPU baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (--workload em)')
+    ap.add_argument('--lean', action='store_true', help='with --full: skip the extra untimed iterations (per-family event breakdown, TNC M-step, MFMA peak probe): for runs under rocprofv3')
     ap.add_argument('--opts', default='', help='context options key=value,... (experiments)')
     ap.add_argument('--events-every', type=int, default=4, help='HIP events around the GEMM launches on every n-th timed step (1: all of them)')
     ap.add_argument('--dry-run', action='store_true', help='launcher self-test: every rank reports its environment and exits (no GPU work)')
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != 'em' or args.config == 'c5'):
+        raise SystemExit('bench.py: --dump-outputs is implemented for --workload em')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         return spawn_ranks(args.gpus)
@@ -795,7 +842,9 @@ def main():
     cd_method = [args.cd_method]
     nll_hist, estep_ms, mstep_ms, facts, solves, pcgs, cdp, nwt_ms, nwt_bytes, ranks = [], [], [], [], [], [], [], [], [], []
     nwt_bytes_survey, nwt_bytes_moved = [], []
-    sess.ctx.set_option('time_newton', 1)           # two HIP events per inner solve: the Newton-solve kernels' time, next to their bytes
+    last = {}
+    if args.full:
+        sess.ctx.set_option('time_newton', 1)       # two HIP events per inner solve: the Newton-solve kernels' time, next to their bytes
 
     def em_step():
         nonlocal params, optim
@@ -804,6 +853,7 @@ def main():
         t1 = time.time()
         params, _ = funs.learning.updateParams(params, infRes, exp, CdOptimMethod=cd_method[0])
         t2 = time.time()
+        last.update(infRes=infRes, nll=nll)
         nll_hist.append(float(nll))
         estep_ms.append((t1 - t0) * 1e3)
         mstep_ms.append((t2 - t1) * 1e3)
@@ -811,37 +861,42 @@ def main():
         solves.append(sess.ctx.info('last_newton_solves'))
         pcgs.append(sess.ctx.info('last_pcg_iterations'))
         cdp.append(list(getattr(sess, '_cd_passes', (0, 0))))
-        nwt_ms.append(sess.ctx.info('last_newton_solve_ms'))
-        nwt_bytes.append(sess.ctx.info('last_newton_solve_bytes'))
-        nwt_bytes_survey.append(sess.ctx.info('last_newton_solve_bytes_survey'))
-        nwt_bytes_moved.append(sess.ctx.info('last_newton_solve_bytes_moved'))
+        if args.full:
+            nwt_ms.append(sess.ctx.info('last_newton_solve_ms'))
+            nwt_bytes.append(sess.ctx.info('last_newton_solve_bytes'))
+            nwt_bytes_survey.append(sess.ctx.info('last_newton_solve_bytes_survey'))
+            nwt_bytes_moved.append(sess.ctx.info('last_newton_solve_bytes_moved'))
         ranks.append(sess.ctx.info('lowrank_rtot'))
 
     for _ in range(args.warmup):
         em_step()
-    # HIP events (on the context's stream) around the GEMM launches of the timed region - the roofline kernel - on every 4th step: a pair of
+    # --full: HIP events (on the context's stream) around the GEMM launches of the timed region - the roofline kernel - on every 4th step: a pair of
     # events costs ~10 us of device time per launch (two barrier packets; tools/probes/launch_probe.hip: a bare launch is 3 us), ~400 launches per
     # step - recorded on every step the measurement itself was 4 % of the number it sits next to
     every = max(1, args.events_every)
-    sess.ctx.set_option('profile', 2)
-    sess.ctx.set_option('profile_pause', 1)
+    if args.full:
+        sess.ctx.set_option('profile', 2)
+        sess.ctx.set_option('profile_pause', 1)
     event_steps = []
     barrier()
     t_begin = time.time()
     for i in range(args.steps):
-        if i % every == 0:
+        if args.full and i % every == 0:
             sess.ctx.set_option('profile_pause', 0)
             event_steps.append(i)
         em_step()
-        if i % every == 0:
+        if args.full and i % every == 0:
             sess.ctx.set_option('profile_pause', 1)
     barrier()
     elapsed = time.time() - t_begin
-    gemm_ms, gemm_flops, gemm_launches = (sess.ctx.info('prof_gemm_' + k) for k in ('ms', 'flops', 'launches'))
-    gemm_max_ms, gemm_max_flops = sess.ctx.info('prof_gemm_max_ms'), sess.ctx.info('prof_gemm_max_flops')
-    ytm_ms, ytm_flops, ytm_launches = (sess.ctx.info('prof_mix_' + k) for k in ('ms', 'flops', 'launches'))
-    ytm_fused = sess.ctx.info('last_yt_mix_fused') == 1.0
-    sess.ctx.set_option('profile', 0)
+    if args.full:
+        gemm_ms, gemm_flops, gemm_launches = (sess.ctx.info('prof_gemm_' + k) for k in ('ms', 'flops', 'launches'))
+        gemm_max_ms, gemm_max_flops = sess.ctx.info('prof_gemm_max_ms'), sess.ctx.info('prof_gemm_max_flops')
+        ytm_ms, ytm_flops, ytm_launches = (sess.ctx.info('prof_mix_' + k) for k in ('ms', 'flops', 'launches'))
+        ytm_fused = sess.ctx.info('last_yt_mix_fused') == 1.0
+        sess.ctx.set_option('profile', 0)
+    if args.dump_outputs and rank == 0:
+        dump_em_outputs(args.dump_outputs, last['infRes'], last['nll'], params)
 
     def drop_last():
         for lst in (estep_ms, mstep_ms, nll_hist, facts, solves, pcgs, cdp, nwt_ms, nwt_bytes, nwt_bytes_survey, nwt_bytes_moved, ranks):
@@ -849,7 +904,7 @@ def main():
 
     # one more (untimed) EM iteration with events around every tagged launch: the per-kernel-family breakdown
     prof = {}
-    if not args.lean:
+    if args.full and not args.lean:
         sess.ctx.set_option('profile', 1)
         em_step()
         prof = {tag: sess.ctx.info('prof_%s_ms' % tag) for tag in ('gemm', 'mix', 'cd', 'potrf', 'poisson', 'vsm', 'assemble', 'solve')}
@@ -857,7 +912,7 @@ def main():
         drop_last()
     # one more (untimed) EM iteration with the reference engine's default (C,d) driver, for the record
     tnc_ms = None
-    if world == 1 and args.cd_method != 'TNC' and not args.lean:
+    if world == 1 and args.cd_method != 'TNC' and args.full and not args.lean:
         cd_method[0] = 'TNC'
         em_step()
         tnc_ms = mstep_ms[-1]
@@ -868,7 +923,7 @@ def main():
     # the settled fit without running it there - the last one is reported (the first two pay for the jump: modes far from the warm
     # start, then an extrapolated start across the jump)
     plateau = None
-    if not args.lean and args.config != 'c1':
+    if args.full and not args.lean and args.config != 'c1':
         keep = (params, optim)
         params = {k: np.asarray(v, dtype=np.float64).copy() for k, v in true_params.items()}
         for _ in range(4):
@@ -889,33 +944,8 @@ def main():
     ms_per_step = t_max / args.steps * 1e3
     value = (args.steps * total_trials / 1024.0) / t_max if args.config == 'c3' else args.steps / t_max
     timed = slice(args.warmup, args.warmup + args.steps)
-    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     warm_e = float(np.mean(estep_ms[timed]))
-    n_ms, n_by = float(np.sum(nwt_ms[timed])), float(np.sum(nwt_bytes[timed]))
-    n_by_survey = float(np.sum(nwt_bytes_survey[timed]))
-    n_by_moved = float(np.sum(nwt_bytes_moved[timed]))
     per_1024 = (total_trials / 1024.0) if args.config == 'c3' else 1.0
-    step_ms_on_events = max(1e-9, float(np.sum([estep_ms[args.warmup + i] + mstep_ms[args.warmup + i] for i in event_steps])))
-    roof_gemm = {'bound': 'mfma', 'kernel': 'gemm_mfma_kernel (FP64 16x16x4 MFMA: preconditioner applications, prior mat-vecs, factor/inverse/selected products)',
-                 'achieved': achieved, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / FP64_MATRIX_PEAK_TFLOPS,
-                 # HBM counters are not collected inside a timed run (rocprofv3 --pmc serialises kernels): null here; the per-round PMC
-                 # passes of this command are under profiles/ (rNN_pmc_hbm_traffic.json)
-                 'traffic': None,
-                 'algorithmic_flops_per_launch': gemm_flops / max(gemm_launches, 1.0), 'launches': gemm_launches, 'avg_launch_ms': gemm_ms / max(gemm_launches, 1.0),
-                 # (events on these steps of the timed region only; share = GEMM time of those steps / their wall time)
-                 'events_on_steps': event_steps, 'kernel_share_of_step': gemm_ms / step_ms_on_events,
-                 # the longest single launch of the timed region
-                 'largest_launch': {'ms': gemm_max_ms, 'algorithmic_flops': gemm_max_flops,
-                                    'achieved': gemm_max_flops / (gemm_max_ms * 1e-3) / 1e12 if gemm_max_ms > 0 else 0.0,
-                                    'frac': gemm_max_flops / (gemm_max_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS if gemm_max_ms > 0 else 0.0}}
-    roof_cov = None if not (ytm_fused and ytm_ms > 0) else {
-        'bound': 'mfma', 'kernel': 'yt_mix_kernel (FP64 16x16x4 MFMA products + FP64 vector mixing in registers; writes the FP32 correction D and post_vsm)',
-        'achieved': ytm_flops / (ytm_ms * 1e-3) / 1e12, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-        'frac': ytm_flops / (ytm_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
-        # HBM bytes per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE): from the committed passes, not from this run - see traffic_source
-        'traffic': (pmc_traffic('yt_mix_kernel') or {}).get('bytes_per_launch'), 'traffic_source': (pmc_traffic('yt_mix_kernel') or {}).get('source'),
-        'algorithmic_flops_per_launch': ytm_flops / max(ytm_launches, 1.0), 'launches': ytm_launches, 'avg_launch_ms': ytm_ms / max(ytm_launches, 1.0),
-        'events_on_steps': event_steps, 'kernel_share_of_step': ytm_ms / step_ms_on_events}
     out = {
         'metric': 'EM iterations/sec',
         'value': value,
@@ -924,10 +954,6 @@ def main():
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
         'config': {'workload': '%s: %d neurons, %d latents, %d bins, %d trials per GPU, Laplace batch EM (warm-started E-step; M-step: (C,d) by %s, tau by the 4-point lockstep root finder)'
                                % (args.config, q, p, T, R, 'device per-neuron Newton' if args.cd_method == 'newton' else 'scipy ' + args.cd_method), 'trials_total': total_trials, 'parallelism': 'trial-sharded x%d' % world},
-        # the rate of a settled fit (see above) and the rate a caller gets with the reference engine's default (C,d) driver (scipy TNC)
-        'value_at_plateau': None if plateau is None else per_1024 * 1e3 / (plateau['estep_ms'] + plateau['mstep_ms']),
-        'plateau': plateau,
-        'value_reference_defaults': None if tnc_ms is None else per_1024 * 1e3 / (warm_e + tnc_ms),
         'estep_ms_per_trial': warm_e / R,
         'estep_ms': [round(x, 1) for x in estep_ms], 'mstep_ms': [round(x, 1) for x in mstep_ms],
         'estep_ms_cold_start': round(estep_ms[0], 1), 'estep_ms_warm_mean': round(warm_e, 1),
@@ -937,27 +963,59 @@ def main():
         'pcg_iterations_per_trial': [round(f / R, 2) for f in pcgs],
         'cd_newton_passes_full_chord': cdp,
         'nll': nll_hist,
-        'mstep_ms_with_reference_default_TNC': tnc_ms,
-        'kernel_time_ms_one_untimed_step': {k: round(v, 1) for k, v in prof.items()},
-        # The line's `roofline` names the dominant kernel of the step - the top row of the rocprof summary (profiles/rNN_c3_bench_kernel_stats.csv):
-        # Yt = F L^-T and its mixing in one launch per E-step (csrc/ytmix.h).  HIP events (on the context's stream) around it on the sampled steps of
-        # the timed region; flops = products over the triangular panels + the per-(bin, column) mixing (csrc/cov.hip); traffic: the committed PMC
-        # passes (profiles/rNN_pmc_hbm_traffic.json).  The GEMM family (a pool of ~165 launches of a dozen shapes) follows as `roofline_gemm`.
-        'roofline': roof_cov if roof_cov is not None else roof_gemm,
-        'roofline_gemm': roof_gemm,
-        'roofline_covariance': roof_cov,
-        # the Newton solve (north star: >= 40 % of the HBM roofline): every inner PCG solve of the timed region between two HIP events.  `frac` prices
-        # the bytes the kernels really MOVE (round 6; z, s, p, q, t / y of a solve are stored in single precision - csrc/estep.hip: newton_bytes_moved);
-        # the 17-pass FP64 model of rounds 3-5 and SURVEY 8(d)'s B_E = q T + 8 (2 p T + T p^2) bytes per pass per trial are printed next to it so that
-        # the fraction cannot move by accounting
-        'roofline_newton': {'bound': 'hbm', 'bytes': n_by_moved, 'ms': n_ms, 'achieved': n_by_moved / (n_ms * 1e-3) / 1e9 if n_ms > 0 else 0.0, 'peak': HBM_PEAK_GBS,
-                            'unit': 'GB/s', 'frac': n_by_moved / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
-                            'byte_model': 'bytes moved by the kernels of the step as built (per slot-iteration: n-vector passes at their storage width + packed FP32 curvature; operators once per step)',
-                            'bytes_17pass_fp64_model': n_by, 'frac_17pass_fp64_model': n_by / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
-                            'bytes_survey_model': n_by_survey, 'frac_survey_model': n_by_survey / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
-                            'ms_per_em_iteration': n_ms / args.steps, 'pcg_iterations_per_trial_per_estep': float(np.mean(pcgs[timed])) / R},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        n_ms, n_by = float(np.sum(nwt_ms[timed])), float(np.sum(nwt_bytes[timed]))
+        n_by_survey = float(np.sum(nwt_bytes_survey[timed]))
+        n_by_moved = float(np.sum(nwt_bytes_moved[timed]))
+        step_ms_on_events = max(1e-9, float(np.sum([estep_ms[args.warmup + i] + mstep_ms[args.warmup + i] for i in event_steps])))
+        roof_gemm = {'bound': 'mfma', 'kernel': 'gemm_mfma_kernel (FP64 16x16x4 MFMA: preconditioner applications, prior mat-vecs, factor/inverse/selected products)',
+                     'achieved': achieved, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / FP64_MATRIX_PEAK_TFLOPS,
+                     # HBM counters are not collected inside a timed run (rocprofv3 --pmc serialises kernels): null here; the per-round PMC
+                     # passes of this command are under profiles/ (rNN_pmc_hbm_traffic.json)
+                     'traffic': None,
+                     'algorithmic_flops_per_launch': gemm_flops / max(gemm_launches, 1.0), 'launches': gemm_launches, 'avg_launch_ms': gemm_ms / max(gemm_launches, 1.0),
+                     # (events on these steps of the timed region only; share = GEMM time of those steps / their wall time)
+                     'events_on_steps': event_steps, 'kernel_share_of_step': gemm_ms / step_ms_on_events,
+                     # the longest single launch of the timed region
+                     'largest_launch': {'ms': gemm_max_ms, 'algorithmic_flops': gemm_max_flops,
+                                        'achieved': gemm_max_flops / (gemm_max_ms * 1e-3) / 1e12 if gemm_max_ms > 0 else 0.0,
+                                        'frac': gemm_max_flops / (gemm_max_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS if gemm_max_ms > 0 else 0.0}}
+        roof_cov = None if not (ytm_fused and ytm_ms > 0) else {
+            'bound': 'mfma', 'kernel': 'yt_mix_kernel (FP64 16x16x4 MFMA products + FP64 vector mixing in registers; writes the FP32 correction D and post_vsm)',
+            'achieved': ytm_flops / (ytm_ms * 1e-3) / 1e12, 'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+            'frac': ytm_flops / (ytm_ms * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
+            # HBM bytes per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE): from the committed passes, not from this run - see traffic_source
+            'traffic': (pmc_traffic('yt_mix_kernel') or {}).get('bytes_per_launch'), 'traffic_source': (pmc_traffic('yt_mix_kernel') or {}).get('source'),
+            'algorithmic_flops_per_launch': ytm_flops / max(ytm_launches, 1.0), 'launches': ytm_launches, 'avg_launch_ms': ytm_ms / max(ytm_launches, 1.0),
+            'events_on_steps': event_steps, 'kernel_share_of_step': ytm_ms / step_ms_on_events}
+        out.update({
+            # the rate of a settled fit (see above) and the rate a caller gets with the reference engine's default (C,d) driver (scipy TNC)
+            'value_at_plateau': None if plateau is None else per_1024 * 1e3 / (plateau['estep_ms'] + plateau['mstep_ms']),
+            'plateau': plateau,
+            'value_reference_defaults': None if tnc_ms is None else per_1024 * 1e3 / (warm_e + tnc_ms),
+            'mstep_ms_with_reference_default_TNC': tnc_ms,
+            'kernel_time_ms_one_untimed_step': {k: round(v, 1) for k, v in prof.items()},
+            # The line's `roofline` names the dominant kernel of the step - the top row of the rocprof summary (profiles/rNN_c3_bench_kernel_stats.csv):
+            # Yt = F L^-T and its mixing in one launch per E-step (csrc/ytmix.h).  HIP events (on the context's stream) around it on the sampled steps of
+            # the timed region; flops = products over the triangular panels + the per-(bin, column) mixing (csrc/cov.hip); traffic: the committed PMC
+            # passes (profiles/rNN_pmc_hbm_traffic.json).  The GEMM family (a pool of ~165 launches of a dozen shapes) follows as `roofline_gemm`.
+            'roofline': roof_cov if roof_cov is not None else roof_gemm,
+            'roofline_gemm': roof_gemm,
+            'roofline_covariance': roof_cov,
+            # the Newton solve (north star: >= 40 % of the HBM roofline): every inner PCG solve of the timed region between two HIP events.  `frac` prices
+            # the bytes the kernels really MOVE (round 6; z, s, p, q, t / y of a solve are stored in single precision - csrc/estep.hip: newton_bytes_moved);
+            # the 17-pass FP64 model of rounds 3-5 and SURVEY 8(d)'s B_E = q T + 8 (2 p T + T p^2) bytes per pass per trial are printed next to it so that
+            # the fraction cannot move by accounting
+            'roofline_newton': {'bound': 'hbm', 'bytes': n_by_moved, 'ms': n_ms, 'achieved': n_by_moved / (n_ms * 1e-3) / 1e9 if n_ms > 0 else 0.0, 'peak': HBM_PEAK_GBS,
+                                'unit': 'GB/s', 'frac': n_by_moved / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
+                                'byte_model': 'bytes moved by the kernels of the step as built (per slot-iteration: n-vector passes at their storage width + packed FP32 curvature; operators once per step)',
+                                'bytes_17pass_fp64_model': n_by, 'frac_17pass_fp64_model': n_by / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
+                                'bytes_survey_model': n_by_survey, 'frac_survey_model': n_by_survey / (n_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if n_ms > 0 else 0.0,
+                                'ms_per_em_iteration': n_ms / args.steps, 'pcg_iterations_per_trial_per_estep': float(np.mean(pcgs[timed])) / R},
+        })
+    if args.full and not args.no_cpu_baseline and world == 1:
         out['cpu_baseline'] = cpu_baseline(q, p, T, R, true_params, Ys[0], bin_ms, init, estimate=args.cpu_estimate, budget_s=args.cpu_budget)
         out['speedup_vs_cpu_baseline'] = (args.steps / t_max) / out['cpu_baseline']['value']
         out['speedup_vs_cpu_baseline_note'] = 'ratio to the cpu_baseline sample as described there'

@@ -530,6 +530,43 @@ def test_bench_launcher_reports_a_rank_stuck_in_comm_init():
     assert float(re.search(r"PGPFA_BENCH_TIMEOUT', '(\d+)'", src).group(1)) <= 900
 
 
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files of the last timed step's parameters, nll and posterior - every trial's post_mean at config 3's
+    size, a fixed seeded sample of trials past the budget, post_vsm of 16 sampled trials (their positions written next to them), under 64 MB;
+    the workloads that write no outputs refuse the option before any work."""
+    import bench
+    from funs._session import LazyTrialList
+
+    class Posterior(dict):                         # stand-in for the device-backed infRes: entry i of every list holds the value i
+        def __init__(self, n, p, T):
+            super().__init__(post_mean=LazyTrialList(n, lambda i: np.full((p, T), float(i))),
+                             post_vsm=LazyTrialList(n, lambda i: np.full((T, p, p), float(i))))
+
+        def materialize(self, keys):
+            return self
+    params = {'C': np.ones((200, 10)), 'd': np.zeros(200), 'tau': np.full(10, 0.1)}
+    for n in (1024, 4096):
+        out = tmp_path / str(n)
+        bench.dump_em_outputs(str(out), Posterior(n, 10, 500), -1.5, params)
+        arr = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+        assert sorted(arr) == ['C', 'd', 'nll', 'post_mean', 'post_mean_trials', 'post_vsm', 'post_vsm_trials', 'tau']
+        assert all(a.dtype == np.float64 for a in arr.values())
+        assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) < 64e6
+        assert np.array_equal(arr['C'], params['C']) and arr['nll'].tolist() == [-1.5]
+        assert np.array_equal(arr['post_mean'][:, 0, 0], arr['post_mean_trials']) and np.array_equal(arr['post_vsm'][:, 0, 0, 0], arr['post_vsm_trials'])
+        assert arr['post_vsm'].shape == (16, 500, 10, 10) and len(set(arr['post_vsm_trials'])) == 16
+        if n == 1024:
+            assert np.array_equal(arr['post_mean_trials'], np.arange(n))
+        else:
+            assert 1000 < len(arr['post_mean_trials']) < n and np.all(np.diff(arr['post_mean_trials']) > 0)
+    again = tmp_path / 'again'
+    bench.dump_em_outputs(str(again), Posterior(4096, 10, 500), -1.5, params)
+    assert np.array_equal(np.load(str(again / 'post_mean_trials.npy')), np.load(str(tmp_path / '4096' / 'post_mean_trials.npy')))
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'dual', '--dump-outputs', str(tmp_path / 'x')],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and '--dump-outputs is implemented for --workload em' in out.stderr and not (tmp_path / 'x').exists()
+
+
 def test_header_documents_every_option_and_info_key():
     """include/pgpfa.h is the C-ABI's documentation: every key pgpfa_set_option accepts and every info key the library sets is named there."""
     import re

@@ -429,6 +429,30 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert line['n_gpus'] == 2 and line['value'] > 0
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps EM iterations and leaves the --full measurements out (CPU baseline, roofline events, untimed
+    extra iterations); --dump-outputs writes the last timed step's parameters, nll and posterior, the same from run to run."""
+    import json
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / ('out%d' % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--config', 'c1', '--steps', '3', '--warmup', '1',
+                              '--dump-outputs', str(out_dir)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line['metric'] == 'EM iterations/sec' and line['higher_is_better'] is True and line['dtype'] == 'f64' and line['steps'] == 3
+        assert abs(line['value'] - 1e3 / line['ms_per_step']) <= 1e-9 * line['value']
+        assert len(line['nll']) == len(line['estep_ms']) == 4
+        assert not any(key in line for key in ('cpu_baseline', 'roofline', 'roofline_newton', 'plateau', 'value_reference_defaults'))
+        arr = {f[:-4]: np.load(str(out_dir / f)) for f in os.listdir(str(out_dir))}
+        assert sorted(arr) == ['C', 'd', 'nll', 'post_mean', 'post_mean_trials', 'post_vsm', 'post_vsm_trials', 'tau']
+        assert arr['C'].shape == (30, 3) and arr['post_mean'].shape == (20, 3, 100) and arr['post_vsm'].shape == (16, 100, 3, 3)
+        assert arr['nll'][0] == line['nll'][-1] and np.all(np.isfinite(arr['post_mean']))
+        dumps.append(arr)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # synthetic population drawn on the device (SURVEY 8f row 1; reference recipe util.py:705-750)
 # ---------------------------------------------------------------------------------------------------------------

@@ -5,16 +5,16 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_c3_driver_protocol.json 2> $O/bench_c3.err
-python bench.py --config c2 --steps 20 --warmup 5 > $O/bench_c2.json 2>/dev/null
-python bench.py --config c1 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_c1.json 2>/dev/null
-python bench.py --workload online --steps 6 --warmup 2 > $O/bench_c4_online.json 2>/dev/null
-python bench.py --workload online --steps 6 --warmup 2 --tau-method TNC --no-cpu-baseline --lean > $O/bench_c4_online_reference_tau_TNC.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c3_driver_protocol.json 2> $O/bench_c3.err
+python bench.py --full --config c2 --steps 20 --warmup 5 > $O/bench_c2.json 2>/dev/null
+python bench.py --full --config c1 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_c1.json 2>/dev/null
+python bench.py --full --workload online --steps 6 --warmup 2 > $O/bench_c4_online.json 2>/dev/null
+python bench.py --full --workload online --steps 6 --warmup 2 --tau-method TNC --no-cpu-baseline --lean > $O/bench_c4_online_reference_tau_TNC.json 2>/dev/null
 PGPFA_PLAN_TRACE=1 python tools/jump_probe.py 6 > $O/jump_probe.txt 2>&1
 PGPFA_PLAN_TRACE=1 python tools/jump_probe.py 6 extrapolate_guard=0 start_guard=0 workspace_grow_budget_ms=0 > $O/jump_probe_round5_behaviour.txt 2>&1
-python bench.py --workload floor --steps 3 --warmup 1 --trials 128 > $O/bench_c3_floor_dense_engine.json 2>/dev/null
-python bench.py --workload dual --config c5 --trials 256 > $O/bench_c5_dual_estep_mixed.json 2>/dev/null
-python bench.py --workload dual --config c5 --trials 256 --precision f64 > $O/bench_c5_dual_estep_f64.json 2>/dev/null
+python bench.py --full --workload floor --steps 3 --warmup 1 --trials 128 > $O/bench_c3_floor_dense_engine.json 2>/dev/null
+python bench.py --full --workload dual --config c5 --trials 256 > $O/bench_c5_dual_estep_mixed.json 2>/dev/null
+python bench.py --full --workload dual --config c5 --trials 256 --precision f64 > $O/bench_c5_dual_estep_f64.json 2>/dev/null
 python bench.py --workload dual --config c5 --trials 256 --dual-iters 6 --warmup 1 > $O/bench_c5_dual_unit_mixed.json 2>/dev/null
 python bench.py --workload dual --config c5 --trials 256 --dual-iters 6 --warmup 1 --precision f64 > $O/bench_c5_dual_unit_f64.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp

@@ -12,6 +12,6 @@ if [ $RC -ge 128 ] || grep -q "Fatal Python error" $LOG; then
   cat /proc/sys/kernel/core_pattern
   CORE=$(ls -t core core.* /tmp/core* 2>/dev/null | head -1)
   echo "interpreter died (rc $RC), core: $CORE"
-  if [ -n "$CORE" ]; then /opt/rocm/bin/rocgdb -batch -ex bt -ex "info threads" python "$CORE" > $LOG.bt 2>&1; grep -n "^#" $LOG.bt | head -40; fi
+  if [ -n "$CORE" ]; then gdb -batch -ex bt -ex "info threads" python "$CORE" > $LOG.bt 2>&1; grep -n "^#" $LOG.bt | head -40; fi
 fi
 exit $RC

@@ -142,7 +142,12 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * slab start on 128-byte lines), "dual_gemm" (1: the neuron contractions of the dual evaluation as GEMMs against a pair / loading table),
  * "cd_debug" (0; measurement only: bit switches that drop the exp / the products / the staging of the (C,d) kernels, tools/cd_probe.py). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
-/* Info: "chunk_trials", "plan_lowrank", "n_pad", "lowrank_rtot", "last_estep_ms", "last_newton_factorizations",
+/* Options that pgpfa_set_params builds from - "eps_noise" (Gram matrices, their inverses, the low-rank factors), "lowrank_tol" (the low-rank
+ * factors), "rank_gran", "thin_products" and "use_mfma" (the rank tables: compact offsets need both) - re-run it with the stored parameters
+ * when they change after it, so an option set before or after pgpfa_set_params gives the same numbers. */
+/* Info: "chunk_trials", "plan_lowrank", "n_pad", "lowrank_rtot" (total rank of the r x r system), "lowrank_rtot16" (the same with every
+ * latent's rank rounded up to 16: roff16[p], the rows the products with F take), "lowrank_compact" (1: compact rank offsets are live,
+ * "rank_gran" 4 or 8 - lowrank_rtot < lowrank_rtot16 when they save rows), "last_estep_ms", "last_newton_factorizations",
  * "last_newton_solves", "last_pcg_iterations", "last_shared_factorizations", "last_cov_lowrank",
  * "last_dense_retries", "hbm_bytes_allocated", "hbm_bytes_free" / "hbm_bytes_total" (hipMemGetInfo of the context's device, now), "n_trials_global", "prof_<tag>_{ms,flops,launches}" (tags gemm, potrf, solve, poisson, assemble, vsm, cd, mix; "prof_mix_flops" counts BYTES for the stand-alone mixing
  * passes and FLOPs - products + mixing - when "last_yt_mix_fused" is 1), "counts_two_bytes",

@@ -145,6 +145,24 @@ def marginal_blocks(Sigma, p, T):
     return vsmGP, vsm
 
 
+def laplace_cov_at(X, C, d, tau, T, binSize):
+    """post_vsm (T,p,p) and post_vsmGP (T,T,p) of inference.py:130-172 at a GIVEN mode X (p,T): the dense
+    p T x p T Hessian of nlp_hess inverted in FP64, then marginal_blocks.  The yardstick for a device
+    covariance at the device's own mode (the Hessian does not depend on the counts).
+
+    The inverse is LAPACK's LU one (getrf / getri through np.linalg.inv, as the reference, inference.py:131),
+    not Cholesky's: at c3_spot.npz's polished mode dpotrf / dpotri (also scaled to a unit diagonal, also
+    through cho_solve) land 1.2e-9 of the largest entry away from that inverse after one step of iterative
+    refinement, the LU inverse 5.6e-13 - too far for a yardstick of 1e-8."""
+    C = np.asarray(C, dtype=np.float64)
+    d = np.asarray(d, dtype=np.float64).reshape(-1)
+    p = C.shape[1]
+    Kinv = np.linalg.inv(make_K(tau, T, binSize))
+    H = nlp_hess(np.asarray(X, dtype=np.float64).reshape(p, T), None, C, d, Kinv)
+    vsmGP, vsm = marginal_blocks(np.linalg.inv(H), p, T)
+    return vsm, vsmGP
+
+
 def newton_mode(Y, C, d, Kinv, x0=None, xtol=1e-11, max_iter=100):
     """Exact (polished) Laplace mode by damped Newton on the structured objective.
 

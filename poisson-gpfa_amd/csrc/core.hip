@@ -836,6 +836,8 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
     HIPC(hipGetLastError());
   }
   c->info["lowrank_rtot"] = c->rtot;
+  c->info["lowrank_rtot16"] = c->rtot16;
+  c->info["lowrank_compact"] = c->rank_compact ? 1.0 : 0.0;
   c->flr32_valid = false;
   return 0;
 }
@@ -1016,7 +1018,13 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   const std::string k(key);
   if (k == "newton_xtol") c->xtol = v;
   else if (k == "newton_max_iter") c->max_iter = (int)v;
-  else if (k == "use_mfma") c->mfma = (v != 0.0);
+  else if (k == "use_mfma") {
+    const bool was = c->mfma;
+    c->mfma = (v != 0.0);
+    // (compact rank offsets need the thin products, which need the matrix cores: rebuild the rank tables, as for thin_products)
+    if (c->have_params && c->rank_gran != 16 && was != c->mfma)
+      CHK(pgpfa_set_params(c, std::vector<double>(c->hC).data(), std::vector<double>(c->hd).data(), std::vector<double>(c->htau).data()));
+  }
   else if (k == "cd_mfma") c->cd_mfma = (v != 0.0);
   else if (k == "cd_hess_mfma") c->cd_hess_mfma = (v != 0.0);
   else if (k == "cross_kernel") c->cross_kernel = (v != 0.0);
@@ -1056,7 +1064,13 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "split_cov") c->split_cov = (v != 0.0);
   else if (k == "split_max_norm") c->split_max_norm = v;
   else if (k == "cov_mode") c->cov_mode = (int)v;
-  else if (k == "lowrank_tol") c->lr_tol = v;
+  else if (k == "lowrank_tol") {
+    const bool changed = c->lr_tol != v;
+    c->lr_tol = v;
+    // (the low-rank factors are built in pgpfa_set_params)
+    if (c->have_params && changed)
+      CHK(pgpfa_set_params(c, std::vector<double>(c->hC).data(), std::vector<double>(c->hd).data(), std::vector<double>(c->htau).data()));
+  }
   else if (k == "keep_trial_vsmgp") c->keep_trial_vsmgp = (v != 0.0);
   else if (k == "dual_lowrank") c->dual_lowrank = (v != 0.0);
   else if (k == "dual_f32") c->dual_f32 = (int)v;
@@ -1087,7 +1101,13 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "workspace_grow_floor_slots") c->grow_floor_slots = std::max(1, (int)v);
   else if (k == "workspace_granule_mb") c->vmm_granule = (size_t)std::max(2.0, v) << 20;
   else if (k == "workspace_vmm") { if (c->arena_cap > 0) return fail("workspace_vmm must be set before the first E-step"); c->vmm = (v != 0.0) ? 0 : -1; }
-  else if (k == "eps_noise") c->eps = v;
+  else if (k == "eps_noise") {
+    const bool changed = c->eps != v;
+    c->eps = v;
+    // (the Gram matrices, their inverses and the low-rank factors are built from it in pgpfa_set_params; the E-step reads it directly)
+    if (c->have_params && changed)
+      CHK(pgpfa_set_params(c, std::vector<double>(c->hC).data(), std::vector<double>(c->hd).data(), std::vector<double>(c->htau).data()));
+  }
   else if (k == "profile") {
     // 0: off (the accumulated sums stay readable), 1: time every tagged launch, 2: GEMM launches only
     if (v != 0.0) {

@@ -192,6 +192,8 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
     // the two block-diagonal products as kernels of their own (thin.h) where the matrix cores are in use; the general product otherwise
     const bool thin = c->thin_products && c->mfma && c->T >= 4 && (size_t)c->rpad <= (size_t)c->ld;
     if ((vec_row > 0 || vec_f32) && (!thin || first_apply || final_apply)) return fail("internal: padded vector rows need the thin products and no per-bin application");
+    // (the general GEMM's row-tile tables start tiles on multiples of 16: compact offsets must never reach it)
+    if (c->rank_compact && !(thin && c->thin_products >= 2)) return fail("internal: compact rank offsets without the thin products (rank tables are stale)");
     ThinP tp{};
     tp.F = c->Flr; tp.Tf = c->Tp; tp.T = c->T; tp.Tx = vec_row > 0 ? vec_row : c->T; tp.FT = c->FTbig; tp.ldft = c->rpad;
     tp.cols = cols; tp.n_dev = (cols && c->cur_ndev) ? c->cur_ndev : nullptr; tp.ncols = ng; tp.skip = skip;

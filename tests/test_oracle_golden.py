@@ -222,3 +222,33 @@ def test_oracle_with_counts_above_255():
     assert np.max(np.abs(orc.mstep_cd_grad(g['v1'], Ys, ref_res['post_mean'], ref_res['post_vsm'], p, q) - g['grad1'])) <= 1e-11 * np.max(np.abs(g['grad1']))
     assert abs(orc.dual_cost(g['lam'], ybar, C_big, K_big, Kinv_big, d_big) - float(g['dual_cost'])) <= 1e-10 * abs(float(g['dual_cost']))
     assert np.max(np.abs(orc.dual_grad(g['lam'], ybar, C_big, K_big, Kinv_big, d_big) - g['dual_grad'])) <= 1e-9 * np.max(np.abs(g['dual_grad']))
+
+
+def test_laplace_cov_at_a_given_mode_vs_reference():
+    """orc.laplace_cov_at - the dense FP64 yardstick (dpotrf / dpotri of the full p T x p T Hessian) that the GPU tests
+    compare the covariance engine with at the DEVICE's modes - against the reference's own inverse (inference.py:130-172)
+    at the reference's modes: c3_spot.npz's polished mode (200 x 10 x 500) and c1_laplace.npz's raw modes of all 20
+    trials, blocks and PautoSum (learning.py:145-173) to 1e-10 of the largest entry."""
+    g = load_golden('c3_spot.npz')
+    p, T = 10, 500
+    vsm, G = orc.laplace_cov_at(g['polished'].reshape(p, T), g['init_C'], g['init_d'], g['init_tau'], T, float(g['binSize']))
+    e = (rel(vsm, g['polished_vsm']), rel(np.stack([np.diag(G[:, :, k]) for k in range(p)]), g['polished_vsmGP_diag']),
+         rel(G[::50, :, :], g['polished_vsmGP_rows']))
+    print('c3 polished: post_vsm %.2e, post_vsmGP diagonal %.2e, rows %.2e' % e)
+    assert max(e) <= 1e-10
+    c1 = load_golden('c1_dataset.npz')
+    lap = load_golden('c1_laplace.npz')
+    p, T = 3, 100
+    P = np.zeros((p, T, T))
+    worst = 0.0
+    for r in range(lap['post_mean'].shape[0]):
+        m = lap['post_mean'][r]
+        vsm, G = orc.laplace_cov_at(m, c1['init_C'], c1['init_d'], c1['init_tau'], T, float(c1['binSize']))
+        worst = max(worst, rel(vsm, lap['post_vsm'][r]))
+        if r == 0:
+            e0 = rel(G, lap['post_vsmGP_trial0'])
+        for k in range(p):
+            P[k] += G[:, :, k] + np.outer(m[k], m[k])
+    eP = rel(P, lap['PautoSum'])
+    print('c1 raw modes: post_vsm %.2e (worst of 20 trials), post_vsmGP trial 0 %.2e, PautoSum %.2e' % (worst, e0, eP))
+    assert worst <= 1e-10 and e0 <= 1e-10 and eP <= 1e-10

@@ -311,6 +311,9 @@ __global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, lo
   }
 }
 
+// INVARIANT (read by the LDS-DMA panel staging of yt_mix, ytmix.h): every diagonal NB x NB block of Mt is written WHOLE here, and Dinv holds zeros
+// on the other side of its diagonal (potrf_diag_kernel_t above) - so Mt is zero below the diagonal INSIDE its diagonal blocks, whatever an earlier
+// use of the slab left there.  (Below the diagonal blocks it is not: nobody may read that.)
 // Mt[jblk, jblk] = Dinv[jb]^T for the diagonal block at k0 + blockIdx.y * NB (grid = (slots, blocks): every diagonal block of a factorisation in one
 // launch - they only depend on the factor; a launch per block column was 21 us of per-workgroup latency each, 26 launches per E-step)
 template <typename T>

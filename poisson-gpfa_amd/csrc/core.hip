@@ -787,6 +787,11 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
       const int last = std::min((int)b * 16 + 15, c->rtot - 1);
       nrtab[b] = std::min(c->rtot16, round_up(pmap[last] + 1, 16));
     }
+    // The DMA form of yt_mix's panel staging (ytmix.h) moves whole row PAIRS, 16 bytes from a 16-byte aligned address: a pair is padding as a
+    // whole or two consecutive slab rows from an even one (real rows come in multiples of 4 from a multiple of 4).  A table that breaks this is an error.
+    for (int i = 0; i + 1 < n16; i += 2)
+      if (cmap[i] < 0 ? cmap[i + 1] >= 0 : ((cmap[i] & 1) != 0 || cmap[i + 1] != cmap[i] + 1))
+        return fail("rank tables: padded rows %d, %d map to slab rows %d, %d - not a pair the panel staging can move whole", i, i + 1, cmap[i], cmap[i + 1]);
     CHK(upload_list(c, c->d_cmap, cmap));
     CHK(upload_list(c, c->d_nrtab, nrtab));
   }
@@ -940,6 +945,7 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   c->tab_cap = 4 * ((size_t)c->ld / 64 + 2 * (size_t)p + 4);
   rc |= dmalloc(c, &c->d_kr_ft, c->tab_cap); rc |= dmalloc(c, &c->d_kr_f, c->tab_cap);
   rc |= dmalloc(c, &c->sink, 128, true);
+  rc |= dmalloc(c, &c->zero16, 2, true);
   rc |= dmalloc(c, &c->d_thin_ft, c->tab_cap); rc |= dmalloc(c, &c->d_thin_f, c->tab_cap); rc |= dmalloc(c, &c->d_thin_s, c->tab_cap);
   rc |= dmalloc(c, &c->Fbig, (size_t)c->ld * c->ld + 256 * (size_t)c->ld, true); rc |= dmalloc(c, &c->FTbig, (size_t)c->ld * c->ld + 256 * (size_t)c->ld, true);
   rc |= dmalloc(c, &c->Gbar, (size_t)T * p * p + 64); rc |= dmalloc(c, &c->Wtbar, (size_t)T * p * p + 64); rc |= dmalloc(c, &c->d_blk_lat, (size_t)p * c->Tp / 16 + 64); rc |= dmalloc(c, &c->d_blk_col, (size_t)p * c->Tp / 16 + 64);
@@ -1044,6 +1050,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "vsm_b4") c->vsm_b4 = (int)v;
   else if (k == "poisson_tiles") c->poisson_tiles = (int)v;
   else if (k == "yt_mix_dbg") c->yt_mix_dbg = (int)v;
+  else if (k == "yt_mix_dma") c->yt_mix_dma = (v != 0.0);
   else if (k == "syrk_dbg") c->syrk_dbg = (int)v;
   else if (k == "syrk_tile") c->syrk_tile = (int)v;
   else if (k == "mix_wide") c->mix_wide = (int)v;

@@ -168,8 +168,14 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
         a.ncmap = c->rank_compact ? round_up(c->rtot16, (int)NB) : 0;
         if (ytmix_lds(PW) + (size_t)a.ncmap * sizeof(int) > (size_t)160 * 1024) a.ncmap = 0;     // (the kernel then reads the map from memory)
         const size_t lds = ytmix_lds(PW) + (size_t)a.ncmap * sizeof(int);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&yt_mix_kernel<PW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(yt_mix_kernel<PW>, dim3((unsigned)(a.nbx * nb)), dim3(YTM_THREADS), lds, c->st, a);
+        a.zero16 = c->zero16;
+        // (the DMA form reads the row map from its LDS copy only, and moves 16 bytes from 16-byte aligned addresses: even strides, an aligned slab)
+        const bool dma = c->yt_mix_dma && c->zero16 && (!a.cmap || a.ncmap > 0) && rpad % 2 == 0 && lw.sM % 2 == 0 && (reinterpret_cast<uintptr_t>(lw.Mt) & 15) == 0;
+        auto launch = [&](auto kern) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          hipLaunchKernelGGL(kern, dim3((unsigned)(a.nbx * nb)), dim3(YTM_THREADS), lds, c->st, a);
+        };
+        if (dma) launch(&yt_mix_kernel<PW, true>); else launch(&yt_mix_kernel<PW, false>);
       }
     });
     prof_end(c);

@@ -243,6 +243,7 @@ struct pgpfa_ctx {
   bool last_cov_lowrank = false;
   bool shared_pcg = true;
   bool pcg_trace = false;
+  double* zero16 = nullptr;                      // 16 zero bytes: what the LDS-DMA staging of yt_mix reads in place of rows it must not stage
   double* sink = nullptr;                        // 128 doubles nobody reads: where the rows past p of mix_vsm_wide2_kernel store
   int mix_wide = 1;                              // 1: the mixing pass of 17..20 latents with lanes along the bins (mix_vsm_wide2_kernel); 0: mix_vsm_wide_kernel
   int poisson_tiles = 2;                      // option poisson_tiles: 16-bin tiles per wave of the matrix-core Poisson pass up to 10 latents (2: the table fragments of a neuron tile serve two tiles; 1)
@@ -251,6 +252,7 @@ struct pgpfa_ctx {
   int yt_mix = 1;                             // option yt_mix: Yt = F L^-T and the mixing pass of the split form as one kernel up to 10 latents - Yt is never written (ytmix.h)
   int syrk_tile = 256;                        // option syrk_tile: workgroup tile of the FP16 term of the split sum (256 where T > 256 and the strides allow; 128)
   int syrk_dbg = 0;                           // option syrk_dbg: timing experiments on syrk_f16x2_kernel (parts switched off, results wrong)
+  int yt_mix_dma = 1;                         // option yt_mix_dma: that kernel stages the panels of L^-T by LDS-DMA, a chunk ahead of the products (ytmix.h); 0: through registers, behind them
   int yt_mix_dbg = 0;                         // option yt_mix_dbg: timing experiments on that kernel (parts switched off, results wrong); never set outside tools/
   int mix_slot = 3;                           // option mix_slot (3: two column halves per bin, two workgroups per CU - mix_slot3_kernel; 2: mix_slot2_kernel): the mixing pass of the split form with a thread per bin and whole columns per workgroup (split.h)
   bool cross_kernel = true;                       // option cross_kernel = 0: the cross term of the split form through the general GEMM kernel

@@ -9,12 +9,13 @@
 // per workgroup), stores D and adds the pair sums of post_vsm.  Yt never exists in memory.
 //
 // Operands: the column block's panel of L^-T (rows 0 .. b0 + 15 - it is upper triangular - of 16 columns) is staged once per workgroup in LDS, in
-// chunks of YTM_KC rows; the rows of F_k are read straight from global memory (F is shared by every slot: 1.2 MB at config 3, L2-resident), four
+// chunks of YTM_KC rows - by LDS-DMA, a chunk ahead of the products that read it (DMA = true; DMA = false: through registers, behind them: option
+// yt_mix_dma = 0 and row maps too long for LDS; same bits); the rows of F_k are read straight from global memory (F is shared by every slot: 1.2 MB at config 3, L2-resident), four
 // K steps (one 16-row group) ahead of the matrix cores.
 //
 // Same arithmetic as gemm_mfma_kernel_t + mix_slot2_kernel up to the order of the sums over K and over the columns.
 // grid = ceil(T / YTM_BINS) * nslots workgroups (1-D, remapped so that the workgroups of a slot share an XCD and its L2), block = YTM_THREADS,
-// dynamic LDS = ytmix_lds(PW); p <= PW <= 10 (the widths dispatch_pw instantiates), ranks and offsets multiples of 16 (they are: build_lowrank),
+// dynamic LDS = ytmix_lds(PW) + the row map; p <= PW <= 10 (the widths dispatch_pw instantiates), ranks and offsets multiples of 16 (they are: build_lowrank),
 // ract = roff[p].
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,10 +47,23 @@ struct YtMixArgs {
   const int* cmap; const int* nrtab;
   int ncmap;                                 // entries of cmap (copied into LDS behind the panel images: a staged pair's row is then an LDS read away, not a dependent memory round trip)
   int ts;
+  const void* zero16;                        // 16 zero bytes in device memory (the DMA form of the panel staging reads what it must not stage from there)
   int dbg;                                   // timing experiments only (option yt_mix_dbg; results are wrong when set): 1 no F loads, 2 no products, 4 no mixing, 8 no D stores, 16 no panel staging, 32 no barriers, 64 no panel loads
 };
 
-template <int PW>
+// One LDS-DMA wave instruction (global_load_lds_dwordx4): lane l's 16 bytes at gsrc go to LDS byte address lds_dst + 16 l - 1 KB in lane order, no
+// VGPR data, no ds_write.  Written as a statement of its own because the compiler counts a DMA it knows about as a pending LDS write and waits for
+// it (vmcnt(0)) at the next use of any ordinary load: here that is the first F fragment of the product loop the copy is meant to run under.  The
+// compiler therefore does NOT count these: ytm_dma_wait is the only wait they get.  (M0, the destination base, is the compiler's: saved and restored.)
+__device__ __forceinline__ void ytm_dma16(const void* gsrc, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// Loads, stores and DMAs retire in issue order through one counter: all but the wave's N youngest vector-memory operations are done behind this.
+template <int N>
+__device__ __forceinline__ void ytm_dma_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+template <int PW, bool DMA>
 __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(YtMixArgs a) {
   typedef double v4d __attribute__((ext_vector_type(4)));
   typedef double v2d __attribute__((ext_vector_type(2)));
@@ -94,22 +108,25 @@ __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(
   double sums[NPAIR];
 #pragma unroll
   for (int i = 0; i < NPAIR; ++i) sums[i] = 0.0;
-  // The panel of a column block goes through registers into one of TWO LDS images, in steps of YTM_KC rows: the waves that have finished with one
+  // Register form (DMA = false).  The panel of a column block goes through registers into one of TWO LDS images, in steps of YTM_KC rows: the waves that have finished with one
   // image request the next step's rows (panel_fetch: all of a thread's loads go out together), mask them and write the other image (panel_write) -
   // one barrier per step, behind that write.
   constexpr int TPC = YTM_THREADS / 16, NJ = YTM_KC / (2 * TPC);     // threads per column, row pairs per thread
   const int pcol = tid / TPC, prp = (tid % TPC) * 2;
-  v2d tmp[NJ];
-  int trow[NJ];                                               // slab row of the pair a thread has in flight (compact offsets: through cmap)
+  v2d tmp[DMA ? 1 : NJ];
+  int trow[DMA ? 1 : NJ];                                     // slab row of the pair a thread has in flight (compact offsets: through cmap)
+  if constexpr (!DMA) {
 #pragma unroll
-  for (int j = 0; j < NJ; ++j) { tmp[j] = v2d{0.0, 0.0}; trow[j] = 0; }
+    for (int j = 0; j < NJ; ++j) { tmp[j] = v2d{0.0, 0.0}; trow[j] = 0; }
+  }
   int* const cmap_s = reinterpret_cast<int*>(As + 2 * 16 * YTM_AS);
   if (a.cmap)
     for (int e = tid; e < a.ncmap; e += YTM_THREADS) cmap_s[e] = a.cmap[e];
   // (ncmap = 0: the map did not fit LDS next to the images - very long rank totals - and is read where it lies)
   const int* const cmap = a.cmap ? (a.ncmap > 0 ? cmap_s : a.cmap) : nullptr;
   if (a.cmap && a.ncmap > 0) __syncthreads();
-  auto nr_of = [&](int b0) { return cmap ? a.nrtab[b0 >> 4] : b0 + 16; };
+  // (nrtab through the constant address space: a scalar load - as a vector load it waited for every vector-memory operation in flight)
+  auto nr_of = [&](int b0) { return cmap ? ((__attribute__((address_space(4))) const int*)a.nrtab)[b0 >> 4] : b0 + 16; };
   auto panel_fetch = [&](int b0, int kc0, int kc1) {
     const double* src = Ms + (size_t)(b0 + pcol) * a.rpad;
 #pragma unroll
@@ -141,10 +158,39 @@ __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(
       }
     }
   };
+  // DMA form of the staging (option yt_mix_dma): a chunk of YTM_KC rows x 16 columns is 32 wave instructions of 128 rows of one column each, four
+  // per wave (columns 2 wave, 2 wave + 1; an image row is 16-byte aligned and no instruction crosses one).  Lane l of an instruction carries the row
+  // pair kc0 + 128 h + 2 l; the masks of panel_write become SOURCE choices, at pair granularity (pairs never split and start on an even slab row:
+  // build_lowrank checks the tables it uploads):
+  //  - a pair past the chunk's rows, a padding pair and a pair at or below slab row b0 + 16 read the 16 zero bytes at a.zero16;
+  //  - a pair between the diagonal and slab row b0 + 15 lies inside a 128 x 128 DIAGONAL block of Mt, and those hold zeros below the diagonal:
+  //    INVARIANT kept by chol.h (potrf_diag_kernel_t writes Dinv with zeros on the other side, diag_transpose_kernel_t writes every diagonal block
+  //    of Mt whole).  They are read as they are.
+  const unsigned as_lds = (unsigned)(unsigned long long)((__attribute__((address_space(3))) char*)As);
+  auto panel_dma = [&](int buf, int b0, int kc0, int kc1) {
+    const double* src0 = Ms + (size_t)(b0 + 2 * wave) * a.rpad;
+    // (the map is read from its LDS copy, as LDS: a load through the generic `cmap` is a flat load, and one from memory a vector load - either waits
+    //  for the F fragments in flight.  A map too long for LDS, ncmap = 0, runs the register form: the launch sees to it.)
+    int ic[2];
+    bool real[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = kc0 + 128 * h + 2 * lane;
+      const bool in = i < kc1 && !(a.dbg & 64);
+      ic[h] = a.cmap ? ((__attribute__((address_space(3))) const int*)cmap_s)[in ? i : kc0] : i;
+      real[h] = in && ic[h] >= 0 && ic[h] < b0 + 16;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        ytm_dma16(real[h] ? (const void*)(src0 + (size_t)c * a.rpad + ic[h]) : a.zero16, as_lds + (unsigned)((((buf * 16 + 2 * wave + c) * YTM_AS) + 128 * h) * sizeof(double)));
+  };
   const bool staged = !(a.dbg & 16);
   {
     const int nk0 = nr_of(0) < YTM_KC ? nr_of(0) : YTM_KC;
-    if (staged) { panel_fetch(0, 0, nk0); panel_write(0, 0, 0, nk0); }
+    if constexpr (DMA) { if (staged) panel_dma(0, 0, 0, nk0); ytm_dma_wait<0>(); }
+    else if (staged) { panel_fetch(0, 0, nk0); panel_write(0, 0, 0, nk0); }
   }
   __syncthreads();                                            // (also: the G image is written)
   int buf = 0;
@@ -182,6 +228,14 @@ __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(
     for (int kc0 = 0; kc0 < nr; kc0 += YTM_KC) {
       const int kc1 = kc0 + YTM_KC < nr ? kc0 + YTM_KC : nr;
       const double* arow = As + (buf * 16 + l15) * YTM_AS + l4 - kc0;
+      if constexpr (DMA) {
+        // the chunk behind this one - of this block, or the first of the next - into the image every wave has left (the barrier that opened this
+        // chunk): the copy runs under this chunk's products, and under the mixing and the stores where it is the block's last
+        if (staged) {
+          if (kc1 < nr) panel_dma(buf ^ 1, b0, kc1, kc1 + YTM_KC < nr ? kc1 + YTM_KC : nr);
+          else if (b0 + 16 < a.ract) panel_dma(buf ^ 1, b0 + 16, 0, nr_of(b0 + 16) < YTM_KC ? nr_of(b0 + 16) : YTM_KC);
+        }
+      }
       if (!(a.dbg & 2))
 #pragma unroll
       for (int k = 0; k < PW; ++k) {
@@ -212,7 +266,8 @@ __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(
       }
       if (kc1 < nr) {                                         // this block's next chunk (nothing to hide it under)
         const int nk1 = kc1 + YTM_KC < nr ? kc1 + YTM_KC : nr;
-        if (staged) { panel_fetch(b0, kc1, nk1); panel_write(buf ^ 1, b0, kc1, nk1); if (!(a.dbg & 32)) __syncthreads(); }
+        if constexpr (DMA) { ytm_dma_wait<0>(); if (staged && !(a.dbg & 32)) __syncthreads(); }
+        else if (staged) { panel_fetch(b0, kc1, nk1); panel_write(buf ^ 1, b0, kc1, nk1); if (!(a.dbg & 32)) __syncthreads(); }
         buf ^= 1;
       }
     }
@@ -258,7 +313,8 @@ __global__ __launch_bounds__(YTM_THREADS, 512 / YTM_THREADS) void yt_mix_kernel(
       asm volatile("" ::: "memory");                          // (the reads of G_t stay inside their column pair: 55 values kept across the two pairs would not fit)
     }
     // the first chunk of the next block into the other image (requested under the mixing it bought nothing measurable for eight registers)
-    if (more) { panel_fetch(nb0, 0, nk1); panel_write(buf ^ 1, nb0, 0, nk1); }
+    if constexpr (DMA) ytm_dma_wait<0>();                     // (the copy is older than everything the block issued behind it: long done; what this waits for is the D stores, as the register form's loads did)
+    else if (more) { panel_fetch(nb0, 0, nk1); panel_write(buf ^ 1, nb0, 0, nk1); }
     if (staged && !(a.dbg & 32)) __syncthreads();
     buf ^= 1;
   }

@@ -219,7 +219,10 @@ int pgpfa_mstep_cd_costgrad(pgpfa_ctx* ctx, const double* vecCd, const double* p
 int pgpfa_mstep_cd_newton_pass(pgpfa_ctx* ctx, const double* vecCd, const double* prior_center, double inv_s2,
                                double* cost_n /* [q] */, double* delta /* [q*(p+1)] */, double* dec /* [q] */);
 /* Chord pass: cost and gradient at vecCd (one cheap sweep), step from the per-neuron Hessians of the last
- * pgpfa_mstep_cd_newton_pass (also across EM iterations: they stay SPD, the step stays a descent direction). */
+ * pgpfa_mstep_cd_newton_pass (also across EM iterations: they stay SPD, the step stays a descent direction).
+ * The trial lists of the two passes need not have the same length: the gradient is the mean over the trials of THIS
+ * pass, the Hessians the mean over the trials of that Newton pass (its all-reduced count is kept with its sums), so
+ * delta = -(H_A / n_A)^-1 (g_B / n_B) and dec = -g . delta. */
 int pgpfa_mstep_cd_chord_pass(pgpfa_ctx* ctx, const double* vecCd, const double* prior_center, double inv_s2,
                               double* cost_n /* [q] */, double* delta /* [q*(p+1)] */, double* dec /* [q] */);
 int pgpfa_mstep_cd_cost_per_neuron(pgpfa_ctx* ctx, const double* vecCd, const double* prior_center, double inv_s2,
@@ -238,7 +241,8 @@ int pgpfa_mstep_tau_costgrad_multi(pgpfa_ctx* ctx, int m, const double* logp, do
 /* The same pass in two halves (round 6): _begin enqueues it on the context's side stream and returns at once, _end waits for it and returns
  * cost[m][p], grad[m][p] - the same bits as the call above.  Between the two the caller may run the (C,d) passes of the same M-step (learning.py:
  * 93-141 and 257-293 are independent problems; the reference solves them one after the other); one pass in flight per context, every other
- * timescale / precomp / E-step entry point fails while one is. */
+ * timescale / precomp / E-step entry point - pgpfa_mstep_tau_costgrad for a single latent among them, it shares the pass's scratch -
+ * fails while one is, and leaves the pass intact. */
 int pgpfa_mstep_tau_costgrad_multi_begin(pgpfa_ctx* ctx, int m, const double* logp);
 int pgpfa_mstep_tau_costgrad_multi_end(pgpfa_ctx* ctx, double* cost, double* grad);
 

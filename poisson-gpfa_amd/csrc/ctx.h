@@ -132,7 +132,7 @@ struct pgpfa_ctx {
   double split_max_norm = 0.07;
   double *cdym = nullptr, *cdym_part = nullptr;   // count terms of the (C,d) cost: sum_t y m_t, sum_t y per neuron (per E-step)
   bool cdym_valid = false, cd_mfma = true, cd_hess_mfma = true; int cd_debug = 0;
-  bool cd_hess_valid = false; int cd_hess_ntr = 0;   // per-neuron Hessian sums of the last Newton pass are resident
+  bool cd_hess_valid = false;   // per-neuron Hessian sums of the last Newton pass are resident
   std::vector<double> logdetK;                  // log det of the p Gram matrices (from the factor in build_kinv)
   bool dual_lowrank = true;                     // dual-variational entry points use the low-rank engine when it pays (want_lowrank)
   double* dual_tbl = nullptr; int dual_ncol = 0, dual_npd = 0; bool dual_gemm = true;   // pair / loading table of the GEMM form (dual.h)

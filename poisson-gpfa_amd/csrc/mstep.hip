@@ -101,14 +101,17 @@ int pgpfa_mstep_cd_costgrad(pgpfa_ctx* c, const double* vecCd, const double* pri
 }
 
 
-// Tail of both Newton-pass variants: the q independent (p+1)-dim Newton steps on the reduced sums in c->cdhout (trial count at rtot_dev, read
-// by the kernel), then ONE read-back of [cost sums | delta | dec | R] through pinned memory.
+// Tail of both Newton-pass variants: the q independent (p+1)-dim Newton steps on the reduced sums in c->cdhout (trial count of the cost /
+// gradient rows at rtot_dev, read by the kernel; the Hessian rows are divided by the count they were summed over, which the Newton pass left
+// behind them in c->cdhout - a chord pass may follow a posterior over another number of trials), then ONE read-back of
+// [cost sums | delta | dec | R] through pinned memory.
 static int cd_newton_finish(pgpfa_ctx* c, const double* rtot_dev, const double* vecCd, const double* prior_center, double inv_s2, double* cost_n,
                             double* delta, double* dec) {
   const int q = c->q, p = c->p, D = p + 1;
+  const int NH = 1 + D + D * (D + 1) / 2;
   const int th = std::max(1, std::min(32, (int)(48 * 1024 / ((D * D + 2 * D) * sizeof(double)))));
   hipLaunchKernelGGL(cd_newton_step_kernel, dim3((q + th - 1) / th), dim3(th), (size_t)th * (D * D + 2 * D) * sizeof(double), c->st, c->cdhout, q, p,
-                     rtot_dev, c->vec, prior_center ? c->cdcenter : nullptr, inv_s2, c->cdpack);
+                     rtot_dev, c->cdhout + (size_t)NH * q, c->vec, prior_center ? c->cdcenter : nullptr, inv_s2, c->cdpack);
   HIPC(hipGetLastError());
   const size_t np = (size_t)q * (D + 2) + 1;
   CHK(ensure_hbuf(c, np));
@@ -180,12 +183,12 @@ int pgpfa_mstep_cd_newton_pass(pgpfa_ctx* c, const double* vecCd, const double* 
   CHK(upload_nosync(c, c->cdhout + (size_t)NH * q, &cnt, sizeof(double)));
   CHK(allreduce_dev(c, c->cdhout, (size_t)NH * q + 1));
   c->cd_hess_valid = true;
-  c->cd_hess_ntr = a.ntr;
   return cd_newton_finish(c, c->cdhout + (size_t)NH * q, vecCd, prior_center, inv_s2, cost_n, delta, dec);
 }
 
 // Chord variant of the pass above: cost and gradient are evaluated at vecCd (the cheap kernel), the per-neuron
-// Hessians are the ones of the last pgpfa_mstep_cd_newton_pass (still a descent direction: they are SPD).
+// Hessians are the ones of the last pgpfa_mstep_cd_newton_pass (still a descent direction: they are SPD), each mean over its own trial
+// count: the gradient over the trials of this sweep, the Hessians over those of that Newton pass (the count stays behind them in cdhout).
 int pgpfa_mstep_cd_chord_pass(pgpfa_ctx* c, const double* vecCd, const double* prior_center, double inv_s2, double* cost_n,
                               double* delta, double* dec) {
   PhaseRange range_phase("pgpfa.mstep_cd_chord_pass");
@@ -195,7 +198,6 @@ int pgpfa_mstep_cd_chord_pass(pgpfa_ctx* c, const double* vecCd, const double* p
   if (!c->cd_hess_valid) return fail("no per-neuron Hessians resident: call pgpfa_mstep_cd_newton_pass first");
   HIPC(hipSetDevice(c->device));
   const int q = c->q, p = c->p, D = p + 1;
-  const int NH = 1 + D + D * (D + 1) / 2;
   const int len = (p + 2) * q;
   CHK(upload_nosync(c, c->vec, vecCd, (size_t)q * D * sizeof(double)));
   if (prior_center) CHK(upload_nosync(c, c->cdcenter, prior_center, (size_t)q * D * sizeof(double)));
@@ -204,7 +206,6 @@ int pgpfa_mstep_cd_chord_pass(pgpfa_ctx* c, const double* vecCd, const double* p
   CHK(upload_nosync(c, c->cdout + len, &cnt, sizeof(double)));
   CHK(allreduce_dev(c, c->cdout, (size_t)len + 1));
   hipLaunchKernelGGL(cd_chord_merge_kernel, dim3((len + 255) / 256), dim3(256), 0, c->st, c->cdout, q, p, c->cdhout);
-  (void)NH;
   return cd_newton_finish(c, c->cdout + len, vecCd, prior_center, inv_s2, cost_n, delta, dec);
 }
 
@@ -292,6 +293,7 @@ int pgpfa_mstep_tau_costgrad(pgpfa_ctx* c, int k, double logp, double* cost, dou
   if (!c->have_precomp) return fail("pgpfa_mstep_precomp has not been called");
   if (k < 0 || k >= c->p) return fail("latent %d out of range", k);
   if (!std::isfinite(logp)) return fail("log-gamma is not finite");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");   // it shares kws, tK, tM, tscal with this one
   HIPC(hipSetDevice(c->device));
   const int Tp = c->Tp;
   const size_t slab = (size_t)Tp * Tp;
@@ -358,7 +360,7 @@ static int tau_pass_enqueue(pgpfa_ctx* c, int nq, double* dlogp, double* dres) {
   const int nbk = 64;
   auto bdot = [&](const double* A, const double* B, double* out, int bmod) {
     hipLaunchKernelGGL(dot_part_batch_kernel, dim3(nbk, nq), dim3(256), 0, c->st, A, (long long)slab, B, (long long)slab, (long long)slab, c->tpart, bmod);
-    hipLaunchKernelGGL(sum_part_batch_kernel, dim3(1), dim3(64), 0, c->st, c->tpart, nbk, out, nq);
+    hipLaunchKernelGGL(sum_part_batch_kernel, dim3((nq + 63) / 64), dim3(64), 0, c->st, c->tpart, nbk, out, nq);   // (80 queries at 20 latents, 128 at 32)
   };
   bdot(c->tK, c->Pauto, dres + nq, p);
   bdot(c->tK, c->tM, dres + 2 * nq, 0);

@@ -161,7 +161,8 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * displacement of the parameters between consecutive Laplace E-steps: the largest of |dC| / |C|, |dd| / |d|, |d log tau|; -1: unknown),
  * "last_cold_restarts", "last_retry_ms" (time of the dense retry pass), "last_fallback_no_descent" / "last_fallback_line_search" /
  * "last_fallback_outer_cap" (slots the shared-preconditioner Newton phase gave up on, by reason); of the context: "plans" and "plan_ms_total"
- * (workspace plans made and their time), "arena_grow_ms_total" (of it: mapping memory), "set_params_calls". */
+ * (workspace plans made and their time), "arena_grow_ms_total" (of it: mapping memory), "set_params_calls"; "trial_lengths_set" (1 while
+ * pgpfa_set_trial_lengths has given the trials bin counts of their own, 0 when every trial has T bins). */
 int pgpfa_get_info(pgpfa_ctx* ctx, const char* key, double* value);
 
 /* ---- data ---------------------------------------------------------------------- */
@@ -171,6 +172,16 @@ int pgpfa_get_info(pgpfa_ctx* ctx, const char* key, double* value);
 int pgpfa_upload_counts_f64(pgpfa_ctx* ctx, const double* Y);
 int pgpfa_upload_counts_u8(pgpfa_ctx* ctx, const uint8_t* Y);
 int pgpfa_upload_counts_u16(pgpfa_ctx* ctx, const uint16_t* Y);
+/* Trials of unequal length: len[R], the number of bins T_r (1 <= T_r <= T) of every trial; NULL: every trial has T bins again.  Called after
+ * the counts are uploaded, which stay one zero-padded [R][q][T] tensor: the call fails, naming the trial, on a length outside 1..T or on a
+ * non-zero count at a padded bin t >= T_r.  Uploading counts again drops the table.  Padded bins carry no likelihood term: no rate, no count, no
+ * contribution to the Laplace objective, its gradient and curvature blocks, or to any sum of the (C,d) M-step; the GP prior still spans all T
+ * bins of every trial, so the posterior over the first T_r bins is that of the T_r-bin problem (a GP is consistent under marginalisation), the
+ * padded bins hold the prior conditional and the objective at the mode is the same number.  Posterior getters and pgpfa_set_posterior keep
+ * their padded [T] layouts; PautoSum and the timescale cost are those of the padded problem; pgpfa_count_moments counts sum_r T_r samples.  The
+ * dual-variational entry points, pgpfa_loo_predict and pgpfa_generate do not know the lengths and fail while a table is set (info key
+ * "trial_lengths_set"). */
+int pgpfa_set_trial_lengths(pgpfa_ctx* ctx, const int32_t* len /* [R], NULL: all T */);
 /* resident counts of the listed trials (idx NULL: all) as uint16 [n][q][T] */
 int pgpfa_get_counts_u16(pgpfa_ctx* ctx, int n, const int32_t* idx, uint16_t* out);
 /* params = {'C': [q][p], 'd': [q], 'tau': [p] seconds} (engine.py:40-44).  Builds the p Gram
@@ -248,7 +259,8 @@ int pgpfa_mstep_tau_costgrad_multi_end(pgpfa_ctx* ctx, double* cost, double* gra
 
 /* ---- count moments (util.py:523-533 Poisson-PCA initialiser; engine.py:487-492 diagnostics) ---- */
 /* Exact integer moments of the resident counts over all (trial, bin) samples of the listed trials:
- * sum[i] = sum y_i, cross[i][j] = sum y_i y_j, n_samples = trials * T (np.mean / np.cov of the raster follow). */
+ * sum[i] = sum y_i, cross[i][j] = sum y_i y_j, n_samples = trials * T - the sum of the listed trials' lengths under
+ * pgpfa_set_trial_lengths - (np.mean / np.cov of the raster follow). */
 int pgpfa_count_moments(pgpfa_ctx* ctx, int n, const int32_t* idx, int64_t* sum /* [q] */, int64_t* cross /* [q][q] */,
                         int64_t* n_samples);
 

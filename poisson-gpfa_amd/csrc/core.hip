@@ -978,6 +978,7 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   if (const char* g = std::getenv("PGPFA_RANK_GRAN")) { const int v = std::atoi(g); if (v == 4 || v == 8 || v == 16) c->rank_gran = v; }
   c->info["n_pad"] = c->npad;
   c->info["counts_two_bytes"] = 0.0;
+  c->info["trial_lengths_set"] = 0.0;
   c->info["arena_bytes"] = 0.0;
   c->info["last_eps_wt_norm"] = 0.0;
   c->info["last_eps_wt_rms"] = 0.0;
@@ -1000,6 +1001,7 @@ int pgpfa_destroy(pgpfa_ctx* c) {
   if (c->lam_keep) hipFree(c->lam_keep);
   if (c->split_buf) hipFree(c->split_buf);
   if (c->Yhi) hipFree(c->Yhi);
+  if (c->trial_len) hipFree(c->trial_len);
   arena_release(c);
   if (c->hbuf) hipHostFree(c->hbuf);
   if (c->dl_stage) hipHostFree(c->dl_stage);
@@ -1208,10 +1210,83 @@ int ensure_high_plane(pgpfa_ctx* c) {
   return 0;
 }
 
+// ---- trials of unequal length --------------------------------------------------------------------------------------------------
+static void drop_trial_lengths(pgpfa_ctx* c) {
+  if (c->trial_len) {
+    hipStreamSynchronize(c->st);
+    hipFree(c->trial_len);
+    c->bytes -= (size_t)c->R * sizeof(int);
+    c->trial_len = nullptr;
+  }
+  c->trial_len_h.clear();
+  c->info["trial_lengths_set"] = 0.0;
+}
+
+int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry) {
+  if (c && c->trial_len)
+    return fail("%s does not support trials of unequal length yet: per-trial bin counts are set (pgpfa_set_trial_lengths) and the padded bins "
+                "would be treated as data", entry);
+  return 0;
+}
+
+// cnt[r] = number of non-zero counts of trial r at bins t >= len[r] (either byte plane).  grid = R, block = 256
+static __global__ __launch_bounds__(256) void padded_counts_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const int* __restrict__ len,
+                                                                   int q, int T, int* __restrict__ cnt) {
+  __shared__ int red[4];
+  const size_t r = blockIdx.x;
+  const int L = len[r], w = T - L;
+  int bad = 0;
+  for (long long e = threadIdx.x; e < (long long)q * w; e += 256) {
+    const size_t i = (r * q + (size_t)(e / w)) * T + L + (size_t)(e % w);
+    bad += (Y[i] != 0) || (Yhi && Yhi[i] != 0);
+  }
+  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[r] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
+  if (!c) return fail("null context");
+  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_trial_lengths checks them");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  if (!len) {                                               // back to R trials of T bins; what was computed under the table is stale
+    if (c->trial_len) { drop_trial_lengths(c); counts_changed(c, nullptr); }
+    return 0;
+  }
+  for (int r = 0; r < c->R; ++r)
+    if (len[r] < 1 || len[r] > c->T) return fail("trial %d: length %d is outside 1..T = %d", r, (int)len[r], c->T);
+  int* dlen = nullptr;
+  int* dcnt = nullptr;
+  HIPC(hipMalloc((void**)&dlen, (size_t)c->R * sizeof(int)));
+  if (hipMalloc((void**)&dcnt, (size_t)c->R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); hipFree(dlen); return fail("hipMalloc failed"); }
+  std::vector<int> lv(len, len + c->R), bad(c->R, 0);
+  hipMemcpyAsync(dlen, lv.data(), (size_t)c->R * sizeof(int), hipMemcpyHostToDevice, c->st);
+  hipLaunchKernelGGL(padded_counts_kernel, dim3(c->R), dim3(256), 0, c->st, c->Y, c->Yhi, dlen, c->q, c->T, dcnt);
+  hipMemcpyAsync(bad.data(), dcnt, (size_t)c->R * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  const hipError_t e = hipStreamSynchronize(c->st);
+  hipFree(dcnt);
+  if (e != hipSuccess || hipGetLastError() != hipSuccess) { hipFree(dlen); return fail("pgpfa_set_trial_lengths: %s", hipGetErrorString(e)); }
+  for (int r = 0; r < c->R; ++r)
+    if (bad[r]) {
+      hipFree(dlen);
+      return fail("trial %d: %d non-zero counts at padded bins (t >= %d): the count tensor must be zero-padded behind a trial's length", r, bad[r], lv[r]);
+    }
+  drop_trial_lengths(c);
+  c->trial_len = dlen;
+  c->bytes += (size_t)c->R * sizeof(int);
+  c->trial_len_h.swap(lv);
+  c->info["trial_lengths_set"] = 1.0;
+  counts_changed(c, nullptr);                               // sums and posteriors computed under other lengths are stale
+  return 0;
+}
+
 int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
   if (!c || !Y) return fail("null argument");
   HIPC(hipSetDevice(c->device));
   drop_high_plane(c);
+  drop_trial_lengths(c);                                    // (a length table belongs to the counts it was checked against)
   HIPC(hipMemcpyAsync(c->Y, Y, (size_t)c->R * c->q * c->T, hipMemcpyHostToDevice, c->st));
   HIPC(hipStreamSynchronize(c->st));
   c->have_counts = true;
@@ -1232,6 +1307,7 @@ static int upload_counts_wide(pgpfa_ctx* c, const TS* Y) {
   hipError_t e = hipMalloc((void**)&flags, 2 * sizeof(int));
   if (e != hipSuccess) { hipFree(tmp); return fail("hipMalloc: %s", hipGetErrorString(e)); }
   drop_high_plane(c);
+  drop_trial_lengths(c);
   int hf[2] = {0, 0};
   int rc = 0;
   for (int pass = 0; pass < 2 && !rc; ++pass) {

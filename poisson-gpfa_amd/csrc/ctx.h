@@ -95,6 +95,10 @@ struct pgpfa_ctx {
   // persistent device state
   uint8_t* Y = nullptr;
   uint8_t* Yhi = nullptr;                        // high bytes of the counts: allocated only while the tensor holds a count above 255
+  // Trials of unequal length (pgpfa_set_trial_lengths): bins t >= trial_len[r] of trial r are padding - zero counts, no likelihood term in the
+  // Poisson pass and the (C,d) passes; the GP prior, the solvers and the covariance engines still span all T bins.  NULL: every trial has T bins.
+  int* trial_len = nullptr;                      // device [R]
+  std::vector<int> trial_len_h;                  // host copy (count_moments); empty while trial_len is NULL
   double *C = nullptr, *d = nullptr, *tau = nullptr;
   double *Kpad = nullptr, *Kinv = nullptr;      // [p][Tp][Tp]
   double* Xmode = nullptr;                       // [R][p][T]   post_mean / warm start
@@ -420,6 +424,7 @@ int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
 int resolve_trials(pgpfa_ctx* c, int n, const int32_t* idx, Trials* out, bool distinct = false);
 void counts_changed(pgpfa_ctx* c, const std::vector<int>* trials);
+int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry);      // fails while per-trial bin counts are set: entry points that do not know them
 int ensure_high_plane(pgpfa_ctx* c);
 int ready(pgpfa_ctx* c);
 int ready_estep(pgpfa_ctx* c, bool allow_lowrank);

@@ -15,6 +15,7 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   a.X = X; a.sX = c->ld; a.G = G; a.sG = c->ld; a.W = W; a.sW = (long long)c->T * c->p * c->p;
   a.fpart = c->fpart; a.slots = d_list; a.trial_of_slot = c->trial_of_slot;
   a.mask = c->mask_active ? c->mask_of_slot : nullptr;
+  a.len = c->trial_len;                                          // NULL unless pgpfa_set_trial_lengths gave the trials bin counts of their own
   a.off = c->var_active ? c->voff : nullptr; a.sOff = (long long)c->q * c->T;
   a.lam_out = c->lam_out_active ? c->lamd : nullptr; a.sLam = (long long)c->q * c->T;
   a.q = c->q; a.p = c->p; a.T = c->T; a.ntile = (c->T + 63) / 64; a.full = full;
@@ -30,7 +31,7 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
     CHK(ensure_lambda(c));
     prof_begin(c, TAG_POISSON, fl);
     hipLaunchKernelGGL(rates_wide_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
-                       a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->q, c->p, c->T);
+                       a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->q, c->p, c->T);
     prof_end(c);
     if (full) {
       const int np = c->p * (c->p + 1) / 2;
@@ -374,14 +375,16 @@ static int shared_factor(pgpfa_ctx* c, int nb) {
 
 // The reference's negative log-posterior (inference.py:12-32) of a slot's trial AT x = 0: f0 = sum_n (T exp(d_n) - d_n sum_t y_nt), the objective of
 // the cold start - what a warm start has to beat (estep_impl: a start point that does worse is replaced by zero).  One pass over the slot's count
-// rows (q T bytes).  grid = (slots), block = 256 (a wave per neuron row); mask (may be null): the neuron a leave-one-out item leaves out.
+// rows (q T bytes).  grid = (slots), block = 256 (a wave per neuron row); mask (may be null): the neuron a leave-one-out item leaves out;
+// len (may be null): per-trial bin counts - a trial of T_r bins has f0 = sum_n (T_r exp(d_n) - d_n sum_t y_nt).
 static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ d,
-                                                                    const int* __restrict__ trial_of_slot, const int* __restrict__ mask, int q, int T,
-                                                                    double* __restrict__ f0) {
+                                                                    const int* __restrict__ trial_of_slot, const int* __restrict__ mask,
+                                                                    const int* __restrict__ len, int q, int T, double* __restrict__ f0) {
   __shared__ double red[4];
   const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t base = (size_t)trial_of_slot[s] * q * T;
   const int skip = mask ? mask[s] : -1;
+  const int Tl = len ? len[trial_of_slot[s]] : T;       // bins of the trial that carry a rate (the counts behind them are zero)
   double acc = 0.0;
   for (int n = wave; n < q; n += 4) {
     if (n == skip) continue;
@@ -393,7 +396,7 @@ static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_
       for (int t = lane; t < T; t += 64) cnt += (unsigned)rh[t] << 8;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-    if (lane == 0) acc += (double)T * exp(d[n]) - d[n] * (double)cnt;
+    if (lane == 0) acc += (double)Tl * exp(d[n]) - d[n] * (double)cnt;
   }
   if (lane == 0) red[wave] = acc;
   __syncthreads();
@@ -515,7 +518,7 @@ int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, do
     if (vo == 0 && !var && any_warm && c->start_guard) {
       // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
       hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
-                         c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->q, T, c->sc_alpha);
+                         c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->q, T, c->sc_alpha);
       CHK(dl_enqueue(c, ftry.data(), c->sc_alpha, nb * sizeof(double)));
     }
     CHK(eval_start());
@@ -1328,6 +1331,7 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
 
 int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, double* err_sum) {
   if (!c || !y_pred || !err_sum) return fail("null argument");
+  CHK(refuse_trial_lengths(c, "pgpfa_loo_predict"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   const int q = c->q, T = c->T;

@@ -179,6 +179,7 @@ struct PoissonArgs {
   const int* slots;                // list of slots to process
   const int* trial_of_slot;
   const int* mask;                 // optional per slot: index of a neuron left out of the likelihood (NULL / -1: none)
+  const int* len;                  // optional per TRIAL: bins that carry a likelihood term (NULL: all T); bins t >= len[trial] have no rate and no count
   // optional per slot [q][T]: an offset added to the log rate, h = C x + d + off (the variance term 1/2 c_n^T Sigma_t c_n of the
   // variational fixed point, pgpfa_dual_fixed_point), and an output for the rates exp(h) themselves
   const double* off; long long sOff;
@@ -202,6 +203,8 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
   const int t = blockIdx.x * 64 + tx;
   const bool valid = t < a.T;
   const int p = a.p, q = a.q, T = a.T;
+  const int Tl = a.len ? a.len[trial] : T;          // bins of this trial with a likelihood term (uniform over the workgroup)
+  const bool lik = t < Tl;
   const double* X = a.X + (size_t)slot * a.sX;
   const uint8_t* Y = a.Y + (size_t)trial * q * T;
   const uint8_t* Yh = a.Yhi ? a.Yhi + (size_t)trial * q * T : nullptr;
@@ -219,11 +222,12 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
   }
   double facc = 0.0;
 
-  for (int n0 = 0; n0 < q; n0 += PNC) {
+  // (a workgroup wholly past the trial's length skips the neuron loop: its bins keep G = 0 and W = 0, which the solvers still read)
+  for (int n0 = 0; n0 < q && blockIdx.x * 64 < Tl; n0 += PNC) {
     for (int nn = ty; nn < PNC; nn += KY) {
       const int n = n0 + nn;
       double e = 0.0, r = 0.0;
-      if (n < q && valid && n != held_out) {
+      if (n < q && lik && n != held_out) {
         double h = a.d[n];
         if (a.off) h += a.off[(size_t)slot * a.sOff + (size_t)n * T + t];
         const double* Cn = a.C + (size_t)n * p;
@@ -327,6 +331,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
   const int trial = a.trial_of_slot[slot];
   const int held_out = a.mask ? a.mask[slot] : -1;
   const int p = a.p, q = a.q, T = a.T, pp = p * p;
+  const int Tl = a.len ? a.len[trial] : T;                          // bins of this trial with a likelihood term (no table: all T)
   const int sbase0 = blockIdx.x * 64 * NBT + wave * 16 * NBT;       // this wave's bins: NBT consecutive tiles of 16
   const double* X = a.X + (size_t)slot * a.sX;
   const uint8_t* Y = a.Y + (size_t)trial * q * T;
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
   }
   double facc = 0.0;
 
-  if (sbase0 < T) {
+  if (sbase0 < Tl) {
     // every global load of a neuron tile (offsets, counts, table fragments) is issued up front with clamped,
     // branch-free addresses; invalid rows/bins are masked afterwards
     for (int nb0 = 0; nb0 < qpad; nb0 += 16) {
@@ -400,7 +405,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
       }
 #pragma unroll
       for (int bt = 0; bt < NBT; ++bt) {
-        if (sbase0 + 16 * bt >= T) continue;                    // (uniform over the wave)
+        if (sbase0 + 16 * bt >= Tl) continue;                   // (uniform over the wave; a tile past the trial's length leaves zeros)
         mdouble4 h;
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = (nb0 + l4 + 4 * r < q) ? dv[bt][r] : 0.0;
@@ -410,7 +415,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = nb0 + l4 + 4 * r;
-          const bool ok = (n < q) && vt[bt] && (n != held_out);
+          const bool ok = (n < q) && (sbase0 + 16 * bt + l15 < Tl) && (n != held_out);
           const double y = ok ? (double)yv[bt][r] : 0.0;
           const double ev = ok ? exp(h[r]) : 0.0;
           e[r] = ev;
@@ -1043,6 +1048,7 @@ struct CdArgs {
   const uint8_t* Y; const uint8_t* Yhi;     // counts [R][q][T] (+ plane of high bytes, NULL when none: count_at)
   const double* mean; const double* vsm; const double* vec;   // vecCd
   const int* trials; int ntr;
+  const int* len;        // optional per trial: bins that enter the sums (NULL: all T); an item's tn is clipped to it, items past it do nothing
   double* part;          // [gridDim.y][p+2][q]
   int q, p, T;
   int dbg;               // timing experiments only (option cd_debug): bit 0 no exp, bit 1 no second product, bit 2 no first product, bit 3 no staging
@@ -1081,7 +1087,9 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
   for (int item = blockIdx.y; item < nitems; item += gridDim.y) {
     const size_t r = a.trials[item / ntt];
     const int t0 = (item % ntt) * TT;
-    const int tn = (T - t0 < TT) ? T - t0 : TT;
+    const int Tl = a.len ? a.len[r] : T;
+    if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
     const uint8_t* Y = a.Y + r * q * T;
@@ -1193,7 +1201,9 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
   for (int item = blockIdx.y; item < nitems; item += gridDim.y) {
     const size_t r = a.trials[item / ntt];
     const int t0 = (item % ntt) * TT;
-    const int tn = (T - t0 < TT) ? T - t0 : TT;
+    const int Tl = a.len ? a.len[r] : T;
+    if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
     const uint8_t* Y = a.Y + r * q * T;
@@ -1338,7 +1348,9 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
   for (int item = blockIdx.y; item < nitems; item += gridDim.y) {
     const size_t r = a.trials[item / ntt];
     const int t0 = (item % ntt) * TT;
-    const int tn = (T - t0 < TT) ? T - t0 : TT;
+    const int Tl = a.len ? a.len[r] : T;
+    if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
     const uint8_t* Y = a.Y + r * q * T;

@@ -36,8 +36,9 @@ struct CdM {
 // part[blockIdx.x][(p+1)][q].  grid = (nblocks), block = 256; a block walks trials, per trial bin tiles of 64: the count tile
 // [q][64] (coalesced 64-byte rows) and the mean tile [p][64] are staged in LDS, thread = neuron (q <= 256 per pass).
 // (Yhi: plane of the counts' high bytes, NULL when every count fits one byte - a second pass over the tile with weight 256)
+// (len: per-trial bin counts, NULL when every trial has T bins - the bin tiles of a trial stop at its length; the counts behind it are zero)
 inline __global__ __launch_bounds__(256) void cd_ym_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ mean,
-                                                    const int* __restrict__ trials, int ntr, int q, int p, int T, double* __restrict__ part) {
+                                                    const int* __restrict__ trials, const int* __restrict__ len, int ntr, int q, int p, int T, double* __restrict__ part) {
   __shared__ double ms[32][64];
   __shared__ unsigned yt[256][17];                      // 64 counts of a neuron as 16 words (+1: bank spread)
   double* out = part + (size_t)blockIdx.x * (p + 1) * q;
@@ -49,8 +50,9 @@ inline __global__ __launch_bounds__(256) void cd_ym_kernel(const uint8_t* __rest
     for (int k = 0; k < 33; ++k) acc[k] = 0.0;
     for (int i = blockIdx.x; i < ntr; i += gridDim.x) {
       const size_t r = trials[i];
-      for (int t0 = 0; t0 < T; t0 += 64) {
-        const int tn = min(64, T - t0);
+      const int Tl = len ? len[r] : T;                   // bins of the trial that enter the sums (no table: all T)
+      for (int t0 = 0; t0 < Tl; t0 += 64) {
+        const int tn = min(64, Tl - t0);
         __syncthreads();
         for (int e = threadIdx.x; e < p * 64; e += 256) {
           const int k = e >> 6, t = e & 63;
@@ -120,7 +122,7 @@ inline __global__ __launch_bounds__(256) void cd_ym_kernel(const uint8_t* __rest
 // coalesced, 64 bins per tile); the mean tile is kept bin-major with stride 16 - fragment reads conflict-free.  Wave w takes neuron tiles w, w + 4, ...
 // Same part layout: part[blockIdx.x][(p+1)][q].  grid = (nblocks), block = 256.
 inline __global__ __launch_bounds__(256) void cd_ym_mfma_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ mean,
-                                                                const int* __restrict__ trials, int ntr, int q, int p, int T, double* __restrict__ part) {
+                                                                const int* __restrict__ trials, const int* __restrict__ len, int ntr, int q, int p, int T, double* __restrict__ part) {
   typedef double v4d __attribute__((ext_vector_type(4)));
   __shared__ double ms[64][16];                         // [bin][k]
   __shared__ unsigned yt[256][17], yh[256][17];         // 64 counts of a neuron as 16 words (+1: bank spread): low and high byte planes
@@ -135,8 +137,9 @@ inline __global__ __launch_bounds__(256) void cd_ym_mfma_kernel(const uint8_t* _
     for (int j = 0; j < 4; ++j) acc[j] = v4d{0.0, 0.0, 0.0, 0.0};
     for (int i = blockIdx.x; i < ntr; i += gridDim.x) {
       const size_t r = trials[i];
-      for (int t0 = 0; t0 < T; t0 += 64) {
-        const int tn = min(64, T - t0);
+      const int Tl = len ? len[r] : T;                   // bins of the trial that enter the sums (no table: all T)
+      for (int t0 = 0; t0 < Tl; t0 += 64) {
+        const int tn = min(64, Tl - t0);
         __syncthreads();
         for (int e = tid; e < (p + 1) * 64; e += 256) {
           const int k = e >> 6, t = e & 63;
@@ -307,7 +310,8 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
   auto prefetch = [&](int itrial, int itile) {
     const size_t r = a.trials[itrial];
     const int t0 = itile * BT;
-    const int tn = (T - t0 < BT) ? T - t0 : BT;
+    const int Tl = a.len ? a.len[r] : T;                // (a tile past the trial's length: tn <= 0, every element is staged as zero)
+    const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;
     const double* vsm = a.vsm + (r * T + t0) * pp;
     const double* mean = a.mean + r * p * T + t0;
     double raw[MAXPF];
@@ -341,7 +345,8 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
   int cur = 0;
   for (; item < nitems; item += gridDim.x) {
     const int t0 = c_ti * BT;
-    const int tn = (T - t0 < BT) ? T - t0 : BT;
+    const int Tl = a.len ? a.len[a.trials[c_tr]] : T;
+    const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;      // bins of this item inside the trial's length (<= 0: the item does nothing)
     const bool more = item + (int)gridDim.x < nitems;
     c_tr += step_tr; c_ti += step_ti;
     if (c_ti >= ntt) { c_ti -= ntt; c_tr += 1; }
@@ -577,7 +582,8 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
   auto prefetch = [&](int itrial, int itile) {
     const size_t r = a.trials[itrial];
     const int t0 = itile * BT;
-    const int tn = (T - t0 < BT) ? T - t0 : BT;
+    const int Tl = a.len ? a.len[r] : T;                // (a tile past the trial's length: tn <= 0, every element is staged as zero)
+    const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;
     const double* vsm = a.vsm + (r * T + t0) * pp;
     const double* mean = a.mean + r * p * T + t0;
     double raw[MAXPF];
@@ -608,7 +614,8 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
   int cur = 0;
   for (; item < nitems; item += gridDim.x) {
     const int t0 = c_ti * BT;
-    const int tn = (T - t0 < BT) ? T - t0 : BT;
+    const int Tl = a.len ? a.len[a.trials[c_tr]] : T;
+    const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;      // bins of this item inside the trial's length (<= 0: the item does nothing)
     const bool more = item + (int)gridDim.x < nitems;
     c_tr += step_tr; c_ti += step_ti;
     if (c_ti >= ntt) { c_ti -= ntt; c_tr += 1; }

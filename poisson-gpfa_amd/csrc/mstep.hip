@@ -15,9 +15,9 @@ static int ensure_cdym(pgpfa_ctx* c) {
   const int q = c->q, p = c->p, ntr = (int)c->last_trials_h.size();
   const int nbk = std::max(1, std::min(1024, ntr));
   if (c->mfma && c->cd_mfma && p + 1 <= 16)
-    hipLaunchKernelGGL(cd_ym_mfma_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, ntr, q, p, c->T, c->cdym_part);
+    hipLaunchKernelGGL(cd_ym_mfma_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->trial_len, ntr, q, p, c->T, c->cdym_part);
   else
-    hipLaunchKernelGGL(cd_ym_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, ntr, q, p, c->T, c->cdym_part);
+    hipLaunchKernelGGL(cd_ym_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->trial_len, ntr, q, p, c->T, c->cdym_part);
   hipLaunchKernelGGL(reduce_parts_kernel, dim3(((p + 1) * q + 31) / 32), dim3(256), 0, c->st, c->cdym_part, nbk, (p + 1) * q, c->cdym);
   HIPC(hipGetLastError());
   c->cdym_valid = true;
@@ -29,7 +29,7 @@ static int cd_sweep(pgpfa_ctx* c) {
   const int len = (p + 2) * q;
   CdArgs a{};
   a.Y = c->Y; a.Yhi = c->Yhi; a.mean = c->Xmode; a.vsm = c->vsm; a.vec = c->vec;
-  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size();
+  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); a.len = c->trial_len;
   a.part = c->cdpart; a.q = q; a.p = p; a.T = T; a.dbg = c->cd_debug;
   const double flops = (double)a.ntr * q * T * (2.0 * p * p + 8.0 * p);
   if (c->mfma && c->cd_mfma && p <= 10) {
@@ -148,7 +148,7 @@ int pgpfa_mstep_cd_newton_pass(pgpfa_ctx* c, const double* vecCd, const double* 
   if (prior_center) CHK(upload_nosync(c, c->cdcenter, prior_center, (size_t)q * D * sizeof(double)));
   CdArgs a{};
   a.Y = c->Y; a.Yhi = c->Yhi; a.mean = c->Xmode; a.vsm = c->vsm; a.vec = c->vec;
-  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size();
+  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); a.len = c->trial_len;
   a.part = c->cdhpart; a.q = q; a.p = p; a.T = T; a.dbg = c->cd_debug;
   int nby = std::max(1, std::min(a.ntr * 4, 128));
   const bool on_mfma = c->mfma && c->cd_mfma && c->cd_hess_mfma && p <= 10;     // two-stage matrix-core form (mstep.h)

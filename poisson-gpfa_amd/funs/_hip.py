@@ -28,6 +28,7 @@ _SIGNATURES = {
     'pgpfa_upload_counts_f64': [ct.c_void_p, c_double_p],
     'pgpfa_upload_counts_u8': [ct.c_void_p, c_uint8_p],
     'pgpfa_upload_counts_u16': [ct.c_void_p, ct.POINTER(ct.c_uint16)],
+    'pgpfa_set_trial_lengths': [ct.c_void_p, c_int32_p],
     'pgpfa_get_counts_u16': [ct.c_void_p, ct.c_int, c_int32_p, ct.POINTER(ct.c_uint16)],
     'pgpfa_set_params': [ct.c_void_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_get_gram': [ct.c_void_p, c_double_p],
@@ -184,6 +185,17 @@ class Context:
         else:
             Y = as_f64(Y)
             check(self.lib.pgpfa_upload_counts_f64(self.h, dptr(Y)))
+
+    def set_trial_lengths(self, lengths):
+        """Per-trial bin counts T_r (1..T) of the zero-padded resident counts; None: every trial has T bins again.  Bins t >= T_r of trial r
+        then carry no likelihood term (pgpfa_set_trial_lengths); getters keep their padded shapes."""
+        if lengths is None:
+            check(self.lib.pgpfa_set_trial_lengths(self.h, None))
+            return
+        ln = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if ln.shape != (self.R,):
+            raise ValueError('one length per trial expected (R=%d), got %d' % (self.R, ln.size))
+        check(self.lib.pgpfa_set_trial_lengths(self.h, iptr(ln)))
 
     def set_params(self, C, d, tau):
         C, d, tau = as_f64(C), as_f64(d).reshape(-1), as_f64(tau).reshape(-1)

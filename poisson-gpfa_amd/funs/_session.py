@@ -246,10 +246,12 @@ class DeviceInfRes(dict):
         n = len(self.trial_idx)
         tid = self.trial_idx
         self.local_positions = local_pos                              # positions in the caller's trial list
-        self['post_mean'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_mean') and ctx.post_mean(tid[i:i + 1])[0])
-        self['post_vsm'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_vsm') and ctx.post_vsm(tid[i:i + 1])[0])
-        self['post_vsmGP'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_vsmGP') and ctx.post_vsmgp(tid[i:i + 1])[0])
-        self['post_cov'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_cov') and ctx.post_cov(int(tid[i])))
+        # (trials of unequal length: the device keeps every trial padded to the longest; an entry is cut to the trial's own bins)
+        cut = session.cut
+        self['post_mean'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_mean') and cut('post_mean', tid[i], ctx.post_mean(tid[i:i + 1])[0]))
+        self['post_vsm'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_vsm') and cut('post_vsm', tid[i], ctx.post_vsm(tid[i:i + 1])[0]))
+        self['post_vsmGP'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_vsmGP') and cut('post_vsmGP', tid[i], ctx.post_vsmgp(tid[i:i + 1])[0]))
+        self['post_cov'] = LazyTrialList(n, lambda i: self._fresh(i, 'post_cov') and cut('post_cov', tid[i], ctx.post_cov(int(tid[i]))))
 
     def _fresh(self, i, what):
         """The reference returns immutable per-trial arrays; here entry i is a view of device memory that the next
@@ -281,7 +283,7 @@ class DeviceInfRes(dict):
                 part = missing[c0:c0 + step]
                 arr = fetch[key](self.trial_idx[part])
                 for j, i in enumerate(part):
-                    lst._cache[i] = arr[j].copy()
+                    lst._cache[i] = self.session.cut(key, self.trial_idx[i], arr[j]).copy()
         return self
 
     def host_bytes(self, keys=('post_mean', 'post_vsm')):
@@ -296,7 +298,7 @@ class DeviceOptimRes(LazyTrialList):
     def __init__(self, session, trial_idx):
         tid = np.asarray(trial_idx, dtype=np.int32)
         ctx = session.ctx
-        super().__init__(len(tid), lambda i: self._fresh(i) and ctx.post_mean(tid[i:i + 1])[0].reshape(-1))
+        super().__init__(len(tid), lambda i: self._fresh(i) and session.cut('post_mean', tid[i], ctx.post_mean(tid[i:i + 1])[0]).reshape(-1))
         self.session = session
         self.trial_idx = tid
         self.stamp = session.mode_stamp
@@ -351,11 +353,19 @@ class DeviceDualOptimRes(LazyTrialList):
 
 # ----------------------------------------------------------------------------------------------
 class Session:
-    def __init__(self, Y, p, bin_ms):
+    def __init__(self, Y, p, bin_ms, lengths=None):
         R, q, T = Y.shape
         self.R, self.q, self.T, self.p = R, q, T, p
+        # per-trial bin counts, or None when every trial has T bins (then nothing below differs from a context without the table)
+        self.lengths = None
+        if lengths is not None and np.any(np.asarray(lengths) != T):
+            self.lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
+            if self.lengths.shape != (R,):
+                raise ValueError('one length per trial expected')
         self.ctx = _hip.Context(q, p, T, R, bin_ms, device=WORLD.device())
         self.ctx.upload_counts(Y)
+        if self.lengths is not None:
+            self.ctx.set_trial_lengths(self.lengths)
         self.post_stamp = 0
         self.mode_stamp = 0
         self.trial_stamp = np.zeros(R, dtype=np.int64)      # post_stamp of the E-step that last wrote each trial's posterior
@@ -386,6 +396,48 @@ class Session:
     def set_params(self, params):
         self.ctx.set_params(params['C'], params['d'], params['tau'])
 
+    def cut(self, key, trial, arr):
+        """The padded device entry `arr` of `trial` restricted to the trial's own T_r bins: post_mean (p, T_r), post_vsm (T_r, p, p),
+        post_vsmGP (T_r, T_r, p), post_cov the p T_r x p T_r sub-matrix (latent-major).  Equal trials: `arr` itself."""
+        if self.lengths is None:
+            return arr
+        L = int(self.lengths[int(trial)])
+        if L == self.T:
+            return arr
+        if key == 'post_mean':
+            return np.ascontiguousarray(arr[:, :L])
+        if key == 'post_vsm':
+            return np.ascontiguousarray(arr[:L])
+        if key == 'post_vsmGP':
+            return np.ascontiguousarray(arr[:L, :L])
+        if key == 'post_cov':
+            keep = (np.arange(self.p)[:, None] * self.T + np.arange(L)[None, :]).reshape(-1)
+            return np.ascontiguousarray(arr[np.ix_(keep, keep)])
+        raise KeyError(key)
+
+    def pad_modes(self, trials, rows):
+        """Host modes of the listed trials as one (n, p*T) array.  With trials of unequal length an entry may have the trial's own
+        p*T_r values (what lapOptimRes returns): its padded bins start at zero."""
+        if self.lengths is None:
+            return np.stack([np.asarray(x, dtype=np.float64).reshape(-1) for x in rows])
+        X = np.zeros((len(rows), self.p, self.T))
+        for j, (t, x) in enumerate(zip(trials, rows)):
+            x = np.asarray(x, dtype=np.float64).reshape(-1)
+            L = int(self.lengths[int(t)])
+            if x.size == self.p * L:
+                X[j, :, :L] = x.reshape(self.p, L)
+            elif x.size == self.p * self.T:
+                X[j] = x.reshape(self.p, self.T)
+            else:
+                raise ValueError('prevOptimRes entry %d has %d values; trial %d has %d bins (xdim*T_r = %d)' % (j, x.size, int(t), L, self.p * L))
+        return X.reshape(len(rows), -1)
+
+    def refuse_unequal(self, what):
+        """Entry points that do not know per-trial lengths must not run on padded data as if the padding were observed."""
+        if self.lengths is not None:
+            raise NotImplementedError('%s does not support trials of unequal length yet (this experiment has %d..%d bins per trial); '
+                                      'only the Laplace EM path does' % (what, int(self.lengths.min()), int(self.lengths.max())))
+
     def mark_dual_written(self, trial_idx):
         """A variational E-step has just overwritten the resident dual variables of these trials."""
         self.dual_stamp += 1
@@ -408,7 +460,27 @@ _sessions = weakref.WeakKeyDictionary()
 
 
 def _stack_counts(experiment):
-    Y = np.stack([np.asarray(tr['Y']) for tr in experiment.data])
+    """(counts [R][q][T], lengths [R]) of experiment.data: T is the longest trial, shorter trials are padded with zeros behind their
+    own T_r bins.  Raises ValueError for a trial without bins or trials with different numbers of neurons."""
+    trials = [np.asarray(tr['Y']) for tr in experiment.data]
+    for r, y in enumerate(trials):
+        if y.ndim != 2:
+            raise ValueError("trial %d: 'Y' must be (ydim, T), got shape %s" % (r, y.shape))
+        if y.shape[0] != trials[0].shape[0]:
+            raise ValueError('trial %d has %d neurons, trial 0 has %d' % (r, y.shape[0], trials[0].shape[0]))
+        if y.shape[1] < 1:
+            raise ValueError('trial %d has no bins' % r)
+    lengths = np.asarray([y.shape[1] for y in trials], dtype=np.int32)
+    if np.all(lengths == lengths[0]):
+        Y = np.stack(trials)
+    else:
+        Y = np.zeros((len(trials), trials[0].shape[0], int(lengths.max())), dtype=np.result_type(*trials))
+        for r, y in enumerate(trials):
+            Y[r, :, :y.shape[1]] = y
+    return _pack_counts(Y), lengths
+
+
+def _pack_counts(Y):
     if Y.min() >= 0 and Y.max() <= 65535 and np.all(Y == np.floor(Y)):
         return Y.astype(np.uint8 if Y.max() <= 255 else np.uint16)
     return Y.astype(np.float64)            # (the C-ABI rejects it with the reason)
@@ -430,8 +502,8 @@ def session_for(experiment, p):
     n_trials = len(experiment.data)
     sess = per_exp.get(p)
     if sess is None or sess.R != n_trials:
-        Y = _stack_counts(experiment)
-        sess = Session(Y, p, float(experiment.binSize))
+        Y, lengths = _stack_counts(experiment)
+        sess = Session(Y, p, float(experiment.binSize), lengths)
         per_exp[p] = sess
     return sess, np.arange(n_trials, dtype=np.int32)
 

@@ -44,7 +44,9 @@ class PPGPFAfit():
         if inferenceMethod not in ('laplace', 'variational'):
             raise ValueError("inferenceMethod must be 'laplace' or 'variational'")
         self.experiment = experiment
-        ydim, T = np.shape(experiment.data[0]['Y'])
+        ydim = np.shape(experiment.data[0]['Y'])[0]
+        trialBins = [int(np.shape(tr['Y'])[1]) for tr in experiment.data]
+        T = max(trialBins)                                     # trials may differ in length: T is the longest
         numTrials = len(experiment.data)
         if initParams is None:
             initParams = util.initializeParams(xdim, ydim, experiment)
@@ -177,6 +179,8 @@ class PPGPFAfit():
             self.onlineParamUpdateMethod = onlineParamUpdateMethod
 
         self.xdim, self.ydim, self.T = xdim, ydim, T
+        # bins per trial on average: what an expected spike count per trial is taken over (equal trials: T itself)
+        self.meanT = T if min(trialBins) == T else float(np.mean(trialBins))
         self.trialDur, self.binSize, self.numTrials = experiment.trialDur, experiment.binSize, numTrials
         self.maxEMiter, self.EMmode, self.inferenceMethod = maxEMiter, EMmode, inferenceMethod
         self.initParams, self.paramSeq, self.optimParams = initParams, paramSeq, params
@@ -205,7 +209,7 @@ class PPGPFAfit():
         for i in range(n):
             C = np.asarray(seq[i]['C'], dtype=np.float64)
             self.tauSeq[:, i] = np.asarray(seq[i]['tau']).reshape(-1)
-            self.expectedSpikeCountsEst[:, i] = self.T * np.exp(0.5 * np.sum(C * C, axis=1) + np.asarray(seq[i]['d']).reshape(-1))
+            self.expectedSpikeCountsEst[:, i] = self.meanT * np.exp(0.5 * np.sum(C * C, axis=1) + np.asarray(seq[i]['d']).reshape(-1))
             self.CabsoluteValue[i] = float(np.sum(C ** 2))
         self.expectedSpikeCountsEstVar = np.var(self.expectedSpikeCountsEst, axis=0)
         # per-neuron total counts / number of trials: from the device's integer sums, not from a host raster
@@ -215,7 +219,7 @@ class PPGPFAfit():
         self.sampleMeanSpikeCountsVar = np.var(self.sampleMeanSpikeCounts)
         if hasattr(self.experiment, 'params'):
             Ct = np.asarray(self.experiment.params['C'], dtype=np.float64)
-            self.expectedSpikeCountsTrue = self.T * np.exp(0.5 * np.sum(Ct * Ct, axis=1) + np.asarray(self.experiment.params['d']).reshape(-1))
+            self.expectedSpikeCountsTrue = self.meanT * np.exp(0.5 * np.sum(Ct * Ct, axis=1) + np.asarray(self.experiment.params['d']).reshape(-1))
             self.expectedSpikeCountsTrueVar = np.var(self.expectedSpikeCountsTrue)
             self.varESpkCountTrue_Ratios = self.expectedSpikeCountsEstVar / self.expectedSpikeCountsTrueVar
             self.subspaceAngleC = [util.subspaceAngle(self.experiment.params['C'], seq[i]['C']) for i in range(n)]
@@ -250,7 +254,9 @@ class PPGPFAfit():
         import scipy.linalg
         _, D, Vh = scipy.linalg.svd(np.asarray(self.optimParams['C'], dtype=np.float64))
         mix = np.diag(D) @ Vh.T
-        self.x_tilde = np.asarray([mix @ np.asarray(self.infRes['post_mean'][tr]) for tr in range(self.numTrials)])
+        x_tilde = [mix @ np.asarray(self.infRes['post_mean'][tr]) for tr in range(self.numTrials)]
+        # (trials of unequal length: a list of (xdim, T_r) arrays)
+        self.x_tilde = np.asarray(x_tilde) if len({x.shape for x in x_tilde}) <= 1 else x_tilde
 
     def leaveOneOutPrediction(self):
         """reference engine.py:599-644: y_pred_mode[numTrials][ydim][T] and pred_err_mode with the fitted parameters."""

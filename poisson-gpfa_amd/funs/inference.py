@@ -89,6 +89,8 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     entries are lazy device-backed sequences; 'post_cov' and 'post_vsmGP' are rebuilt on access.
     prevOptimRes: the previous call's lapOptimRes (or host arrays) as in the reference; additionally the string
     'resident' starts every trial from the mode an earlier E-step left on the device, if any (minibatch EM).
+    Trials may differ in length (experiment.data[r]['Y'] of shape (ydim, T_r)): entries of trial r then have T_r bins, lapOptimRes[r]
+    xdim*T_r values, and bins past T_r carry no likelihood term on the device.
     """
     sess, trial_idx = _prepare(experiment, params)
     n_all = len(trial_idx)
@@ -107,9 +109,9 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
                     and prevOptimRes.stamp == sess.mode_stamp and np.array_equal(prevOptimRes.trial_idx, mine))
         if not resident:
             if len(prevOptimRes) == n_all:
-                X = np.stack([np.asarray(prevOptimRes[i], dtype=np.float64).reshape(-1) for i in range(lo, hi)])
+                X = sess.pad_modes(mine, [prevOptimRes[i] for i in range(lo, hi)])
             elif len(prevOptimRes) == len(mine):
-                X = np.stack([np.asarray(x, dtype=np.float64).reshape(-1) for x in prevOptimRes])
+                X = sess.pad_modes(mine, list(prevOptimRes))
             else:
                 raise ValueError('prevOptimRes has %d entries for %d trials' % (len(prevOptimRes), n_all))
             if len(mine):
@@ -471,6 +473,7 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     """
     import scipy.optimize as op
     sess, trial_idx = _prepare(experiment, params)
+    sess.refuse_unequal('dualVariational')
     n_all = len(trial_idx)
     local_shard = bool(getattr(experiment, '_pgpfa_local_shard', False))
     lo, hi = (0, n_all) if local_shard else sess.local_slice(n_all)

@@ -95,6 +95,7 @@ def leaveOneOutPrediction(params, experiment):
     from . import _session
     xdim = np.shape(params['C'])[1]
     sess, trial_idx = _session.session_for(experiment, xdim)
+    sess.refuse_unequal('leaveOneOutPrediction')
     lo, hi = (0, len(trial_idx)) if getattr(experiment, '_pgpfa_local_shard', False) else sess.local_slice(len(trial_idx))
     sess.set_params(params)
     y_loc, err_loc = sess.ctx.loo_predict(trial_idx[lo:hi])
@@ -269,7 +270,8 @@ class dataset:
 def countMoments(experiment, xdim):
     """Mean and covariance of the spike counts over all (trial, bin) samples - np.mean / np.cov of the concatenated
     raster (reference util.py:523-533, engine.py:487-492) - from the device's exact integer sums of the resident
-    count tensor; the raster is never formed on the host.  Returns (mean[q], cov[q][q], per-neuron totals, samples)."""
+    count tensor; the raster is never formed on the host.  Returns (mean[q], cov[q][q], per-neuron totals, samples).
+    Trials of unequal length: the samples are the sum of the trials' own bin counts (their padding is no sample)."""
     from . import _session
     sess, trial_idx = _session.session_for(experiment, xdim)
     local = getattr(experiment, '_pgpfa_local_shard', False)

@@ -62,6 +62,16 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * "dual_f32" (0; 1: with dual_lowrank, the r x r system B = I + F^T Wt F, its factorisation, its inverse and the Yt product run in single
  * precision on the FP32 matrix cores, log det / covariance blocks / gradient accumulated in FP64: the mixed-precision form BASELINE
  * config 5 asks for; 2: the same with B assembled in FP64 and rounded once),
+ * "laplace_f32" (0 - the default: the FP64 engine, the same instructions and bits as without the option; 1: in the passes of the low-rank engine that
+ * produce post_vsmGP or its sum - the covariance phase of pgpfa_estep_laplace, sum-only or with "keep_trial_vsmgp", and the per-trial blocks
+ * rebuilt on demand - B = I + F^T Wt F is assembled from single-precision factors, factorised and inverted on the FP32 matrix cores (the 128-wide
+ * diagonal blocks of the factorisation in FP64 registers over the single-precision slab, rounded once); L^-T is
+ * then widened to FP64 and everything behind it - the Yt product or the fused pass, the mixing, the split sums, post_vsm, post_vsmGP, PautoSum -
+ * is the FP64 path, unchanged; 2: the same with B assembled in FP64 and rounded once; any other value fails.  The mode search and the objective
+ * do not depend on it (bit-identical); the split verdict, the fused / unfused choice and the workspace plan come out the same.  A chunk whose
+ * single-precision factorisation meets a non-positive pivot is redone in FP64 as a whole - info "last_cov_f32_fallbacks" - never an error.  The
+ * dense engine ignores the option and "dual_f32" keeps its meaning for the dual's evaluations.  Measured error of the covariance outputs
+ * against a dense FP64 inverse: docs/history/laplace_f32.md),
  * "pcg_fused" (1: inner PCG iterations without host round trips, pcg.h), "pcg_w32" (1: packed FP32 curvature blocks in the PCG
  * Hessian-vector product), "cd_mfma" (1: (C,d) sweep on the matrix cores, mstep.h), "cd_hess_mfma" (1: the Newton pass
  * of the (C,d) M-step - cost, gradient, per-neuron Hessians - on the matrix cores up to 10 latents; 0: the vector kernel), "vsm_mfma" (1: beyond 10 latents the per-bin
@@ -153,7 +163,10 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * "last_newton_solves", "last_pcg_iterations", "last_shared_factorizations", "last_cov_lowrank",
  * "last_dense_retries", "hbm_bytes_allocated", "hbm_bytes_free" / "hbm_bytes_total" (hipMemGetInfo of the context's device, now), "n_trials_global", "prof_<tag>_{ms,flops,launches}" (tags gemm, potrf, solve, poisson, assemble, vsm, cd, mix; "prof_mix_flops" counts BYTES for the stand-alone mixing
  * passes and FLOPs - products + mixing - when "last_yt_mix_fused" is 1), "counts_two_bytes",
- * "arena_bytes", "last_split_cov", "last_yt_mix_fused" (1 when the last covariance pass ran product and mixing as one kernel), "last_eps_wt_norm", "last_eps_wt_rms", "last_newton_solve_ms", "last_newton_solve_bytes",
+ * "arena_bytes", "last_split_cov", "last_yt_mix_fused" (1 when the last covariance pass ran product and mixing as one kernel), "last_cov_f32" (1 when the last covariance pass ran the
+ * single-precision r x r phase of "laplace_f32", else 0: set by every pass, as "last_split_cov"), "last_cov_f32_fallbacks" (chunks of the last
+ * pgpfa_estep_laplace call redone in FP64 after a non-positive pivot of the single-precision factorisation; reset at the start of that call),
+ * "last_eps_wt_norm", "last_eps_wt_rms", "last_newton_solve_ms", "last_newton_solve_bytes",
  * "last_newton_solve_bytes_moved" (what the step's kernels really move: with "pcg_vec32" five of its vectors are single precision),
  * "last_newton_solve_bytes_survey" (the same slot-iterations priced at q T + 8 (2 p T + T p^2) bytes each: SURVEY 8(d)'s B_E per pass per trial),
  * "arena_vmm_failed" (1 once the virtual-memory arena fell back to plain allocations), "last_newton_max_iter", "last_dual_evaluations",

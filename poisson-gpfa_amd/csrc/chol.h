@@ -247,9 +247,12 @@ __device__ __forceinline__ void potrf_diag_inverse(PotrfLds<T>& S, int tid, int 
 // v_readlane, no barrier - with the rank-16 trailing updates on the matrix cores: a column still costs ~1000 cycles - the FP64 reciprocal
 // square root and the 30 lane broadcasts of a step are one dependent chain - 70 us against 62, and 300 against 180 at batch 1024, where the
 // other seven waves of every workgroup wait.)
-template <typename T, int PH = 3, int ALG = 2>
-__global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, long long sH, int ld, int k0,
-                                                            T* __restrict__ Dinv, long long sD,
+// TS: type of the slabs (default: T).  <double, 3, 2, float> factors and inverts a block of a SINGLE-precision slab in FP64 registers and LDS and rounds L and
+// L^-1 once on the way out (option laplace_f32): a float trailing block is rounded at each of its up to 127 rank-1 updates, and the kernel is bound by the
+// latency of its steps, not by their arithmetic.
+template <typename T, int PH = 3, int ALG = 2, typename TS = T>
+__global__ __launch_bounds__(512) void potrf_diag_kernel_t(TS* __restrict__ H, long long sH, int ld, int k0,
+                                                            TS* __restrict__ Dinv, long long sD,
                                                             const int* __restrict__ slots, int* __restrict__ info) {
   __shared__ __attribute__((aligned(16))) PotrfLds<T> S;
   const int tid = threadIdx.x;
@@ -257,8 +260,8 @@ __global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, lo
   const int cg = tid >> 7;                      // 0..3, uniform per wave
   const int pos_r = (r & 3) * 32 + (r >> 2);
   const long long slot = slots ? slots[blockIdx.x] : blockIdx.x;
-  T* Hs = H + slot * sH + (size_t)k0 * ld + k0;
-  T* Ds = Dinv + slot * sD + (size_t)(k0 / NB) * NB * NB;
+  TS* Hs = H + slot * sH + (size_t)k0 * ld + k0;
+  TS* Ds = Dinv + slot * sD + (size_t)(k0 / NB) * NB * NB;
 
   if constexpr (ALG == 2) {
     const int tr = tid & 31, tc = tid >> 5;
@@ -266,7 +269,7 @@ __global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, lo
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int m = 0; m < 8; ++m) a2[i][m] = Hs[(size_t)(tc + 16 * m) * ld + tr + 32 * i];   // entries above the diagonal are never used
+      for (int m = 0; m < 8; ++m) a2[i][m] = (T)Hs[(size_t)(tc + 16 * m) * ld + tr + 32 * i];   // entries above the diagonal are never used
     if constexpr (PH & 1) {
       potrf_diag_chol_steps2<0>(a2, S, tr, tc, info, slot, k0);
       potrf_diag_chol_steps2<1>(a2, S, tr, tc, info, slot, k0);
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, lo
   } else {
     T a[32];
 #pragma unroll
-    for (int m = 0; m < 32; ++m) a[m] = Hs[(size_t)(cg + 4 * m) * ld + r];   // entries above the diagonal are never used
+    for (int m = 0; m < 32; ++m) a[m] = (T)Hs[(size_t)(cg + 4 * m) * ld + r];   // entries above the diagonal are never used
     if constexpr (PH & 1) {
       potrf_diag_chol_steps<0>(a, S, r, cg, pos_r, info, slot, k0);
       potrf_diag_chol_steps<1>(a, S, r, cg, pos_r, info, slot, k0);
@@ -301,13 +304,13 @@ __global__ __launch_bounds__(512) void potrf_diag_kernel_t(T* __restrict__ H, lo
   __syncthreads();
   for (int e = tid; e < NB * NB; e += 512) {
     const int rr = e & (NB - 1), cc = e >> 7;
-    if (rr >= cc) Hs[(size_t)cc * ld + rr] = S.L[potrf_lidx(cc, rr)];
+    if (rr >= cc) Hs[(size_t)cc * ld + rr] = (TS)S.L[potrf_lidx(cc, rr)];
   }
   // ---- X = L^-1 over the factor in LDS, then out (Ds[c][r] = X[r][c], zero above the diagonal)
   if constexpr (PH & 2) potrf_diag_inverse(S, tid, r, cg);
   for (int e = tid; e < NB * NB; e += 512) {
     const int rr = e & (NB - 1), cc = e >> 7;
-    Ds[(size_t)cc * NB + rr] = (rr >= cc) ? S.L[potrf_lidx(cc, rr)] : (T)0;
+    Ds[(size_t)cc * NB + rr] = (rr >= cc) ? (TS)S.L[potrf_lidx(cc, rr)] : (TS)0;
   }
 }
 

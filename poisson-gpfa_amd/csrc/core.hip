@@ -984,6 +984,8 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   c->info["last_eps_wt_rms"] = 0.0;
   c->info["last_split_cov"] = 0.0;
   c->info["last_yt_mix_fused"] = 0.0;
+  c->info["last_cov_f32"] = 0.0;
+  c->info["last_cov_f32_fallbacks"] = 0.0;
   for (const char* k : {"plan_ms_total", "plans", "set_params_calls", "last_retry_ms", "last_dense_retries", "last_param_step", "last_param_step_prev",
                         "last_fallback_no_descent", "last_fallback_line_search", "last_fallback_outer_cap", "arena_grow_ms_total", "last_cold_restarts"}) c->info[k] = 0.0;
   *out = c;
@@ -1083,6 +1085,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "keep_trial_vsmgp") c->keep_trial_vsmgp = (v != 0.0);
   else if (k == "dual_lowrank") c->dual_lowrank = (v != 0.0);
   else if (k == "dual_f32") c->dual_f32 = (int)v;
+  else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
   else if (k == "dual_gemm") c->dual_gemm = (v != 0.0);

@@ -91,6 +91,7 @@ int ensure_vsmgp_buffer(pgpfa_ctx* c) {
 
 static int posterior_blocks_dense(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp) {
   const int T = c->T, p = c->p;
+  c->info["last_cov_f32"] = 0.0;                             // (option laplace_f32 is the low-rank engine's)
   CHK(ensure_mt_clean(c));
   c->last_cov_lowrank = false;
   CHK(assemble(c, c->ident, nb, diag_scale));
@@ -325,7 +326,8 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
 // B = I + F^T Wt F instead of the n x n Hessian.  Uses the dense engine's slabs as scratch (ld = rpad views).
 // logdet_out (optional, host, nb entries): log det of the posterior precision K^-1 + scatter(W) of every slot,
 //   = -sum_k log det K_k + sum_t log det(I + eps W_t) + log det(I + F^T Wt F)   (Sylvester; K_k = eps I + F_k F_k^T)
-int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out) {
+// (allow_lap32 = false: the FP64 pass that redoes a chunk whose single-precision factorisation failed under option laplace_f32)
+static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, bool allow_lap32) {
   const int T = c->T, p = c->p, Tp = c->Tp, pp = p * p;
   const int rpad = c->rpad;
   const int ract = round_up(c->rtot, 16);          // columns of Yt that are not identically zero (rpad rounds to 128 for the factor)
@@ -335,7 +337,8 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
   CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, logdet_out ? c->ldet_buf : nullptr));
   // sum-only accumulation by the split form (split.h)?  Decided by the relative size of the mixing correction of this chunk,
   // max_t eps ||Wt_t||_inf, measured here and read back just before the mixing pass (info key "last_eps_wt_norm")
-  // (want_vsmgp passes run the FP64 engine whatever dual_f32 says - it only concerns the dual's evaluations - so the split form does not ask)
+  // (want_vsmgp passes run the FP64 engine whatever dual_f32 says - it only concerns the dual's evaluations - and under laplace_f32 everything the
+  //  split form touches is FP64 as well, so the split form does not ask)
   const bool split_candidate = want_vsmgp && accumulate && c->split_cov && c->mfma && (p <= 16 || (p <= 20 && c->mix_wide));
   unsigned* norm_bits = reinterpret_cast<unsigned*>(c->pcg_ratio);         // (scratch word: the inner solves are over)
   if (split_candidate || c->measure_mix) {
@@ -353,7 +356,13 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
   // Mixed precision (option dual_f32, dual-variational evaluations only): B, its Cholesky factor, L^-T and Yt = F L^-T - the O(T r^2) and
   // O(r^3) parts - run on the FP32 matrix cores (twice the FP64 rate, half the bytes); log det and the per-bin covariance blocks are
   // accumulated in FP64 from the single-precision factors.  (dual_f32 = 2: B is still assembled in FP64 and rounded once.)
-  const bool f32 = c->dual_f32 && !want_vsmgp;
+  // Option laplace_f32 (want_vsmgp passes: the Laplace E-step and the blocks rebuilt on demand): the same single-precision B, factor and L^-T; L^-T is then
+  // widened into the FP64 slab (widen_upper_f64_kernel) and everything from Yt on is the FP64 path below, unchanged.  A chunk with a non-positive pivot in
+  // the single-precision factorisation is redone in FP64.
+  const int f32_mode = want_vsmgp ? (allow_lap32 ? c->laplace_f32 : 0) : c->dual_f32;
+  const bool f32 = f32_mode != 0;
+  const bool lap32 = f32 && want_vsmgp;
+  c->info["last_cov_f32"] = lap32 ? 1.0 : 0.0;
   // Yt = F L^-T: L^-T is upper triangular, so the rows of Yt that belong to latent k vanish left of column roff[k].  When the consumer knows
   // the same offsets and takes those entries as zeros without reading them (the mixing pass up to 16 latents, the matrix-core post_vsm
   // beyond 10) the product skips the whole 128-column tiles left of it: ~45 % of the flops and stores.
@@ -383,7 +392,7 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
     }
   }
   HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
-  if (f32 && c->dual_f32 == 1) {
+  if (f32 && f32_mode == 1) {
     hipLaunchKernelGGL(assemble_b_kernel_t<float>, dim3(npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, reinterpret_cast<float*>(lwf.H),
                        (long long)lwf.sH, rpad, nblk64, (const float*)c->Flr32, Tp, T, p, c->d_blk_lat, c->d_blk_col, c->Wt, sW, c->ident, nb, cmap);
     if (cmap && rpad > c->rtot)
@@ -396,11 +405,13 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
   }
   HIPC(hipGetLastError());
   if (f32) {
-    if (c->dual_f32 != 1)
+    if (f32_mode != 1)
       hipLaunchKernelGGL(cvt_lower_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH,
                          reinterpret_cast<float*>(lwf.H), (long long)lwf.sH, rpad);
     c->mt_dirty = true;
-    CHK(factor(c, lwf, c->ident, nb, true));
+    // (laplace_f32: the diagonal blocks of the factorisation in FP64 registers over the single-precision slab - their 127 rank-1 steps in float cost
+    //  6 x the error of the rest, and the kernel is latency-bound either way; the dual's dual_f32 keeps its arithmetic)
+    CHK(factor(c, lwf, c->ident, nb, true, lap32));
   } else {
     CHK(factor(c, lw, c->ident, nb));
   }
@@ -419,7 +430,7 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
     for (int s2 = 0; s2 < nb; ++s2) logdet_out[s2] = -ldk + a[s2] + b2[s2];
   }
   c->mt_dirty = true;
-  if (f32) {
+  if (f32 && !lap32) {
     hipLaunchKernelGGL(fill_slabs_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st,
                        reinterpret_cast<float*>(lwf.Mt), (long long)lwf.sM, (size_t)rpad * rpad, 0.0f);
     CHK(inverse_t(c, lwf, c->ident, nb, true));
@@ -454,6 +465,33 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
     HIPC(hipGetLastError());
     return 0;
   }
+  if (lap32) {
+    // L^-T in single precision into the H slabs (float view, cleared first as for the dual), then widened into the Mt slabs - the single-precision factor
+    // there is dead - before anything writes Yt or D into the H slabs.  The widening writes the zeros the two clears below would have left.
+    hipLaunchKernelGGL(fill_slabs_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st,
+                       reinterpret_cast<float*>(lwf.Mt), (long long)lwf.sM, (size_t)rpad * rpad, 0.0f);
+    CHK(inverse_t(c, lwf, c->ident, nb, true));
+    const int full = (skip_zero_cols && c->mt_fill) ? 0 : 1;
+    const bool vec = lw.sM % 2 == 0 && lw.sH % 2 == 0 && (reinterpret_cast<uintptr_t>(lw.Mt) & 15) == 0 && (reinterpret_cast<uintptr_t>(lw.H) & 15) == 0;
+    prof_begin(c, TAG_MIX, (double)nb * rpad * lw.nact * 6.0);          // (bytes, roughly: the upper triangle read in FP32 and written in FP64)
+    if (vec)
+      hipLaunchKernelGGL(widen_upper_f64_kernel<true>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
+                         lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
+    else
+      hipLaunchKernelGGL(widen_upper_f64_kernel<false>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
+                         lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
+    prof_end(c);
+    HIPC(hipGetLastError());
+    // B >= I in exact arithmetic, so a bad pivot needs cond(B) r 6e-8 of order one; the chunk is then redone through the FP64 path as a whole.  (The
+    // host waits for the factorisation here; where the fused pass runs it would wait for the split form's verdict a few lines on anyway.)
+    std::vector<int> pivot(nb, 0);
+    CHK(dl_enqueue(c, pivot.data(), c->ws.info, sizeof(int) * nb));
+    CHK(dl_flush(c));
+    if (std::any_of(pivot.begin(), pivot.end(), [](int v) { return v != 0; })) {
+      c->info["last_cov_f32_fallbacks"] += 1.0;
+      return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, false);
+    }
+  } else {
   // L^-T's slab holds whatever the last use left (another rank layout, the factor of a dense pass): clear what will be read and not written - all of it,
   // or, when every consumer starts at the latent's own columns (skip_zero_cols), the strictly lower entries of the p rectangles they read
   if (skip_zero_cols && c->mt_fill)
@@ -462,6 +500,7 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
     hipLaunchKernelGGL(fill_slabs_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.Mt, lw.sM,
                        (size_t)rpad * rpad, 0.0);
   CHK(inverse_t(c, lw, c->ident, nb));
+  }
   if (p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, p);
   // the split form's verdict: the relative size of the mixing correction, measured when the chunk's blocks were formed
   bool split = false, decided = false;
@@ -586,6 +625,10 @@ int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumul
   }
   HIPC(hipGetLastError());
   return 0;
+}
+
+int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out) {
+  return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, true);
 }
 
 int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate) {

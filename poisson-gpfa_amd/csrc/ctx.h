@@ -144,6 +144,8 @@ struct pgpfa_ctx {
   bool slab_row_align = true;                   // latent row stride of the Yt slab rounded up to 16 rows (128-byte lines)
   int dual_f32 = 0;                             // ... with the r x r factorisation, its inverse and Yt in single precision (mixed)
   float* Flr32 = nullptr; bool flr32_valid = false;   // single-precision copy of the low-rank factors
+  int laplace_f32 = 0;                          // option laplace_f32: the same single-precision r x r phase for the want_vsmgp passes of the low-rank engine (Laplace E-step, blocks
+                                                // rebuilt on demand); everything behind L^-T stays FP64 (cov.hip).  1: B assembled in FP32, 2: assembled in FP64 and rounded once
   bool keep_trial_vsmgp = false;
   bool pacc_used = false, pacc_valid = false;
   std::vector<char> vsmgp_ok;                    // per trial: c->vsmgp holds the blocks of the resident posterior
@@ -435,7 +437,7 @@ int get_slabs(pgpfa_ctx* c, const double* src, double* out);
 // linalg.hip: the GEMM kernel's launcher with profiling / tile choice / split-K, blocked factorisation and triangular inverse
 double gemm_flops(const pgpfa::GemmP& g);
 int gemm(pgpfa_ctx* c, bool transb, pgpfa::GemmP g, bool f32 = false);
-int factor(pgpfa_ctx* c, const pgpfa::CholWS& w, const int* slots, int nb, bool f32 = false);
+int factor(pgpfa_ctx* c, const pgpfa::CholWS& w, const int* slots, int nb, bool f32 = false, bool wide_diag = false);
 int inverse_t(pgpfa_ctx* c, const pgpfa::CholWS& w, const int* slots, int nb, bool f32 = false);
 // estep.hip: Poisson pass, prior products, shared preconditioner, the E-step driver
 int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G, double* W, double* flik, int full);

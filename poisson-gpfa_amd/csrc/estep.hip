@@ -1260,6 +1260,7 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
   c->pacc_used = false; c->pacc_valid = false;
   c->estep_serial += 1;
   c->info["last_eps_wt_norm"] = 0.0; c->info["last_eps_wt_rms"] = 0.0;      // maxima over the chunks of THIS call
+  c->info["last_cov_f32_fallbacks"] = 0.0;                                  // (counted over the chunks of this call: cov.hip)
   HIPC(hipMemsetAsync(c->Pacc, 0, (size_t)c->Tp * c->Tp * c->p * sizeof(double), c->st));
   snapshot_params(c, tr.v);
   for (int t : tr.v) c->trial_dual[t] = 0;

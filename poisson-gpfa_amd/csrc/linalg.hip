@@ -92,7 +92,8 @@ int gemm(pgpfa_ctx* c, bool transb, GemmP g, bool f32) {
 
 // chol_factor / chol_inverse_t with per-launch profiling (same sequence as chol.h's plain versions)
 // (f32: the slabs of w hold single-precision matrices - same pointers reinterpreted, strides in elements)
-int factor(pgpfa_ctx* c, const CholWS& w, const int* slots, int nb, bool f32) {
+// (wide_diag, with f32: the 128 x 128 diagonal blocks are factored and inverted in FP64 registers - chol.h)
+int factor(pgpfa_ctx* c, const CholWS& w, const int* slots, int nb, bool f32, bool wide_diag) {
   auto at = [f32](double* base, size_t off) { return f32 ? reinterpret_cast<double*>(reinterpret_cast<float*>(base) + off) : base + off; };
   const int np = w.npad, ld = w.ld;
   const int na = (w.nact > 0 && w.nact <= np) ? w.nact : np;   // rows >= na are identity padding: never updated
@@ -100,7 +101,10 @@ int factor(pgpfa_ctx* c, const CholWS& w, const int* slots, int nb, bool f32) {
     const int c1 = std::min(c0 + NSUP, np);
     for (int k0 = c0; k0 < c1; k0 += NB) {
       prof_begin(c, TAG_POTRF, 2.0 * nb * (double)NB * NB * NB / 3.0);
-      if (f32)
+      if (f32 && wide_diag)
+        hipLaunchKernelGGL((potrf_diag_kernel_t<double, 3, 2, float>), dim3(nb), dim3(512), 0, c->st, reinterpret_cast<float*>(w.H), w.sH, ld, k0,
+                           reinterpret_cast<float*>(w.Dinv), w.sD, slots, w.info);
+      else if (f32)
         hipLaunchKernelGGL(potrf_diag_kernel_t<float>, dim3(nb), dim3(512), 0, c->st, reinterpret_cast<float*>(w.H), w.sH, ld, k0,
                            reinterpret_cast<float*>(w.Dinv), w.sD, slots, w.info);
       else

@@ -3378,6 +3378,44 @@ inline __global__ void fill_slabs_f32_kernel(float* __restrict__ p, long long st
     if (i < n) dst[i] = v;
   }
 }
+// L^-T of the mixed Laplace covariance phase (option laplace_f32) from its single-precision slab into the FP64 slab of the same slot: src[slot] (float, n x n,
+// ld = n, upper triangular) -> dst[slot] (double, same shape), columns < nact only.  Below the diagonal it writes the zeros the FP64 path gets from its inverse
+// (the diagonal 128 x 128 blocks) and from clear_lower_reads_kernel (the rectangles the consumers read: rows of latent k - its count rounded up to 16 - from
+// column roff_k rounded down to `ctile` on), or, with full != 0, whole columns as fill_slabs_kernel; nothing below the diagonal of src is read.
+// A wave per column, four consecutive rows per lane (VEC: one 16-byte load, two 16-byte stores; needs 16-byte aligned slabs).  n % 4 == 0.
+// grid = (ceil(nact/4), nslots), block = 256
+template <bool VEC>
+__global__ __launch_bounds__(256) void widen_upper_f64_kernel(const float* __restrict__ src, long long sS, double* __restrict__ dst, long long sD, int n, int nact,
+                                                              const int* __restrict__ roff, int p, int ctile, int full) {
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= nact) return;
+  int zend = n;
+  if (!full) {
+    zend = min(n, (j / 128 + 1) * 128);
+    for (int k = 0; k < p; ++k) {
+      const int r0 = roff[k];
+      const int rend = r0 + min(((roff[k + 1] - r0 + 15) / 16) * 16, n - r0);
+      if (j >= (r0 / ctile) * ctile && j < rend) zend = max(zend, rend);
+    }
+  }
+  const float* a = src + (size_t)blockIdx.y * sS + (size_t)j * n;
+  double* b = dst + (size_t)blockIdx.y * sD + (size_t)j * n;
+  for (int r = 4 * (threadIdx.x & 63); r < zend; r += 256) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r <= j) {
+      if constexpr (VEC) v = *reinterpret_cast<const float4*>(a + r);
+      else v = make_float4(a[r], a[r + 1], a[r + 2], a[r + 3]);
+    }
+    const double2 lo = make_double2(r <= j ? (double)v.x : 0.0, r + 1 <= j ? (double)v.y : 0.0);
+    const double2 hi = make_double2(r + 2 <= j ? (double)v.z : 0.0, r + 3 <= j ? (double)v.w : 0.0);
+    if constexpr (VEC) {
+      *reinterpret_cast<double2*>(b + r) = lo;
+      *reinterpret_cast<double2*>(b + r + 2) = hi;
+    } else {
+      b[r] = lo.x; b[r + 1] = lo.y; b[r + 2] = hi.x; b[r + 3] = hi.y;
+    }
+  }
+}
 // log det from a single-precision Cholesky factor, accumulated in double: out[b] = 2 sum_i log L[b][i][i]
 inline __global__ void logdet_batch_f32_kernel(const float* __restrict__ L, long long sL, int ld, int n, double* __restrict__ out) {
   __shared__ double red[256];

@@ -93,6 +93,7 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     xdim*T_r values, and bins past T_r carry no likelihood term on the device.
     """
     sess, trial_idx = _prepare(experiment, params)
+    sess.ctx.set_option('laplace_f32', int(LAPLACE_F32))       # (True is 1; LAPLACE_F32 is defined next to DUAL_F32 below)
     n_all = len(trial_idx)
     # default: every rank holds the same experiment and takes a contiguous slice of its trials;
     # experiment._pgpfa_local_shard = True says this rank's experiment already IS its shard
@@ -385,6 +386,14 @@ DUAL_LOWRANK = True
 # with DUAL_LOWRANK: factorisation of the r x r system, its inverse and the Yt product of every dual evaluation in single precision
 # on the FP32 matrix cores, log det / covariance blocks / gradient accumulated in FP64 (BASELINE config 5 asks for fp32)
 DUAL_F32 = False
+# Laplace E-step under the low-rank covariance engine: the r x r system B = I + F^T Wt F of every trial, its Cholesky factor and L^-T in single
+# precision on the FP32 matrix cores (C-ABI option laplace_f32).  L^-T is widened to FP64 right behind the inverse and everything after it - the
+# Yt product, the mixing pass, the sums over trials, post_vsm / post_vsmGP / PautoSum - is the FP64 arithmetic of the default path; the mode
+# search and the objective are not touched (bit-identical).  False / 0: off; True / 1: B assembled in FP32 from single-precision factors;
+# 2: B assembled in FP64 and rounded once.  Measured error of the covariance outputs against dense FP64: docs/history/laplace_f32.md.  A chunk
+# whose single-precision factorisation meets a non-positive pivot is redone in FP64 (info key last_cov_f32_fallbacks).  The dense engine
+# ignores the flag; laplace() sends it on every call, dualVariational always runs its own covariance passes without it.
+LAPLACE_F32 = False
 
 
 class _ConcurrentProblems:
@@ -484,6 +493,7 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     # reference's 1e-6 diagonal jitter (inference.py:190) carried by the per-bin blocks; otherwise the dense engine
     ctx.set_option('dual_lowrank', 1 if DUAL_LOWRANK else 0)
     ctx.set_option('dual_f32', 1 if (DUAL_SOLVER in ('device', 'fixedpoint') and DUAL_LOWRANK and DUAL_F32) else 0)
+    ctx.set_option('laplace_f32', 0)                           # pgpfa_dual_finalize's blocks stay FP64 whatever LAPLACE_F32 says
     if DUAL_SOLVER in ('device', 'fixedpoint') and len(mine):
         # on the device, in rho = log(lambda); same optimum as either of the reference's variants
         def prev_rho():

@@ -409,830 +409,40 @@ static __global__ void zero_rows_kernel(double* __restrict__ X, long long ld, in
   if (i < n) X[(size_t)list[blockIdx.y] * ld + i] = 0.0;
 }
 
-int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, double* obj_sum, int32_t* iters, int32_t* status,
-                      const LooJob* loo, const VarJob* var) {
-  PhaseRange range_estep(var ? "pgpfa.dual_fixed_point" : loo ? "pgpfa.loo_mode_search" : "pgpfa.estep_laplace");
-  c->want_slots = std::max(c->want_slots, std::min((int)tr.v.size(), c->R));
-  CHK(ready_estep(c, allow_lr));
-  struct MaskGuard { pgpfa_ctx* c; ~MaskGuard() { c->mask_active = false; c->var_active = false; c->lam_out_active = false; } } mask_guard{c};
-  if (var) CHK(ensure_lambda(c));
-  const int N = (int)tr.v.size();
-  const auto t_begin = std::chrono::steady_clock::now();
-  const int nvec = c->n, p = c->p, T = c->T;
-  const long long ld = c->ld;
-  double total = 0.0;
+// ======== the E-step driver ========
+// estep_impl, at the end of this section, drives every mode search of the library - the Laplace E-step, the leave-one-neuron-out search (loo) and
+// the variational fixed point (var) - and reads top to bottom as DESIGN section 3.  Before it: its state as structs and one function per phase.
+namespace {
+
+struct MaskGuard { pgpfa_ctx* c; ~MaskGuard() { c->mask_active = false; c->var_active = false; c->lam_out_active = false; } };   // lasts the whole call
+struct NdevGuard { pgpfa_ctx* c; ~NdevGuard() { c->cur_ndev = nullptr; } };                                                       // lasts one inner solve
+struct WantGuard { pgpfa_ctx* c; int keep; ~WantGuard() { c->want_slots = keep; } };                                              // lasts one dense retry pass
+
+// what one call counts; publish() writes the info keys
+struct EstepStats {
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
   double n_fact = 0.0, n_solve = 0.0, n_pcg = 0.0, n_shared = 0.0;
-  double newton_bytes = 0.0;                          // mandatory HBM bytes of the inner PCG iterations run (see below)
+  double newton_bytes = 0.0;                          // mandatory HBM bytes of the inner PCG iterations run (see account_bytes)
   double newton_bytes_moved = 0.0;                    // what the kernels of the form in use really move per slot-iteration (single-precision vectors counted as such)
   double newton_bytes_survey = 0.0;                   // the same slot-iterations priced by SURVEY 8(d)'s B_E = q T s_y + 8 (2 p T + T p^2) per pass per trial
   std::vector<std::pair<hipEvent_t, hipEvent_t>> newton_ev;   // events around every inner solve (the Newton-solve kernels)
   int max_it_seen = 0;
   double n_cold = 0.0;                                          // warm starts replaced by zero (start_guard)
   double n_fb_dir = 0.0, n_fb_search = 0.0, n_fb_cap = 0.0;   // slots the shared-preconditioner phase gave up on: no descent direction, line search exhausted, outer cap
-  std::vector<double> f(c->B), qxx(c->B), qdx(c->B), qdd(c->B), dec(c->B), smax(c->B), alpha(c->B), ftry(c->B);
-  std::vector<int> its(c->B), stat(c->B), info(c->B);
-
-  for (int c0 = 0; c0 < N; c0 += c->B) {
-    const int nb = std::min(c->B, N - c0);
-    std::vector<int> tos(tr.v.begin() + c0, tr.v.begin() + c0 + nb);
-    CHK(upload_list(c, c->trial_of_slot, tos));
-    if (loo) {
-      std::vector<int> mk(loo->mask->begin() + c0, loo->mask->begin() + c0 + nb);
-      CHK(upload_list(c, c->mask_of_slot, mk));
-      c->mask_active = true;
-    }
-    HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
-    const size_t mlam = (size_t)c->q * T;
-    std::vector<double> vdelta(nb, 0.0), vdelta_prev(nb, -1.0), vdamp(nb, 1.0);
-    std::vector<int> vstat(nb, 1), vouter(nb, 0), vslow(nb, 0);
-    std::vector<int> how(nb, 0);                  // start point of a slot: 0 cold (zero), 1 the resident mode, 2 its extrapolation
-    bool any_warm = false;
-    // (error paths of the fixed point: the passes have overwritten the per-bin blocks of the chunk's trials - whatever posterior they had is gone)
-    auto var_superseded = [&]() {
-      for (int t : tos) { c->trial_dual[t] = 0; c->trial_snap[t] = -1; c->vsmgp_ok[t] = 0; c->lam_resident[t] = 0; c->lam_valid[t] = 0; }
-    };
-    if (var) {
-      // lambda of the chunk -> W = C^T diag(lambda) C (+ the reference's jitter), the covariance blocks and from them the first offsets;
-      // start point of the mode search: the variational mean of that lambda, -K C_big (lambda - y) (inference.py:194)
-      // (exp / log of the q T entries of every trial run on the device: on the host they were 1.3e8 libm calls per 256 config-5 trials - half a
-      // second each way, more than the whole fixed point)
-      if (var->start == 3) {
-        for (int s = 0; s < nb; ++s) CHK(copy_dev(c, c->lamd + (size_t)s * mlam, c->lam_keep + (size_t)tos[s] * mlam, mlam * sizeof(double)));
-      } else if (var->start != 0) {
-        CHK(upload(c, c->lamd, var->rho + (size_t)c0 * mlam, (size_t)nb * mlam));
-      }
-      int* bad_dev = reinterpret_cast<int*>(c->pcg_ratio);              // (scratch word: no inner solve is running)
-      HIPC(hipMemsetAsync(bad_dev, 0, sizeof(int), c->st));
-      if (var->start != 3) hipLaunchKernelGGL(var_exp_kernel, dim3(2048), dim3(256), 0, c->st, c->lamd, (size_t)nb * mlam, var->start == 0 ? 1 : 0, 0.5, bad_dev);
-      {
-        int bad = 0;
-        CHK(dl_enqueue(c, &bad, bad_dev, sizeof(int)));
-        CHK(dl_flush(c));
-        if (bad) return fail("rho must be finite with a positive finite exp (trials %d..%d)", tos.front(), tos.back());
-      }
-      std::vector<double> sB_, sD_, vKv_;
-      CHK(dual_common(c, nb, &sB_, &sD_, &vKv_));
-      // (only when lambda is a previous optimum: from a cold lambda that mean is far out - hundreds in the log rate - and zero is the safe start)
-      if (var->start >= 2) hipLaunchKernelGGL(negate_rows_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->KD, ld, c->Xc, ld, nvec, c->ident);
-      else HIPC(hipMemsetAsync(c->Xc, 0, (size_t)ld * nb * sizeof(double), c->st));
-      if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }
-      else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
-      CHK(var_offsets(c, nb, c->voff));
-      c->var_active = true;
-    } else {
-      // start points: cold (zero), the resident mode, or its extrapolation; warm_start = 2 takes the resident mode only
-      // for trials some earlier E-step has produced one for (minibatches revisiting trials) and starts the others cold
-      bool any = false;
-      // (the difference of the last two modes is only a prediction while the parameters keep their pace: ctx.h, extrapolate_guard)
-      const bool trend_ok = c->extrapolate && (c->extrapolate_guard <= 0.0 || (c->par_step > 0.0 && c->par_step_prev >= 0.0 &&
-                                                                                 c->par_step_prev <= c->extrapolate_guard * c->par_step));
-      for (int s = 0; s < nb && warm_start; ++s) {
-        const int tr_ = tos[s];
-        if (warm_start == 2 && c->mode_serial[tr_] < 0) continue;
-        how[s] = 1;
-        if (trend_ok && c->mode_serial[tr_] == c->estep_serial - 1 && c->prev_serial[tr_] == c->estep_serial - 2) how[s] = 2;
-        any = true;
-      }
-      any_warm = any;
-      if (any) {
-        CHK(upload_list(c, c->list_a, how));
-        hipLaunchKernelGGL(gather_start_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, c->Xprev, nvec, c->Xc, ld,
-                           c->trial_of_slot, c->list_a, c->extrapolate_beta);
-      } else {
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, nvec, c->Xc, ld, c->trial_of_slot, 1);
-      }
-    }
-    std::vector<int> active;
-    for (int vo = 0;; ++vo) {                     // (one pass for the Laplace E-step; the variational fixed point comes back here with new offsets)
-    // objective, gradient pieces and curvature blocks at the start point
-    auto eval_start = [&]() -> int {
-      CHK(prior_mv_all(c, nb, c->Xc, c->KX));
-      hipLaunchKernelGGL(dots3_kernel, dim3(nb), dim3(256), 0, c->st, c->Xc, ld, c->KX, ld, (const double*)nullptr, 0LL,
-                         (const double*)nullptr, 0LL, nvec, c->ident, c->sc_qxx, c->sc_qdx, c->sc_qdd);
-      CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
-      CHK(dl_enqueue(c, f.data(), c->sc_f, nb * sizeof(double)));
-      CHK(download(c, qxx.data(), c->sc_qxx, nb));
-      for (int s = 0; s < nb; ++s) f[s] += 0.5 * qxx[s];
-      return 0;
-    };
-    if (vo == 0 && !var && any_warm && c->start_guard) {
-      // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
-      hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
-                         c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->q, T, c->sc_alpha);
-      CHK(dl_enqueue(c, ftry.data(), c->sc_alpha, nb * sizeof(double)));
-    }
-    CHK(eval_start());
-    if (vo == 0 && !var && any_warm && c->start_guard) {
-      // A warm start that does worse than x = 0 is no start: after a jump of the parameters (another fold's fit, the generating parameters, a second
-      // fit in one process) the resident modes belong to other loadings - log rates of +-100, a curvature the single-precision copies cannot hold -
-      // and 931 of 1024 trials went through the dense per-trial retry (1.8 s where a cold E-step takes 0.12: tools/jump_probe.py).  Those slots
-      // restart at zero; the objective is strictly convex, the start point never changes the mode.
-      std::vector<int> cold;
-      for (int s = 0; s < nb; ++s)
-        if (how[s] != 0 && !(f[s] <= ftry[s])) cold.push_back(s);
-      if (!cold.empty()) {
-        CHK(upload_list(c, c->list_b, cold));
-        hipLaunchKernelGGL(zero_rows_kernel, dim3((nvec + 255) / 256, (unsigned)cold.size()), dim3(256), 0, c->st, c->Xc, ld, nvec, c->list_b);
-        CHK(eval_start());
-        n_cold += (double)cold.size();
-      }
-    }
-    active.clear();
-    for (int s = 0; s < nb; ++s) {
-      if (vo == 0) its[s] = 0;
-      if (var && vstat[s] != 1) continue;         // (this slot's fixed point is settled)
-      active.push_back(s);
-      stat[s] = 1;
-    }
-    std::vector<int> leftovers;
-    // (small chunks are launch-latency bound: there the extra packing / check launches of the host-free form cost more than
-    // the round trips they remove - measured at config 2: 8.6 vs 8.0 ms per E-step)
-    const bool thin_ok = c->thin_products && c->mfma && T >= 4 && (size_t)c->rpad <= (size_t)c->ld;
-    // (11 .. 20 latents: only the round-5 form of the host-free step exists - pcgw_*_kernel - and it needs the thin products)
-    const bool wide_ok = p <= 20 && c->pcg_form >= 2 && thin_ok && c->pcg_w32 && c->pcg_retire && c->pcg_blk != nullptr;
-    const bool fused = c->pcg_fused && c->plan_lowrank && (p <= 16 || wide_ok) && c->h_pcg != nullptr && (c->pcg_fused == 2 || (double)nb * c->n >= 1.0e6);
-    // form of the host-free iteration (pcg.h): the two-kernel step without the prior mat-vec needs the packed FP32 curvature and per-slot
-    // retirement; otherwise the split kernels of round 3
-    const bool onek = fused && c->pcg_w32 && c->pcg_retire && c->pcg_form != 0 && (p <= 10 || wide_ok);
-    // round 5 (pcg_form = 2): the solve's private vectors on line-aligned latent rows, ONE start kernel (gradient, residual, zero step, first
-    // per-bin application), the step's closing inside kernel A, ONE upload (control block, list, forcing terms); needs the thin products
-    const bool f2 = onek && c->pcg_form >= 2 && thin_ok && c->pcg_blk != nullptr;
-    const int TB = p <= 10 ? 64 : PCGW_TB;               // bins per workgroup tile of the step's per-bin kernels
-    // ... and (second half of round 5) z, s, p, q, t / y of the solve stored in single precision (PcgCgP::vec32)
-    const bool v32 = f2 && c->pcg_vec32;
-    const int Tl = !f2 ? T : (v32 && (long long)p * round_up(T, 32) <= ld) ? round_up(T, 32) : ((long long)p * round_up(T, 16) <= ld) ? round_up(T, 16) : T;
-    // ... and (round 6) the residual and the step as well, up to 10 latents (PcgCgP::X32): x in the free second half of Z's buffer
-    const bool rx32 = v32 && c->pcg_rx32 && p <= 10;
-    auto with_tv = [&](auto&& fn) { if (rx32) fn(float{}, float{}); else if (v32) fn(float{}, double{}); else fn(double{}, double{}); };
-    // packed single-precision curvature of the two-kernel step (pcg.h): component-major [c][Tw], rows on 128-byte lines.  It is written where W is:
-    // by pack_w32t_kernel at the start of a solve for slots whose W came from the Poisson pass at the E-step's start point, and by the commit of an
-    // accepted step (commit_w_pack_kernel: the copy W <- Wt and the packing in one pass over Wt - a solve after the first finds every active slot packed)
-    const int npk = p * (p + 1) / 2;
-    const int Tw = round_up(T, 32);
-    const long long sW32 = (long long)Tw * npk;
-    std::vector<char> w32_ok(nb, 0);
-
-    // backtracking line search along Dl for the slots in `cand` (objective with rounding-noise slack as in
-    // the oracle); needs dec/qxx/qdx/qdd of those slots on the host.  Accepted slots are committed
-    // (X, K^-1 x, likelihood gradient, W); returns the slots whose search was exhausted.
-    auto line_search = [&](const std::vector<int>& cand, std::vector<int>* failed) -> int {
-      std::vector<int> pending;
-      for (int s : cand) { alpha[s] = 1.0; pending.push_back(s); }
-      for (int ls = 0; ls < 40 && !pending.empty(); ++ls) {
-        const int np_ = (int)pending.size();
-        CHK(upload_nosync(c, c->list_b, pending.data(), sizeof(int) * pending.size()));
-        CHK(upload_nosync(c, c->sc_alpha, alpha.data(), sizeof(double) * nb));
-        hipLaunchKernelGGL(make_try_kernel, dim3((nvec + 255) / 256, np_), dim3(256), 0, c->st, c->Xc, ld, c->Dl, ld, c->sc_alpha, c->Xt, ld, nvec,
-                           c->list_b);
-        CHK(poisson(c, c->list_b, np_, c->Xt, c->Glt, c->Wt, c->sc_f, 1));
-        CHK(download(c, ftry.data(), c->sc_f, nb));
-        std::vector<int> acc, rej;
-        for (int s : pending) {
-          const double a = alpha[s];
-          const double ft = ftry[s] + 0.5 * (qxx[s] + 2.0 * a * qdx[s] + a * a * qdd[s]);
-          const double slack = 1e-12 * (1.0 + std::fabs(f[s]));
-          if (std::isfinite(ft) && ft <= f[s] - 1e-4 * a * dec[s] + slack) {
-            f[s] = ft;
-            acc.push_back(s);
-          } else {
-            alpha[s] = 0.5 * a;
-            rej.push_back(s);
-          }
-        }
-        if (!acc.empty()) {
-          const int nacc = (int)acc.size();
-          CHK(upload_nosync(c, c->list_b, acc.data(), sizeof(int) * acc.size()));
-          const int nw = T * p * p;
-          hipLaunchKernelGGL(commit_kernel, dim3((nvec + 255) / 256, nacc), dim3(256), 0, c->st, c->Xc, c->Xt, c->KX, c->KD, c->Gl, c->Glt, ld,
-                             c->W, c->Wt, (long long)nw, c->sc_alpha, nvec, onek ? 0 : nw, c->list_b);
-          if (onek) {
-            hipLaunchKernelGGL(commit_w_pack_kernel, dim3((T + 63) / 64, nacc), dim3(256), (size_t)npk * 65 * sizeof(float), c->st, (const double*)c->Wt, c->W,
-                               (long long)nw, c->W32, sW32, Tw, T, p, c->list_b);
-            for (int s : acc) w32_ok[s] = 1;
-          }
-          HIPC(hipGetLastError());
-        }
-        pending.swap(rej);
-      }
-      *failed = pending;
-      return 0;
-    };
-
-    // ---- phase 1: inexact Newton, all slots in lockstep, PCG on H_r delta = -g preconditioned by ONE shared factor
-    // (the mean-trial Hessian: cond(P^-1 H_r) stays below ~4, measured).  Every preconditioner application is two
-    // multi-RHS triangular sweeps run as GEMMs over the slots; no per-trial factorisation in this phase.
-    if (c->shared_pcg && (nb >= c->shared_min || c->plan_lowrank)) {
-      PhaseRange range_newton("pgpfa.newton_pcg");
-      CHK(shared_factor(c, nb));
-      n_shared += 1;
-      std::vector<double> rr(nb), rr0(nb), err_pred(nb, -1.0);
-      for (int outer = 0; outer < c->pcg_outer_max && !active.empty(); ++outer) {
-        // forcing term of this outer iteration (relative residual the inner solve is run to).  With e the predicted
-        // error of a slot's current iterate, solving beyond eta ~ e buys nothing (the Newton step itself leaves ~e^2),
-        // and when a looser solve already lands below the stopping tolerance that looser value is enough.
-        double eta_target = c->pcg_eta0;
-        for (int s : active) {
-          if (err_pred[s] < 0.0) continue;                       // first outer iteration of this slot
-          const double e = std::max(err_pred[s], 1e-300);
-          const double want = std::max(e, c->chord_xtol / (20.0 * e));
-          eta_target = std::min(eta_target, std::max(1e-9, std::min(c->pcg_eta0, want)));
-        }
-        const int na = (int)active.size();
-        int done_inner = 0;
-        PcgCtl& fused_ctl = c->fused_ctl_host;             // (context member: a queued read-back must not point into this frame)
-        fused_ctl = PcgCtl{};
-        if (!f2) CHK(upload_nosync(c, c->list_a, active.data(), sizeof(int) * active.size()));
-        if (c->time_newton) {
-          newton_ev.emplace_back(prof_event(c->prof), prof_event(c->prof));
-          hipEventRecord(newton_ev.back().first, c->st);
-        }
-        if (!f2) {
-          hipLaunchKernelGGL(grad_total_kernel, dim3((nvec + 255) / 256, na), dim3(256), 0, c->st, c->Gl, ld, c->KX, ld, c->Gt, ld, nvec, c->list_a);
-          hipLaunchKernelGGL(pcg_init_kernel, dim3((c->npad + 255) / 256, na), dim3(256), 0, c->st, c->Gt, c->Rv, c->Dl, ld, nvec, c->npad, c->list_a);
-        }
-        if (onek) {
-          // ---- inner solve: per step pcg_cg_a_kernel, pcg_cg_b_kernel, the closing kernel and the three preconditioner products (pcg.h)
-          const int* skip = &c->pcgctl->stop;
-          {
-            std::vector<float> eta_s(nb, (float)eta_target);
-            for (int s : active) {
-              double es = c->pcg_eta0;
-              if (err_pred[s] >= 0.0) {
-                const double e = std::max(err_pred[s], 1e-300);
-                es = std::max(1e-9, std::min(c->pcg_eta0, std::max(e, c->chord_xtol / (20.0 * e))));
-              }
-              eta_s[s] = (float)es;
-            }
-            PcgCtl h0{};
-            h0.nlive = na; h0.nl[0] = na;
-            if (f2) {
-              // one upload: [control block (16 words) | list_a | first live list | forcing terms] - consecutive pieces of c->pcg_blk
-              const size_t nB = (size_t)c->B;
-              std::vector<int> img(16 + 3 * nB, 0);
-              std::memcpy(img.data(), &h0, sizeof(PcgCtl));
-              std::memcpy(img.data() + 16, active.data(), sizeof(int) * na);
-              std::memcpy(img.data() + 16 + nB, active.data(), sizeof(int) * na);
-              std::memcpy(img.data() + 16 + 2 * nB, eta_s.data(), sizeof(float) * nb);
-              CHK(upload_nosync(c, c->pcg_blk, img.data(), img.size() * sizeof(int)));
-            } else {
-              CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
-              CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
-              CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
-            }
-          }
-          c->h_pcg[0] = 0; c->h_pcg[1] = 0; c->h_pcg[2] = na;
-          PcgCgP cp{};
-          cp.GbT = c->GbT; cp.WbT = reinterpret_cast<const float*>(c->WbT); cp.W32T = c->W32; cp.sW32 = sW32; cp.Tw = Tw;
-          cp.X = c->Dl; cp.R = c->Rv; cp.P = c->Pv; cp.Q = c->Qv; cp.Z = c->Zv; cp.S = c->Sv; cp.Y = c->Xt; cp.sV = ld;
-          cp.part = c->sc_part2; cp.gam = c->cg_scal; cp.alp = c->cg_scal + 2 * (size_t)c->B; cp.rr = c->sc_rr; cp.rr0 = c->sc_rr0; cp.eta = c->pcg_eta;
-          cp.ctl = c->pcgctl; cp.live0 = c->live; cp.live1 = c->live1;
-          cp.eps = c->eps; cp.T = T; cp.p = p; cp.inner_min = c->pcg_inner_min; cp.ntile = (T + TB - 1) / TB; cp.B = c->B; cp.xcd_map = c->pcg_xcd;
-          cp.X32 = reinterpret_cast<float*>(c->Zv) + (size_t)ld * ((size_t)c->B + 128);     // (the single-precision z fills the first half of Zv)
-          cp.Tl = Tl; cp.Tx = T; cp.vec32 = v32 ? 1 : 0; cp.fold_close = f2 ? 1 : 0; cp.host = (volatile int*)c->d_hpcg; cp.Gl = c->Gl; cp.KX = c->KX; cp.Gt = c->Gt;
-          auto cg_grid = [&](int bound) {
-            cp.spw = !c->pcg_adapt ? PCG_SLOTS : bound > 640 ? 16 : bound > 320 ? 8 : 4;
-            if (TB != 64) cp.spw = std::max(cp.spw, PCGW_SL);                                     // (a 32-bin workgroup has 8 slots in flight)
-            return dim3((T + TB - 1) / TB, round_up((bound + cp.spw - 1) / cp.spw, 8));           // (slot groups in blocks of 8: pcg_cg_wg)
-          };
-          if (f2) {
-            const dim3 g0 = cg_grid(na);
-            dispatch_pw(p, [&](auto pw) {
-              constexpr int PW = decltype(pw)::value;
-              if constexpr (PW <= 10) {
-                const size_t lb = pcg_cg_b_lds(PW);
-                with_tv([&](auto tv, auto tx) {
-                  using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
-                  if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_start_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                  hipLaunchKernelGGL((pcg_cg_start_kernel<PW, TV, TX>), g0, dim3(256), lb, c->st, cp);
-                });
-              } else if constexpr (PW <= 20) {
-                const size_t lb = pcgw_b_lds(PW);
-                with_tv([&](auto tv, auto tx) {
-                  using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
-                  if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_start_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                  hipLaunchKernelGGL((pcgw_start_kernel<PW, TV>), g0, dim3(256), lb, c->st, cp);
-                });
-              }
-            });
-          }
-          {
-            std::vector<int> need;
-            for (int s : active) if (!w32_ok[s]) { need.push_back(s); w32_ok[s] = 1; }
-            if (!need.empty()) {
-              CHK(upload_nosync(c, c->list_b, need.data(), sizeof(int) * need.size()));
-              hipLaunchKernelGGL(pack_w32t_kernel, dim3((T + 63) / 64, (unsigned)need.size()), dim3(256), (size_t)npk * 65 * sizeof(float), c->st, c->W,
-                                 (long long)T * p * p, c->W32, sW32, Tw, T, p, c->list_b);
-            }
-          }
-          // t = Gb r0 (the start kernel has it already), then y = F Sb F^T t over the listed columns (left in c->Xt)
-          CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, !f2, false, c->list_a, na, f2 ? Tl : 0, v32));
-          struct NdevGuard { pgpfa_ctx* c; ~NdevGuard() { c->cur_ndev = nullptr; } } ndev_guard{c};
-          c->live_gemms.clear();
-          int last_step = -1;
-          for (int it = 0; it < c->pcg_inner_max; ++it) {
-            cp.par = it & 1; cp.first = (it == 0) ? 1 : 0; cp.step = it; last_step = it;
-            // The launches of a step are sized by the live count the closing kernel last mirrored to the host (it only falls during a solve, so a
-            // value that is a step or two old is an upper bound; the kernels read the true count on the device).  Few live slots: fewer slots per
-            // workgroup, so that the per-bin kernels still offer every CU a workgroup and a wave walks one slot instead of four in a row.
-            const int seen = *(volatile int*)&c->h_pcg[2];
-            const int bound = c->pcg_adapt ? std::max(1, std::min(na, seen)) : na;
-            const dim3 gcg = cg_grid(bound);
-            dispatch_pw(p, [&](auto pw) {
-              constexpr int PW = decltype(pw)::value;
-              if constexpr (PW <= 10) {
-                const size_t la = pcg_cg_a_lds(PW), lb = pcg_cg_b_lds(PW);
-                // (per launch, not once per process: contexts of one process may sit on different devices)
-                with_tv([&](auto tv, auto tx) {
-                  using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
-                  if (la > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_a_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)la);
-                  if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_b_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                  hipLaunchKernelGGL((pcg_cg_a_kernel<PW, TV, TX>), gcg, dim3(256), la, c->st, cp);
-                  hipLaunchKernelGGL((pcg_cg_b_kernel<PW, TV, TX>), gcg, dim3(256), lb, c->st, cp);
-                });
-              } else if constexpr (PW <= 20) {
-                const size_t la = pcgw_a_lds(PW), lb = pcgw_b_lds(PW);
-                with_tv([&](auto tv, auto tx) {
-                  using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
-                  if (la > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_a_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)la);
-                  if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_b_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                  hipLaunchKernelGGL((pcgw_a_kernel<PW, TV>), gcg, dim3(256), la, c->st, cp);
-                  hipLaunchKernelGGL((pcgw_b_kernel<PW, TV>), gcg, dim3(256), lb, c->st, cp);
-                });
-              }
-            });
-            if (!f2) hipLaunchKernelGGL(pcg_iter_close_kernel, dim3(1), dim3(64), 0, c->st, c->pcgctl, it & 1, (volatile int*)c->d_hpcg, -1);
-            // the preconditioner products for the NEXT iteration run over the list this launch has just written
-            c->live_gemm_collect = (it == 0);
-            c->cur_ndev = &c->pcgctl->nl[(it & 1) ^ 1];
-            CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, (it & 1) ? c->live : c->live1, bound, f2 ? Tl : 0, v32));
-            if (*(volatile int*)&c->h_pcg[0]) break;           // the device has already stopped: whatever is enqueued is a no-op
-            if (it + 1 < c->pcg_inner_max) {
-              const auto t_spin = std::chrono::steady_clock::now();
-              while (!*(volatile int*)&c->h_pcg[0] && (it + 1) - *(volatile int*)&c->h_pcg[1] > 2) {
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 5.0) break;   // (never hang on a lost flag)
-              }
-              if (*(volatile int*)&c->h_pcg[0]) break;
-            }
-          }
-          // (pcg_form 2: kernel A of step i + 1 closes step i; the last step enqueued is closed here unless the solve had stopped before it)
-          if (f2 && last_step >= 0) hipLaunchKernelGGL(pcg_iter_close_kernel, dim3(1), dim3(64), 0, c->st, c->pcgctl, last_step & 1, (volatile int*)c->d_hpcg, last_step);
-          c->cur_ndev = nullptr;
-          c->live_gemm_collect = false;
-          CHK(dl_enqueue(c, &fused_ctl, c->pcgctl, sizeof(PcgCtl)));
-          HIPC(hipGetLastError());
-          done_inner = -1;
-        } else if (fused) {
-          // ---- inner solve without host round trips (pcg.h): the stopping test runs on the device, iterations are enqueued
-          // ahead, kernels of iterations past the stop return at once
-          const int ntile = (T + 63) / 64;
-          const int* skip = &c->pcgctl->stop;
-          const long long sW32 = (long long)T * (p * (p + 1) / 2);
-          // the live list starts as the active list; every slot carries its own forcing term (with pcg_retire = 0: the common one)
-          {
-            std::vector<float> eta_s(nb, (float)eta_target);
-            if (c->pcg_retire)
-              for (int s : active) {
-                double es = c->pcg_eta0;
-                if (err_pred[s] >= 0.0) {
-                  const double e = std::max(err_pred[s], 1e-300);
-                  es = std::max(1e-9, std::min(c->pcg_eta0, std::max(e, c->chord_xtol / (20.0 * e))));
-                }
-                eta_s[s] = (float)es;
-              }
-            CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
-            CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
-            PcgCtl h0{};
-            h0.nlive = na;
-            CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
-          }
-          c->h_pcg[0] = 0; c->h_pcg[1] = 0;
-          if (c->pcg_w32)
-            hipLaunchKernelGGL(pack_w32_kernel, dim3((unsigned)((sW32 + 255) / 256), na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->W32,
-                               sW32, T, p, c->list_a);
-          const dim3 gbin(ntile, (na + PCG_SLOTS - 1) / PCG_SLOTS);
-          // z0 = P^-1 r0, p0 = z0
-          CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, false, c->list_a, na));
-          dispatch_pw(p, [&](auto pw) {
-            constexpr int PW = decltype(pw)::value;
-            if constexpr (PW <= 16)
-              hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->list_a, na,
-                                 c->sc_part2, (const int*)nullptr, (const PcgCtl*)nullptr);
-          });
-          hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_part2, ntile, c->sc_rz,
-                             c->sc_rr, c->sc_rr0, 1, (PcgCtl*)nullptr, (float*)nullptr);
-          c->cur_ndev = &c->pcgctl->nlive;
-          struct NdevGuard { pgpfa_ctx* c; ~NdevGuard() { c->cur_ndev = nullptr; } } ndev_guard{c};
-          c->live_gemms.clear();
-          for (int it = 0; it < c->pcg_inner_max; ++it) {
-            c->live_gemm_collect = (it == 0);
-            CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, skip, c->live, na));
-            dispatch_pw(p, [&](auto pw) {
-              constexpr int PW = decltype(pw)::value;
-              if constexpr (PW <= 16) {
-                if (c->pcg_w32)
-                  hipLaunchKernelGGL(pcg_hessvec32_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W32, sW32, c->Pv, c->Qv, ld, T, p,
-                                     c->live, c->sc_pq, skip, (const PcgCtl*)c->pcgctl);
-                else
-                  hipLaunchKernelGGL(pcg_hessvec_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv, c->Qv,
-                                     ld, T, p, c->live, c->sc_pq, (const int*)&c->pcgctl->nlive);
-                hipLaunchKernelGGL(pcg_xr_apply_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Dl, c->Rv, c->Pv, c->Qv, c->Xt, ld, T, p,
-                                   c->live, na, c->sc_rz, c->sc_pq, ntile, skip, (const PcgCtl*)c->pcgctl);
-              }
-            });
-            CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, c->live, na));
-            dispatch_pw(p, [&](auto pw) {
-              constexpr int PW = decltype(pw)::value;
-              if constexpr (PW <= 16)
-                hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->live,
-                                   na, c->sc_part2, skip, (const PcgCtl*)c->pcgctl);
-            });
-            hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->live, c->sc_part2, ntile,
-                               c->sc_rz, c->sc_rr, c->sc_rr0, 0, c->pcgctl, c->pcg_ratio);
-            hipLaunchKernelGGL(pcg_check_kernel, dim3(1), dim3(256), 0, c->st, c->pcgctl, (volatile int*)c->d_hpcg, c->live,
-                               (const float*)c->pcg_ratio, (const float*)c->pcg_eta, c->pcg_inner_min);
-            if (*(volatile int*)&c->h_pcg[0]) break;           // the device has already stopped: whatever is enqueued is a no-op
-            // stay at most 3 iterations ahead of the device (an iteration enqueued past the stop costs ~13 empty launches: that
-            // matters when the kernels themselves take microseconds); the wait spins on the host-mapped counter, no API call
-            if (it + 1 < c->pcg_inner_max) {
-              const auto t_spin = std::chrono::steady_clock::now();
-              while (!*(volatile int*)&c->h_pcg[0] && (it + 1) - *(volatile int*)&c->h_pcg[1] > 3) {
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 5.0) break;   // (never hang on a lost flag)
-              }
-              if (*(volatile int*)&c->h_pcg[0]) break;
-            }
-          }
-          c->cur_ndev = nullptr;
-          c->live_gemm_collect = false;
-          CHK(dl_enqueue(c, &fused_ctl, c->pcgctl, sizeof(PcgCtl)));
-          HIPC(hipGetLastError());
-          done_inner = -1;                                     // read from the control block with the scalars below
-        } else {
-        CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, true, c->list_a, na));
-        hipLaunchKernelGGL(pcg_update_p_kernel, dim3(na), dim3(256), 0, c->st, c->Rv, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_rz, c->sc_rr0, 1);
-        for (int it = 0; it < c->pcg_inner_max; ++it) {
-          CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, nullptr, c->list_a, na));
-          int pq_tiles = 1;
-          dispatch_pw(p, [&](auto pw) {
-            constexpr int PW = decltype(pw)::value;
-            if constexpr (PW <= 16) {
-              pq_tiles = (T + 63) / 64;
-              hipLaunchKernelGGL(pcg_hessvec_dot_kernel<PW>, dim3(pq_tiles, na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv,
-                                 c->Qv, ld, T, p, c->list_a, c->sc_pq);
-            } else {
-              hipLaunchKernelGGL(pcg_hessvec_dot_wide_kernel<PW>, dim3(na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv, c->Qv, ld,
-                                 T, p, c->list_a, c->sc_pq);
-            }
-          });
-          hipLaunchKernelGGL(pcg_update_xr_kernel, dim3(na), dim3(256), 0, c->st, c->Dl, c->Rv, c->Pv, c->Qv, ld, nvec, c->list_a, c->sc_rz, c->sc_pq,
-                             pq_tiles);
-          CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, true, c->list_a, na));
-          hipLaunchKernelGGL(pcg_update_p_kernel, dim3(na), dim3(256), 0, c->st, c->Rv, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_rz, c->sc_rr, 0);
-          done_inner = it + 1;
-          if (done_inner >= c->pcg_inner_min) {
-            CHK(download(c, rr.data(), c->sc_rr, nb));
-            if (it == c->pcg_inner_min - 1) CHK(download(c, rr0.data(), c->sc_rr0, nb));
-            double worst = 0.0;
-            for (int s : active) worst = std::max(worst, rr0[s] > 0.0 ? std::sqrt(rr[s] / rr0[s]) : 0.0);
-            if (worst <= eta_target) break;
-          }
-        }
-        }
-        if (onek && rx32) {
-          // the step comes back in single precision on the solve's private rows: widened into Dl by the kernel that reads it first (inside the timed
-          // region of the solve: it is part of what the single-precision step costs)
-          hipLaunchKernelGGL(step_stats_x32_kernel, dim3(na), dim3(256), 0, c->st, c->Gt, reinterpret_cast<const float*>(c->Zv) + (size_t)ld * ((size_t)c->B + 128),
-                             c->Dl, ld, T, Tl, p, c->list_a, c->sc_dec, c->sc_smax);
-          if (c->time_newton) hipEventRecord(newton_ev.back().second, c->st);
-        } else {
-          if (c->time_newton) hipEventRecord(newton_ev.back().second, c->st);
-          hipLaunchKernelGGL(step_stats_kernel, dim3(na), dim3(256), 0, c->st, c->Gt, c->Dl, ld, nvec, c->list_a, c->sc_dec, c->sc_smax);
-        }
-        CHK(prior_mv_all(c, nb, c->Dl, c->KD));
-        hipLaunchKernelGGL(dots3_kernel, dim3(na), dim3(256), 0, c->st, c->Xc, ld, c->KX, ld, c->Dl, ld, c->KD, ld, nvec, c->list_a, c->sc_qxx,
-                           c->sc_qdx, c->sc_qdd);
-        HIPC(hipGetLastError());
-        {
-          const size_t nB = (size_t)c->B;
-          std::vector<double> pack(7 * nB);
-          CHK(download(c, pack.data(), c->sc_pack, 7 * nB));
-          std::copy(pack.begin(), pack.begin() + nb, dec.begin());
-          std::copy(pack.begin() + nB, pack.begin() + nB + nb, smax.begin());
-          std::copy(pack.begin() + 2 * nB, pack.begin() + 2 * nB + nb, qxx.begin());
-          std::copy(pack.begin() + 3 * nB, pack.begin() + 3 * nB + nb, qdx.begin());
-          std::copy(pack.begin() + 4 * nB, pack.begin() + 4 * nB + nb, qdd.begin());
-          std::copy(pack.begin() + 5 * nB, pack.begin() + 5 * nB + nb, rr.begin());
-          std::copy(pack.begin() + 6 * nB, pack.begin() + 6 * nB + nb, rr0.begin());
-        }
-        double slot_iters = (double)na * done_inner;
-        if (done_inner < 0) {                                   // (the download above synchronised the stream)
-          done_inner = fused_ctl.iters;
-          slot_iters = (double)fused_ctl.slot_iters;
-          if (c->prof.on)                                       // algorithmic flops of the live-list products: per column x slot-iterations
-            for (const auto& lg : c->live_gemms) {
-              c->prof.flops[TAG_GEMM] += lg.second * slot_iters;
-              c->prof.shapes[lg.first].flops += lg.second * slot_iters;
-            }
-        }
-        n_pcg += slot_iters;
-        if (c->pcg_trace) {
-          // achieved residual ratios of the live slots: worst, median, and how many already met the target
-          std::vector<double> ratio;
-          for (int s : active) ratio.push_back(rr0[s] > 0.0 ? std::sqrt(rr[s] / rr0[s]) : 0.0);
-          std::sort(ratio.begin(), ratio.end());
-          int met = 0;
-          for (double v : ratio) met += (v <= eta_target) ? 1 : 0;
-          std::fprintf(stderr, "pcg_trace: outer %d live %d inner %d eta_target %.2e achieved worst %.2e median %.2e best %.2e met %d\n", outer, na, done_inner,
-                       eta_target, ratio.back(), ratio[ratio.size() / 2], ratio.front(), met);
-        }
-        {
-          // mandatory HBM traffic of one PCG iteration (the bytes a perfect implementation still moves): per live slot
-          // 20 passes over an n-vector (H p = K^-1 p + W p: 5; x, r updates: 6; preconditioner G(eps r + F S F^T G r): 6; p = z + beta p: 3),
-          // 4 over an r-vector, the curvature blocks (packed FP32 lower triangles, or FP64 full blocks); once per iteration the operators
-          // K^-1 (p T^2), F and F^T (T r each) and S (r^2).  Dense plan: P^-1 (n^2) instead of F / S.
-          const double npk = (double)(p * (p + 1) / 2);
-          // Two-kernel step (pcg_cg_a/b_kernel): 17 passes (A reads r, y and writes z, s; B reads z, s, p, q, x, r and writes p, q, x, r, t; the
-          // products read t and write y), 4 over an r-vector, the packed FP32 curvature; once per step F, F^T, S and the packed triangles of Gb
-          // (FP64) and Wb (FP32).  No K^-1 in the loop.
-          const double vecs = (onek ? 17.0 : 20.0) * nvec * 8.0 + (c->plan_lowrank ? 4.0 * c->rtot * 8.0 : 0.0);
-          const double curv = (fused && c->pcg_w32) ? (double)T * npk * 4.0 : (double)T * p * p * 8.0;
-          const double ops = onek ? (2.0 * T * c->rtot + (double)c->rtot * c->rtot + 1.5 * T * npk) * 8.0
-                                  : (double)p * T * T * 8.0 + (c->plan_lowrank ? (2.0 * T * c->rtot + (double)c->rtot * c->rtot) * 8.0 : (double)nvec * nvec * 8.0);
-          newton_bytes += slot_iters * (vecs + curv) + (double)done_inner * ops;
-          // (bytes per entry of an n-vector and slot-step: FP64 form 136 = 17 passes; z, s, p, q, t / y in single precision 88; r and x too 68 -
-          //  A reads r 4, y 4, writes z 4, s 4; B reads z 4, s 4, x 4, r 4, p 4, q 4, writes p 4, q 4, x 4, r 4, t 4; the products read t 4, write y 4 -
-          //  plus, once per solve and slot, the widening of the step: 4 read, 8 written)
-          const double vec_b = rx32 ? 68.0 : (v32 ? 88.0 : 0.0);
-          newton_bytes_moved += slot_iters * ((v32 ? vec_b * nvec + (c->plan_lowrank ? 4.0 * c->rtot * 8.0 : 0.0) : vecs) + curv) + (double)done_inner * ops
-                                + ((onek && rx32) ? 12.0 * nvec * (double)na : 0.0);
-          newton_bytes_survey += slot_iters * ((double)c->q * T + 8.0 * (2.0 * p * T + (double)T * p * p));
-        }
-        std::vector<int> cand, next, failed;
-        for (int s : active) {
-          if (!(dec[s] > 0.0) || !std::isfinite(dec[s]) || !std::isfinite(smax[s])) continue;   // leave to the fallback
-          cand.push_back(s);
-        }
-        CHK(line_search(cand, &failed));
-        std::vector<char> bad(nb, 0);
-        for (int s : failed) bad[s] = 1;
-        std::vector<double> gnew;
-        if (onek) {
-          // The inner solve ran on H~ = Kt^-1 + fl32(W): its residual says how well H~ delta = -g was solved, not how far the step took the
-          // TRUE gradient down.  Measure that: |g(x + delta)| / |g(x)| of the accepted full steps (the committed Gl + KX; rr0 = |g(x)|^2) enters
-          // the error prediction next to the inner ratio, so the stopping rule never rests on the model matrix.
-          std::vector<int> okl;
-          for (int s : cand) if (!bad[s]) okl.push_back(s);
-          gnew.assign(nb, 0.0);
-          if (!okl.empty()) {
-            CHK(upload_nosync(c, c->list_b, okl.data(), sizeof(int) * okl.size()));
-            hipLaunchKernelGGL(grad_norm2_kernel, dim3((unsigned)okl.size()), dim3(256), 0, c->st, c->Gl, c->KX, ld, nvec, c->list_b, c->sc_f);
-            CHK(download(c, gnew.data(), c->sc_f, nb));
-          }
-        }
-        for (int s : cand) {
-          if (bad[s]) continue;
-          // inexact Newton: the error after the step is ~ max(eta, |step|) * |step|, eta = achieved relative residual
-          double eta = rr0[s] > 0.0 ? std::sqrt(rr[s] / rr0[s]) : 0.0;
-          if (onek && alpha[s] == 1.0 && rr0[s] > 0.0) eta = std::max(eta, std::sqrt(gnew[s] / rr0[s]));
-          const double step = alpha[s] * smax[s];
-          if (alpha[s] == 1.0 && 10.0 * step * std::max(eta, step) < c->chord_xtol) { stat[s] = 0; continue; }
-          err_pred[s] = (alpha[s] == 1.0) ? step * std::max(eta, step) : step;
-          next.push_back(s);
-        }
-        // slots with a non-descent direction or an exhausted search drop to the per-trial fallback below
-        std::vector<int> fallback;
-        {
-          std::vector<char> in_cand(nb, 0);
-          for (int s : cand) in_cand[s] = 1;
-          for (int s : active) if (!in_cand[s] || bad[s]) { fallback.push_back(s); if (bad[s]) n_fb_search += 1; else n_fb_dir += 1; }
-        }
-        active.swap(next);
-        leftovers.insert(leftovers.end(), fallback.begin(), fallback.end());
-        max_it_seen = std::max(max_it_seen, outer + 1);
-      }
-      // anything still active after the outer cap also goes to the fallback
-      n_fb_cap += (double)active.size();
-      leftovers.insert(leftovers.end(), active.begin(), active.end());
-      active = leftovers;
-      std::sort(active.begin(), active.end());
-    }
-
-    // ---- phase 1b (fallback, and the only path when shared_pcg is off or the chunk is tiny): per-trial Newton with
-    // factor reuse.  A slot factors H at its current point only when it has no factor yet or its chord steps (steps
-    // with the stale factor, still descent directions since that factor is SPD) contract too slowly; otherwise the
-    // resident factor is reused: one HBM-bound solve instead of n^3/3 flops.
-    if (c->plan_lowrank && !active.empty()) {
-      // the per-trial fallback needs full-size factor slabs: leave these trials to the dense retry pass of the caller
-      for (int s : active) stat[s] = 4;
-      active.clear();
-    }
-    std::vector<char> has_factor(nb, 0), fresh(nb, 0), refactor(nb, 0);
-    std::vector<double> prev_step(nb, 0.0);
-    std::vector<int> n_chord(nb, 0);
-    for (int iter = 0; iter < c->max_iter && !active.empty(); ++iter) {
-      const int na = (int)active.size();
-      std::vector<int> need;
-      for (int s : active) {
-        if (!has_factor[s] || refactor[s] || !c->chord) need.push_back(s);
-        fresh[s] = 0;
-      }
-      if (!need.empty()) {
-        CHK(upload_list(c, c->list_a, need));
-        CHK(assemble(c, c->list_a, (int)need.size()));
-        CHK(factor(c, c->ws, c->list_a, (int)need.size()));
-        n_fact += (double)need.size();
-        for (int s : need) { has_factor[s] = 1; fresh[s] = 1; refactor[s] = 0; n_chord[s] = 0; its[s] += 1; }
-      }
-      n_solve += na;
-      CHK(upload_list(c, c->list_a, active));
-      hipLaunchKernelGGL(grad_total_kernel, dim3((nvec + 255) / 256, na), dim3(256), 0, c->st, c->Gl, ld, c->KX, ld, c->Gt, ld, nvec, c->list_a);
-      prof_begin(c, TAG_SOLVE, 2.0 * na * (double)c->npad * c->npad);
-      hipLaunchKernelGGL(chol_solve_kernel, dim3(na), dim3(256), 0, c->st, c->ws.H, c->ws.sH, c->ld, c->npad, c->ws.Dinv, c->ws.sD, c->Gt, c->Dl,
-                         ld, c->list_a, c->sc_dec, c->sc_smax, nvec);
-      prof_end(c);
-      CHK(prior_mv(c, c->list_a, na, c->Dl, c->KD));
-      hipLaunchKernelGGL(dots3_kernel, dim3(na), dim3(256), 0, c->st, c->Xc, ld, c->KX, ld, c->Dl, ld, c->KD, ld, nvec, c->list_a, c->sc_qxx,
-                         c->sc_qdx, c->sc_qdd);
-      HIPC(hipGetLastError());
-      CHK(download(c, dec.data(), c->sc_dec, nb));
-      CHK(download(c, smax.data(), c->sc_smax, nb));
-      CHK(download(c, qxx.data(), c->sc_qxx, nb));
-      CHK(download(c, qdx.data(), c->sc_qdx, nb));
-      CHK(download(c, qdd.data(), c->sc_qdd, nb));
-      CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
-      CHK(dl_flush(c));
-
-      std::vector<int> cand, failed;
-      for (int s : active) {
-        if (info[s] != 0 || !std::isfinite(dec[s])) { stat[s] = 3; continue; }
-        cand.push_back(s);
-      }
-      CHK(line_search(cand, &failed));
-      for (int s : failed) stat[s] = 2;   // line search exhausted
-      std::vector<int> next;
-      for (int s : active) {
-        if (stat[s] == 2 || stat[s] == 3) continue;
-        const double step = alpha[s] * smax[s];
-        if (fresh[s]) {
-          // true Newton step: quadratic convergence, the error after the step is ~step^2
-          if (step < c->xtol) { stat[s] = 0; continue; }
-          if (step > c->chord_max_step) refactor[s] = 1;      // still far from the mode: keep factoring
-        } else {
-          // chord step: linear convergence with ratio rho, the error after the step is ~rho/(1-rho)*step
-          const double rho = prev_step[s] > 0.0 ? step / prev_step[s] : 1.0;
-          n_chord[s] += 1;
-          if (step < c->chord_xtol && rho < 0.5) { stat[s] = 0; continue; }
-          if (rho > c->chord_rho || n_chord[s] >= c->chord_max) refactor[s] = 1;
-        }
-        prev_step[s] = step;
-        next.push_back(s);
-      }
-      active.swap(next);
-      max_it_seen = std::max(max_it_seen, iter + 1);
-    }
-
-    if (!var) break;
-    // ---- variational fixed point: rates at the modes, their covariance blocks, new offsets
-    // A mode search that did not settle (iteration cap 1, line search exhausted 2, factor failure 3 / 4) hands ITS trial back - status 2: the
-    // caller finishes it with L-BFGS from the lambda of the point the search reached - and the other slots go on.  Only a non-finite state
-    // (checked below on the offsets of every slot still open or handed back in this pass) fails the call.
-    std::vector<char> handed(nb, 0);
-    for (int s = 0; s < nb; ++s)
-      if (vstat[s] == 1 && stat[s] != 0) { vstat[s] = 2; handed[s] = 1; vouter[s] = vo + 1; }
-    c->lam_out_active = true;
-    CHK(poisson(c, c->ident, nb, c->Xc, c->Glt, c->Wt, c->sc_f, 0));        // lambda = exp(C m + d + offset) -> c->lamd
-    c->lam_out_active = false;
-    if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }   // (c->W: curvature at the modes = C^T diag(lambda) C)
-    else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
-    CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
-    CHK(dl_flush(c));
-    for (int s = 0; s < nb; ++s)
-      if (info[s] != 0) { var_superseded(); return fail("variational fixed point: posterior precision of trial %d not positive definite", tos[s]); }
-    CHK(var_offsets(c, nb, c->dgrad));
-    {
-      // change of the offsets first (step 0: nothing moves), the update afterwards and only for the slots that go on - a slot that settles
-      // keeps the offsets its lambda was computed with, so that (lambda, mode, offsets) stay one consistent triple
-      std::vector<double> zero(nb, 0.0);
-      CHK(upload_nosync(c, c->sc_alpha, zero.data(), sizeof(double) * nb));
-      hipLaunchKernelGGL(var_update_kernel, dim3(nb), dim3(256), 0, c->st, c->voff, (const double*)c->dgrad, mlam, (const double*)c->sc_alpha, c->sc_f);
-      CHK(download(c, vdelta.data(), c->sc_f, nb));
-    }
-    bool any_open = false;
-    for (int s = 0; s < nb; ++s) {
-      if ((vstat[s] == 1 || handed[s]) && !std::isfinite(vdelta[s])) { var_superseded(); return fail("variational fixed point: non-finite offsets for trial %d", tos[s]); }
-      if (vstat[s] != 1) continue;
-      vouter[s] = vo + 1;
-      if (vdelta[s] <= var->tol) { vstat[s] = 0; continue; }
-      // the map contracts by about half the largest posterior variance of a log rate per pass; a pass that does not shrink the change
-      // halves the step, three such passes give the trial back to the caller (status 2: the L-BFGS driver takes it from this lambda)
-      if (vdelta_prev[s] >= 0.0 && vdelta[s] > 0.7 * vdelta_prev[s]) { vdamp[s] *= 0.5; if (++vslow[s] >= 3) { vstat[s] = 2; continue; } }
-      vdelta_prev[s] = vdelta[s];
-      if (vo + 1 >= var->max_outer) continue;       // (stays 1: iteration cap)
-      any_open = true;
-    }
-    if (!any_open) break;
-    {
-      std::vector<double> step(nb, 0.0);
-      for (int s = 0; s < nb; ++s) step[s] = (vstat[s] == 1) ? vdamp[s] : 0.0;
-      CHK(upload_nosync(c, c->sc_alpha, step.data(), sizeof(double) * nb));
-      hipLaunchKernelGGL(var_update_kernel, dim3(nb), dim3(256), 0, c->st, c->voff, (const double*)c->dgrad, mlam, (const double*)c->sc_alpha, c->sc_f);
-      HIPC(hipGetLastError());
-    }
-    }
-    if (var) {
-      // optimum out: rho = log lambda, the dual cost there (inference.py:196-213), statuses
-      c->var_active = false;
-      CHK(dual_eval_slots(c, nb, tos, false, var->fopt + c0, false));
-      // the optimum stays on the device for pgpfa_dual_finalize(lam = NULL) and for blocks rebuilt on demand
-      if (!c->lam_keep) {
-        const size_t bytes = (size_t)c->R * mlam * sizeof(double);
-        if (hipMalloc((void**)&c->lam_keep, bytes) != hipSuccess) { (void)hipGetLastError(); c->lam_keep = nullptr; return fail("hipMalloc(%zu bytes) for the resident dual variables failed", bytes); }
-        c->bytes += bytes;
-      }
-      for (int s = 0; s < nb; ++s) {
-        CHK(copy_dev(c, c->lam_keep + (size_t)tos[s] * mlam, c->lamd + (size_t)s * mlam, mlam * sizeof(double)));
-        c->lam_resident[tos[s]] = 1; c->lam_valid[tos[s]] = 1;
-        // (lam_keep also feeds the blocks rebuilt on demand of a dual posterior: whatever posterior the trial had is superseded until
-        // pgpfa_dual_finalize has run on the new optimum)
-        c->trial_dual[tos[s]] = 0; c->trial_snap[tos[s]] = -1; c->vsmgp_ok[tos[s]] = 0;
-      }
-      if (var->lam_out) CHK(download(c, var->lam_out + (size_t)c0 * mlam, c->lamd, (size_t)nb * mlam));
-      if (var->rho) {
-        hipLaunchKernelGGL(var_log_kernel, dim3(2048), dim3(256), 0, c->st, (const double*)c->lamd, c->dgrad, (size_t)nb * mlam);
-        CHK(download(c, var->rho + (size_t)c0 * mlam, c->dgrad, (size_t)nb * mlam));
-      }
-      for (int s = 0; s < nb; ++s) {
-        if (var->outer) var->outer[c0 + s] = vouter[s];
-        var->vstatus[c0 + s] = vstat[s];
-        if (iters) iters[c0 + s] = its[s];
-        if (status) status[c0 + s] = stat[s];
-      }
-      n_fact += nb;
-      continue;
-    }
-    if (loo) {
-      // prediction of the held-out neurons from the modes in Xc (Xt and sc_f are free scratch here)
-      hipLaunchKernelGGL(loo_predict_kernel, dim3(nb), dim3(256), 0, c->st, c->Xc, ld, c->C, c->d, c->Y, c->Yhi, c->trial_of_slot, c->mask_of_slot,
-                         c->q, p, T, c->Xt, ld, c->sc_f);
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpy2DAsync(loo->y_pred + (size_t)c0 * T, (size_t)T * sizeof(double), c->Xt, (size_t)ld * sizeof(double), (size_t)T * sizeof(double),
-                            nb, hipMemcpyDeviceToHost, c->st));
-      CHK(download(c, loo->err + c0, c->sc_f, nb));
-      HIPC(hipStreamSynchronize(c->st));
-      for (int s = 0; s < nb; ++s) {
-        if (iters) iters[c0 + s] = its[s];
-        if (status) status[c0 + s] = stat[s];
-      }
-      continue;
-    }
-    // posterior covariance blocks at the mode
-    {
-      const bool sum_only = c->plan_lowrank && !c->keep_trial_vsmgp;
-      PhaseRange range_cov("pgpfa.covariance_blocks");
-      CHK(posterior_blocks(c, nb, 1.0, true, sum_only));
-      for (int t : tos) c->vsmgp_ok[t] = sum_only ? 0 : 1;
-    }
-    n_fact += nb;
-    for (int s = 0; s < nb; ++s) its[s] += 1;
-    {
-      // the mode a trial had before this E-step becomes its extrapolation base (once per E-step: a dense retry pass
-      // of the same E-step must not overwrite it with its own unfinished start point)
-      std::vector<int> rot(nb, 0);
-      for (int s = 0; s < nb; ++s) {
-        const int tr_ = tos[s];
-        if (c->mode_serial[tr_] != c->estep_serial) {
-          rot[s] = 1;
-          c->prev_serial[tr_] = c->mode_serial[tr_];
-          c->mode_serial[tr_] = c->estep_serial;
-        }
-      }
-      CHK(upload_list(c, c->list_a, rot));
-      hipLaunchKernelGGL(scatter_rotate_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xc, ld, nvec, c->Xmode, c->Xprev,
-                         c->trial_of_slot, c->list_a);
-    }
-    CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
-    CHK(dl_flush(c));
-    HIPC(hipGetLastError());
-    for (int s = 0; s < nb; ++s) {
-      if (info[s] != 0 && stat[s] == 0) stat[s] = 3;
-      total += f[s];
-      if (iters) iters[c0 + s] = its[s];
-      if (status) status[c0 + s] = stat[s];
-    }
-  }
-  if (obj_sum) *obj_sum = total;
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  c->info["last_estep_ms"] = ms;
-  c->info["last_newton_factorizations"] = n_fact;
-  c->info["last_newton_solves"] = n_solve;
-  c->info["last_pcg_iterations"] = n_pcg;
-  c->info["last_shared_factorizations"] = n_shared;
-  c->info["last_cov_lowrank"] = c->last_cov_lowrank ? 1.0 : 0.0;
-  c->info["last_newton_max_iter"] = max_it_seen;
-  c->info["last_cold_restarts"] = n_cold;
-  c->info["last_fallback_no_descent"] += n_fb_dir;            // (summed over the passes of one E-step: pgpfa_estep_laplace resets them)
-  c->info["last_fallback_line_search"] += n_fb_search;
-  c->info["last_fallback_outer_cap"] += n_fb_cap;
-  if (c->time_newton) {
+  void publish(pgpfa_ctx* c) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    c->info["last_estep_ms"] = ms;
+    c->info["last_newton_factorizations"] = n_fact;
+    c->info["last_newton_solves"] = n_solve;
+    c->info["last_pcg_iterations"] = n_pcg;
+    c->info["last_shared_factorizations"] = n_shared;
+    c->info["last_cov_lowrank"] = c->last_cov_lowrank ? 1.0 : 0.0;
+    c->info["last_newton_max_iter"] = max_it_seen;
+    c->info["last_cold_restarts"] = n_cold;
+    c->info["last_fallback_no_descent"] += n_fb_dir;            // (summed over the passes of one E-step: pgpfa_estep_laplace resets them)
+    c->info["last_fallback_line_search"] += n_fb_search;
+    c->info["last_fallback_outer_cap"] += n_fb_cap;
+    if (!c->time_newton) return;
     // (every chunk ended on a stream synchronisation: the events are complete)
     double nms = 0.0;
     for (auto& ev : newton_ev) {
@@ -1246,6 +456,940 @@ int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, do
     c->info["last_newton_solve_bytes_survey"] = newton_bytes_survey;
     c->info["last_newton_solve_bytes_moved"] = newton_bytes_moved;
   }
+};
+
+// one chunk of the call's list: nb <= c->B items in the slots [0, nb)
+struct Chunk {
+  explicit Chunk(int B) : f(B), qxx(B), qdx(B), qdd(B), dec(B), smax(B), alpha(B), ftry(B), its(B), stat(B), info(B) {}
+  std::vector<double> f, qxx, qdx, qdd, dec, smax, alpha, ftry;   // slot-indexed scalars of the mode search (sized once per call)
+  std::vector<int> its, stat, info;
+  int c0 = 0, nb = 0;                           // first item of the chunk in the call's list; slots in use
+  std::vector<int> tos;                         // trial of a slot
+  std::vector<int> how;                         // start point of a slot: 0 cold (zero), 1 the resident mode, 2 its extrapolation
+  bool any_warm = false;
+  std::vector<int> active, leftovers;           // slots still searching; slots the shared-preconditioner phase gave up on
+  std::vector<char> w32_ok;                     // slots whose packed single-precision curvature matches W (see SolveForm)
+};
+
+// the variational fixed point of one chunk, per slot: change of the offsets in the last two passes, damping, status, passes taken, slow passes
+struct VarState {
+  VarState(int nb, size_t mlam) : mlam(mlam), delta(nb, 0.0), delta_prev(nb, -1.0), damp(nb, 1.0), stat(nb, 1), outer(nb, 0), slow(nb, 0) {}
+  const size_t mlam;                            // dual variables per trial (q T)
+  std::vector<double> delta, delta_prev, damp;
+  std::vector<int> stat, outer, slow;
+};
+
+// form of the inner solve of the shared-preconditioner phase, fixed per chunk by the options, the plan and the chunk's size
+struct SolveForm {
+  bool thin_ok, wide_ok, fused, onek, f2, v32, rx32;
+  int TB, Tl, Tw, npk;
+  long long sW32;
+  // storage types of the solve's private vectors (z, s, p, q, t / y) and of its residual and step
+  template <class Fn> void with_tv(Fn&& fn) const { if (rx32) fn(float{}, float{}); else if (v32) fn(float{}, double{}); else fn(double{}, double{}); }
+};
+
+static SolveForm solve_form(const pgpfa_ctx* c, int nb) {
+  const int p = c->p, T = c->T; const long long ld = c->ld;
+  SolveForm sf{};
+  // (small chunks are launch-latency bound: there the extra packing / check launches of the host-free form cost more than
+  // the round trips they remove - measured at config 2: 8.6 vs 8.0 ms per E-step)
+  sf.thin_ok = c->thin_products && c->mfma && T >= 4 && (size_t)c->rpad <= (size_t)c->ld;
+  // (11 .. 20 latents: only the round-5 form of the host-free step exists - pcgw_*_kernel - and it needs the thin products)
+  sf.wide_ok = p <= 20 && c->pcg_form >= 2 && sf.thin_ok && c->pcg_w32 && c->pcg_retire && c->pcg_blk != nullptr;
+  sf.fused = c->pcg_fused && c->plan_lowrank && (p <= 16 || sf.wide_ok) && c->h_pcg != nullptr && (c->pcg_fused == 2 || (double)nb * c->n >= 1.0e6);
+  // form of the host-free iteration (pcg.h): the two-kernel step without the prior mat-vec needs the packed FP32 curvature and per-slot
+  // retirement; otherwise the split kernels of round 3
+  sf.onek = sf.fused && c->pcg_w32 && c->pcg_retire && c->pcg_form != 0 && (p <= 10 || sf.wide_ok);
+  // round 5 (pcg_form = 2): the solve's private vectors on line-aligned latent rows, ONE start kernel (gradient, residual, zero step, first
+  // per-bin application), the step's closing inside kernel A, ONE upload (control block, list, forcing terms); needs the thin products
+  sf.f2 = sf.onek && c->pcg_form >= 2 && sf.thin_ok && c->pcg_blk != nullptr;
+  sf.TB = p <= 10 ? 64 : PCGW_TB;               // bins per workgroup tile of the step's per-bin kernels
+  // ... and (second half of round 5) z, s, p, q, t / y of the solve stored in single precision (PcgCgP::vec32)
+  sf.v32 = sf.f2 && c->pcg_vec32;
+  sf.Tl = !sf.f2 ? T : (sf.v32 && (long long)p * round_up(T, 32) <= ld) ? round_up(T, 32) : ((long long)p * round_up(T, 16) <= ld) ? round_up(T, 16) : T;
+  // ... and (round 6) the residual and the step as well, up to 10 latents (PcgCgP::X32): x in the free second half of Z's buffer
+  sf.rx32 = sf.v32 && c->pcg_rx32 && p <= 10;
+  // packed single-precision curvature of the two-kernel step (pcg.h): component-major [c][Tw], rows on 128-byte lines.  It is written where W is:
+  // by pack_w32t_kernel at the start of a solve for slots whose W came from the Poisson pass at the E-step's start point, and by the commit of an
+  // accepted step (commit_w_pack_kernel: the copy W <- Wt and the packing in one pass over Wt - a solve after the first finds every active slot packed)
+  sf.npk = p * (p + 1) / 2;
+  sf.Tw = round_up(T, 32);
+  sf.sW32 = (long long)sf.Tw * sf.npk;
+  return sf;
+}
+
+// bind the chunk that starts at item c0 of the list to the slots: trials, the neurons a leave-one-out item leaves out, cleared factor flags
+static int bind_chunk(pgpfa_ctx* c, Chunk& ch, const Trials& tr, int c0, const LooJob* loo) {
+  const int nb = std::min(c->B, (int)tr.v.size() - c0);
+  ch.c0 = c0; ch.nb = nb;
+  ch.tos.assign(tr.v.begin() + c0, tr.v.begin() + c0 + nb);
+  CHK(upload_list(c, c->trial_of_slot, ch.tos));
+  if (loo) {
+    std::vector<int> mk(loo->mask->begin() + c0, loo->mask->begin() + c0 + nb);
+    CHK(upload_list(c, c->mask_of_slot, mk));
+    c->mask_active = true;
+  }
+  HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
+  ch.how.assign(nb, 0); ch.any_warm = false; ch.active.clear();
+  return 0;
+}
+
+// (error paths of the fixed point: the passes have overwritten the per-bin blocks of the chunk's trials - whatever posterior they had is gone)
+static void var_superseded(pgpfa_ctx* c, const std::vector<int>& tos) {
+  for (int t : tos) { c->trial_dual[t] = 0; c->trial_snap[t] = -1; c->vsmgp_ok[t] = 0; c->lam_resident[t] = 0; c->lam_valid[t] = 0; }
+}
+
+// start of the variational fixed point:
+// lambda of the chunk -> W = C^T diag(lambda) C (+ the reference's jitter), the covariance blocks and from them the first offsets;
+// start point of the mode search: the variational mean of that lambda, -K C_big (lambda - y) (inference.py:194)
+// (exp / log of the q T entries of every trial run on the device: on the host they were 1.3e8 libm calls per 256 config-5 trials - half a
+// second each way, more than the whole fixed point)
+static int start_variational(pgpfa_ctx* c, Chunk& ch, const VarJob* var, const VarState& vs) {
+  const int nb = ch.nb, nvec = c->n; const long long ld = c->ld;
+  const size_t mlam = vs.mlam;
+  if (var->start == 3) {
+    for (int s = 0; s < nb; ++s) CHK(copy_dev(c, c->lamd + (size_t)s * mlam, c->lam_keep + (size_t)ch.tos[s] * mlam, mlam * sizeof(double)));
+  } else if (var->start != 0) {
+    CHK(upload(c, c->lamd, var->rho + (size_t)ch.c0 * mlam, (size_t)nb * mlam));
+  }
+  int* bad_dev = reinterpret_cast<int*>(c->pcg_ratio);              // (scratch word: no inner solve is running)
+  HIPC(hipMemsetAsync(bad_dev, 0, sizeof(int), c->st));
+  if (var->start != 3) hipLaunchKernelGGL(var_exp_kernel, dim3(2048), dim3(256), 0, c->st, c->lamd, (size_t)nb * mlam, var->start == 0 ? 1 : 0, 0.5, bad_dev);
+  int bad = 0;
+  CHK(dl_enqueue(c, &bad, bad_dev, sizeof(int)));
+  CHK(dl_flush(c));
+  if (bad) return fail("rho must be finite with a positive finite exp (trials %d..%d)", ch.tos.front(), ch.tos.back());
+  std::vector<double> sB_, sD_, vKv_;
+  CHK(dual_common(c, nb, &sB_, &sD_, &vKv_));
+  // (only when lambda is a previous optimum: from a cold lambda that mean is far out - hundreds in the log rate - and zero is the safe start)
+  if (var->start >= 2) hipLaunchKernelGGL(negate_rows_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->KD, ld, c->Xc, ld, nvec, c->ident);
+  else HIPC(hipMemsetAsync(c->Xc, 0, (size_t)ld * nb * sizeof(double), c->st));
+  if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }
+  else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
+  CHK(var_offsets(c, nb, c->voff));
+  c->var_active = true;
+  return 0;
+}
+
+// start points of a Laplace or leave-one-out chunk: cold (zero), the resident mode, or its extrapolation; warm_start = 2 takes the resident mode
+// only for trials some earlier E-step has produced one for (minibatches revisiting trials) and starts the others cold
+static int start_laplace(pgpfa_ctx* c, Chunk& ch, int warm_start) {
+  const int nb = ch.nb, nvec = c->n; const long long ld = c->ld;
+  bool any = false;
+  // (the difference of the last two modes is only a prediction while the parameters keep their pace: ctx.h, extrapolate_guard)
+  const bool trend_ok = c->extrapolate && (c->extrapolate_guard <= 0.0 || (c->par_step > 0.0 && c->par_step_prev >= 0.0 &&
+                                                                             c->par_step_prev <= c->extrapolate_guard * c->par_step));
+  for (int s = 0; s < nb && warm_start; ++s) {
+    const int tr_ = ch.tos[s];
+    if (warm_start == 2 && c->mode_serial[tr_] < 0) continue;
+    ch.how[s] = 1;
+    if (trend_ok && c->mode_serial[tr_] == c->estep_serial - 1 && c->prev_serial[tr_] == c->estep_serial - 2) ch.how[s] = 2;
+    any = true;
+  }
+  ch.any_warm = any;
+  if (any) {
+    CHK(upload_list(c, c->list_a, ch.how));
+    hipLaunchKernelGGL(gather_start_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, c->Xprev, nvec, c->Xc, ld,
+                       c->trial_of_slot, c->list_a, c->extrapolate_beta);
+  } else {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, nvec, c->Xc, ld, c->trial_of_slot, 1);
+  }
+  return 0;
+}
+
+// objective, gradient pieces and curvature blocks at the start point
+static int eval_start(pgpfa_ctx* c, Chunk& ch) {
+  const int nb = ch.nb;
+  CHK(prior_mv_all(c, nb, c->Xc, c->KX));
+  hipLaunchKernelGGL(dots3_kernel, dim3(nb), dim3(256), 0, c->st, c->Xc, (long long)c->ld, c->KX, (long long)c->ld, (const double*)nullptr, 0LL,
+                     (const double*)nullptr, 0LL, c->n, c->ident, c->sc_qxx, c->sc_qdx, c->sc_qdd);
+  CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
+  CHK(dl_enqueue(c, ch.f.data(), c->sc_f, nb * sizeof(double)));
+  CHK(download(c, ch.qxx.data(), c->sc_qxx, nb));
+  for (int s = 0; s < nb; ++s) ch.f[s] += 0.5 * ch.qxx[s];
+  return 0;
+}
+
+// eval_start behind the cold-restart guard (guard: the first pass of a Laplace or leave-one-out chunk with warm starts, option start_guard)
+static int eval_start_guarded(pgpfa_ctx* c, Chunk& ch, bool guard, EstepStats& st) {
+  const int nb = ch.nb, nvec = c->n;
+  if (guard) {
+    // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
+    hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
+                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->q, c->T, c->sc_alpha);
+    CHK(dl_enqueue(c, ch.ftry.data(), c->sc_alpha, nb * sizeof(double)));
+  }
+  CHK(eval_start(c, ch));
+  if (!guard) return 0;
+  // A warm start that does worse than x = 0 is no start: after a jump of the parameters (another fold's fit, the generating parameters, a second
+  // fit in one process) the resident modes belong to other loadings - log rates of +-100, a curvature the single-precision copies cannot hold -
+  // and 931 of 1024 trials went through the dense per-trial retry (1.8 s where a cold E-step takes 0.12: tools/jump_probe.py).  Those slots
+  // restart at zero; the objective is strictly convex, the start point never changes the mode.
+  std::vector<int> cold;
+  for (int s = 0; s < nb; ++s)
+    if (ch.how[s] != 0 && !(ch.f[s] <= ch.ftry[s])) cold.push_back(s);
+  if (!cold.empty()) {
+    CHK(upload_list(c, c->list_b, cold));
+    hipLaunchKernelGGL(zero_rows_kernel, dim3((nvec + 255) / 256, (unsigned)cold.size()), dim3(256), 0, c->st, c->Xc, (long long)c->ld, nvec, c->list_b);
+    CHK(eval_start(c, ch));
+    st.n_cold += (double)cold.size();
+  }
+  return 0;
+}
+
+// backtracking line search along Dl for the slots in `cand` (objective with rounding-noise slack as in
+// the oracle); needs dec/qxx/qdx/qdd of those slots on the host.  Accepted slots are committed
+// (X, K^-1 x, likelihood gradient, W); returns the slots whose search was exhausted.
+static int line_search(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, const std::vector<int>& cand, std::vector<int>* failed) {
+  const int nb = ch.nb, nvec = c->n, p = c->p, T = c->T; const long long ld = c->ld;
+  std::vector<int> pending;
+  for (int s : cand) { ch.alpha[s] = 1.0; pending.push_back(s); }
+  for (int ls = 0; ls < 40 && !pending.empty(); ++ls) {
+    const int np_ = (int)pending.size();
+    CHK(upload_nosync(c, c->list_b, pending.data(), sizeof(int) * pending.size()));
+    CHK(upload_nosync(c, c->sc_alpha, ch.alpha.data(), sizeof(double) * nb));
+    hipLaunchKernelGGL(make_try_kernel, dim3((nvec + 255) / 256, np_), dim3(256), 0, c->st, c->Xc, ld, c->Dl, ld, c->sc_alpha, c->Xt, ld, nvec,
+                       c->list_b);
+    CHK(poisson(c, c->list_b, np_, c->Xt, c->Glt, c->Wt, c->sc_f, 1));
+    CHK(download(c, ch.ftry.data(), c->sc_f, nb));
+    std::vector<int> acc, rej;
+    for (int s : pending) {
+      const double a = ch.alpha[s];
+      const double ft = ch.ftry[s] + 0.5 * (ch.qxx[s] + 2.0 * a * ch.qdx[s] + a * a * ch.qdd[s]);
+      const double slack = 1e-12 * (1.0 + std::fabs(ch.f[s]));
+      if (std::isfinite(ft) && ft <= ch.f[s] - 1e-4 * a * ch.dec[s] + slack) {
+        ch.f[s] = ft;
+        acc.push_back(s);
+      } else {
+        ch.alpha[s] = 0.5 * a;
+        rej.push_back(s);
+      }
+    }
+    if (!acc.empty()) {
+      const int nacc = (int)acc.size();
+      CHK(upload_nosync(c, c->list_b, acc.data(), sizeof(int) * acc.size()));
+      const int nw = T * p * p;
+      hipLaunchKernelGGL(commit_kernel, dim3((nvec + 255) / 256, nacc), dim3(256), 0, c->st, c->Xc, c->Xt, c->KX, c->KD, c->Gl, c->Glt, ld,
+                         c->W, c->Wt, (long long)nw, c->sc_alpha, nvec, sf.onek ? 0 : nw, c->list_b);
+      if (sf.onek) {
+        hipLaunchKernelGGL(commit_w_pack_kernel, dim3((T + 63) / 64, nacc), dim3(256), (size_t)sf.npk * 65 * sizeof(float), c->st, (const double*)c->Wt, c->W,
+                           (long long)nw, c->W32, sf.sW32, sf.Tw, T, p, c->list_b);
+        for (int s : acc) ch.w32_ok[s] = 1;
+      }
+      HIPC(hipGetLastError());
+    }
+    pending.swap(rej);
+  }
+  *failed = pending;
+  return 0;
+}
+
+// the shared-preconditioner phase of one pass over a chunk: residual norms and predicted errors per slot, and the outer iteration in flight
+struct NewtonState {
+  explicit NewtonState(int nb) : rr(nb), rr0(nb), err_pred(nb, -1.0) {}
+  std::vector<double> rr, rr0, err_pred;        // err_pred < 0: the slot has taken no step yet
+  double eta_target = 0.0;                      // forcing term of this outer iteration: the smallest over the active slots
+  int outer = 0, na = 0, done_inner = 0;        // na: active slots; done_inner: inner iterations run (-1: read from the control block)
+};
+
+// forcing term of a slot (relative residual the inner solve is run to).  With e the predicted error of the slot's current iterate, solving
+// beyond eta ~ e buys nothing (the Newton step itself leaves ~e^2), and when a looser solve already lands below the stopping tolerance that
+// looser value is enough.
+static double forcing_term(const pgpfa_ctx* c, double err_pred) {
+  if (!(err_pred >= 0.0)) return c->pcg_eta0;                  // first outer iteration of this slot
+  const double e = std::max(err_pred, 1e-300);
+  return std::max(1e-9, std::min(c->pcg_eta0, std::max(e, c->chord_xtol / (20.0 * e))));
+}
+
+// the forcing terms as the host-free solves read them: every slot its own, or (split form with pcg_retire = 0) the common one
+static std::vector<float> forcing_terms(const pgpfa_ctx* c, const Chunk& ch, const NewtonState& nw, bool per_slot) {
+  std::vector<float> eta_s(ch.nb, (float)nw.eta_target);
+  if (per_slot) for (int s : ch.active) eta_s[s] = (float)forcing_term(c, nw.err_pred[s]);
+  return eta_s;
+}
+
+// After enqueuing iteration `it` of a host-free solve: stay at most `lead` iterations ahead of the device (an iteration enqueued past the stop
+// costs ~13 empty launches: that matters when the kernels themselves take microseconds); the wait spins on the host-mapped counter, no API call.
+// True when the device has already stopped: whatever is enqueued is a no-op.
+static bool device_stopped(pgpfa_ctx* c, int it, int lead) {
+  if (*(volatile int*)&c->h_pcg[0]) return true;
+  if (it + 1 < c->pcg_inner_max) {
+    const auto t_spin = std::chrono::steady_clock::now();
+    while (!*(volatile int*)&c->h_pcg[0] && (it + 1) - *(volatile int*)&c->h_pcg[1] > lead) {
+      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spin).count() > 5.0) break;   // (never hang on a lost flag)
+    }
+    if (*(volatile int*)&c->h_pcg[0]) return true;
+  }
+  return false;
+}
+
+// the start kernel of the two-kernel step's round-5 form
+static void launch_cg_start(pgpfa_ctx* c, const SolveForm& sf, const PcgCgP& cp, dim3 g0) {
+  dispatch_pw(c->p, [&](auto pw) {
+    constexpr int PW = decltype(pw)::value;
+    if constexpr (PW <= 10) {
+      const size_t lb = pcg_cg_b_lds(PW);
+      sf.with_tv([&](auto tv, auto tx) {
+        using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
+        if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_start_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+        hipLaunchKernelGGL((pcg_cg_start_kernel<PW, TV, TX>), g0, dim3(256), lb, c->st, cp);
+      });
+    } else if constexpr (PW <= 20) {
+      const size_t lb = pcgw_b_lds(PW);
+      sf.with_tv([&](auto tv, auto tx) {
+        using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
+        if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_start_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+        hipLaunchKernelGGL((pcgw_start_kernel<PW, TV>), g0, dim3(256), lb, c->st, cp);
+      });
+    }
+  });
+}
+
+// kernels A and B of one step
+static void launch_cg_step(pgpfa_ctx* c, const SolveForm& sf, const PcgCgP& cp, dim3 gcg) {
+  dispatch_pw(c->p, [&](auto pw) {
+    constexpr int PW = decltype(pw)::value;
+    if constexpr (PW <= 10) {
+      const size_t la = pcg_cg_a_lds(PW), lb = pcg_cg_b_lds(PW);
+      // (per launch, not once per process: contexts of one process may sit on different devices)
+      sf.with_tv([&](auto tv, auto tx) {
+        using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
+        if (la > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_a_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)la);
+        if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcg_cg_b_kernel<PW, TV, TX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+        hipLaunchKernelGGL((pcg_cg_a_kernel<PW, TV, TX>), gcg, dim3(256), la, c->st, cp);
+        hipLaunchKernelGGL((pcg_cg_b_kernel<PW, TV, TX>), gcg, dim3(256), lb, c->st, cp);
+      });
+    } else if constexpr (PW <= 20) {
+      const size_t la = pcgw_a_lds(PW), lb = pcgw_b_lds(PW);
+      sf.with_tv([&](auto tv, auto tx) {
+        using TV = decltype(tv); using TX = decltype(tx); (void)sizeof(TX);
+        if (la > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_a_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)la);
+        if (lb > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pcgw_b_kernel<PW, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+        hipLaunchKernelGGL((pcgw_a_kernel<PW, TV>), gcg, dim3(256), la, c->st, cp);
+        hipLaunchKernelGGL((pcgw_b_kernel<PW, TV>), gcg, dim3(256), lb, c->st, cp);
+      });
+    }
+  });
+}
+
+// ---- inner solve, two-kernel step: per step pcg_cg_a_kernel, pcg_cg_b_kernel, the closing kernel and the three preconditioner products (pcg.h)
+static int solve_two_kernel(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, NewtonState& nw) {
+  const int nb = ch.nb, na = nw.na, p = c->p, T = c->T, TB = sf.TB; const long long ld = c->ld;
+  const bool f2 = sf.f2;
+  const int* skip = &c->pcgctl->stop;
+  const std::vector<float> eta_s = forcing_terms(c, ch, nw, true);
+  PcgCtl h0{};
+  h0.nlive = na; h0.nl[0] = na;
+  if (f2) {
+    // one upload: [control block (16 words) | list_a | first live list | forcing terms] - consecutive pieces of c->pcg_blk
+    const size_t nB = (size_t)c->B;
+    std::vector<int> img(16 + 3 * nB, 0);
+    std::memcpy(img.data(), &h0, sizeof(PcgCtl));
+    std::memcpy(img.data() + 16, ch.active.data(), sizeof(int) * na);
+    std::memcpy(img.data() + 16 + nB, ch.active.data(), sizeof(int) * na);
+    std::memcpy(img.data() + 16 + 2 * nB, eta_s.data(), sizeof(float) * nb);
+    CHK(upload_nosync(c, c->pcg_blk, img.data(), img.size() * sizeof(int)));
+  } else {
+    CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
+    CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
+    CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
+  }
+  c->h_pcg[0] = 0; c->h_pcg[1] = 0; c->h_pcg[2] = na;
+  PcgCgP cp{};
+  cp.GbT = c->GbT; cp.WbT = reinterpret_cast<const float*>(c->WbT); cp.W32T = c->W32; cp.sW32 = sf.sW32; cp.Tw = sf.Tw;
+  cp.X = c->Dl; cp.R = c->Rv; cp.P = c->Pv; cp.Q = c->Qv; cp.Z = c->Zv; cp.S = c->Sv; cp.Y = c->Xt; cp.sV = ld;
+  cp.part = c->sc_part2; cp.gam = c->cg_scal; cp.alp = c->cg_scal + 2 * (size_t)c->B; cp.rr = c->sc_rr; cp.rr0 = c->sc_rr0; cp.eta = c->pcg_eta;
+  cp.ctl = c->pcgctl; cp.live0 = c->live; cp.live1 = c->live1;
+  cp.eps = c->eps; cp.T = T; cp.p = p; cp.inner_min = c->pcg_inner_min; cp.ntile = (T + TB - 1) / TB; cp.B = c->B; cp.xcd_map = c->pcg_xcd;
+  cp.X32 = reinterpret_cast<float*>(c->Zv) + (size_t)ld * ((size_t)c->B + 128);     // (the single-precision z fills the first half of Zv)
+  cp.Tl = sf.Tl; cp.Tx = T; cp.vec32 = sf.v32 ? 1 : 0; cp.fold_close = f2 ? 1 : 0; cp.host = (volatile int*)c->d_hpcg; cp.Gl = c->Gl; cp.KX = c->KX; cp.Gt = c->Gt;
+  auto cg_grid = [&](int bound) {
+    cp.spw = !c->pcg_adapt ? PCG_SLOTS : bound > 640 ? 16 : bound > 320 ? 8 : 4;
+    if (TB != 64) cp.spw = std::max(cp.spw, PCGW_SL);                                     // (a 32-bin workgroup has 8 slots in flight)
+    return dim3((T + TB - 1) / TB, round_up((bound + cp.spw - 1) / cp.spw, 8));           // (slot groups in blocks of 8: pcg_cg_wg)
+  };
+  if (f2) launch_cg_start(c, sf, cp, cg_grid(na));
+  std::vector<int> need;
+  for (int s : ch.active) if (!ch.w32_ok[s]) { need.push_back(s); ch.w32_ok[s] = 1; }
+  if (!need.empty()) {
+    CHK(upload_nosync(c, c->list_b, need.data(), sizeof(int) * need.size()));
+    hipLaunchKernelGGL(pack_w32t_kernel, dim3((T + 63) / 64, (unsigned)need.size()), dim3(256), (size_t)sf.npk * 65 * sizeof(float), c->st, c->W,
+                       (long long)T * p * p, c->W32, sf.sW32, sf.Tw, T, p, c->list_b);
+  }
+  // t = Gb r0 (the start kernel has it already), then y = F Sb F^T t over the listed columns (left in c->Xt)
+  CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, !f2, false, c->list_a, na, f2 ? sf.Tl : 0, sf.v32));
+  NdevGuard ndev_guard{c};
+  c->live_gemms.clear();
+  int last_step = -1;
+  for (int it = 0; it < c->pcg_inner_max; ++it) {
+    cp.par = it & 1; cp.first = (it == 0) ? 1 : 0; cp.step = it; last_step = it;
+    // The launches of a step are sized by the live count the closing kernel last mirrored to the host (it only falls during a solve, so a
+    // value that is a step or two old is an upper bound; the kernels read the true count on the device).  Few live slots: fewer slots per
+    // workgroup, so that the per-bin kernels still offer every CU a workgroup and a wave walks one slot instead of four in a row.
+    const int seen = *(volatile int*)&c->h_pcg[2];
+    const int bound = c->pcg_adapt ? std::max(1, std::min(na, seen)) : na;
+    const dim3 gcg = cg_grid(bound);
+    launch_cg_step(c, sf, cp, gcg);
+    if (!f2) hipLaunchKernelGGL(pcg_iter_close_kernel, dim3(1), dim3(64), 0, c->st, c->pcgctl, it & 1, (volatile int*)c->d_hpcg, -1);
+    // the preconditioner products for the NEXT iteration run over the list this launch has just written
+    c->live_gemm_collect = (it == 0);
+    c->cur_ndev = &c->pcgctl->nl[(it & 1) ^ 1];
+    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, (it & 1) ? c->live : c->live1, bound, f2 ? sf.Tl : 0, sf.v32));
+    if (device_stopped(c, it, 2)) break;
+  }
+  // (pcg_form 2: kernel A of step i + 1 closes step i; the last step enqueued is closed here unless the solve had stopped before it)
+  if (f2 && last_step >= 0) hipLaunchKernelGGL(pcg_iter_close_kernel, dim3(1), dim3(64), 0, c->st, c->pcgctl, last_step & 1, (volatile int*)c->d_hpcg, last_step);
+  c->cur_ndev = nullptr;
+  c->live_gemm_collect = false;
+  CHK(dl_enqueue(c, &c->fused_ctl_host, c->pcgctl, sizeof(PcgCtl)));
+  HIPC(hipGetLastError());
+  nw.done_inner = -1;
+  return 0;
+}
+
+// ---- inner solve without host round trips, split kernels of round 3 (pcg.h): the stopping test runs on the device, iterations are enqueued
+// ahead, kernels of iterations past the stop return at once
+static int solve_split(pgpfa_ctx* c, Chunk& ch, NewtonState& nw) {
+  const int nb = ch.nb, na = nw.na, nvec = c->n, p = c->p, T = c->T; const long long ld = c->ld;
+  const int ntile = (T + 63) / 64;
+  const int* skip = &c->pcgctl->stop;
+  const long long sW32 = (long long)T * (p * (p + 1) / 2);       // (pack_w32_kernel: rows of T, not the two-kernel step's padded rows)
+  // the live list starts as the active list; every slot carries its own forcing term (with pcg_retire = 0: the common one)
+  const std::vector<float> eta_s = forcing_terms(c, ch, nw, c->pcg_retire);
+  CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
+  CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
+  PcgCtl h0{};
+  h0.nlive = na;
+  CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
+  c->h_pcg[0] = 0; c->h_pcg[1] = 0;
+  if (c->pcg_w32)
+    hipLaunchKernelGGL(pack_w32_kernel, dim3((unsigned)((sW32 + 255) / 256), na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->W32,
+                       sW32, T, p, c->list_a);
+  const dim3 gbin(ntile, (na + PCG_SLOTS - 1) / PCG_SLOTS);
+  // z0 = P^-1 r0, p0 = z0
+  CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, false, c->list_a, na));
+  dispatch_pw(p, [&](auto pw) {
+    constexpr int PW = decltype(pw)::value;
+    if constexpr (PW <= 16)
+      hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->list_a, na,
+                         c->sc_part2, (const int*)nullptr, (const PcgCtl*)nullptr);
+  });
+  hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_part2, ntile, c->sc_rz,
+                     c->sc_rr, c->sc_rr0, 1, (PcgCtl*)nullptr, (float*)nullptr);
+  c->cur_ndev = &c->pcgctl->nlive;
+  NdevGuard ndev_guard{c};
+  c->live_gemms.clear();
+  for (int it = 0; it < c->pcg_inner_max; ++it) {
+    c->live_gemm_collect = (it == 0);
+    CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, skip, c->live, na));
+    dispatch_pw(p, [&](auto pw) {
+      constexpr int PW = decltype(pw)::value;
+      if constexpr (PW <= 16) {
+        if (c->pcg_w32)
+          hipLaunchKernelGGL(pcg_hessvec32_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W32, sW32, c->Pv, c->Qv, ld, T, p,
+                             c->live, c->sc_pq, skip, (const PcgCtl*)c->pcgctl);
+        else
+          hipLaunchKernelGGL(pcg_hessvec_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv, c->Qv,
+                             ld, T, p, c->live, c->sc_pq, (const int*)&c->pcgctl->nlive);
+        hipLaunchKernelGGL(pcg_xr_apply_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Dl, c->Rv, c->Pv, c->Qv, c->Xt, ld, T, p,
+                           c->live, na, c->sc_rz, c->sc_pq, ntile, skip, (const PcgCtl*)c->pcgctl);
+      }
+    });
+    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, c->live, na));
+    dispatch_pw(p, [&](auto pw) {
+      constexpr int PW = decltype(pw)::value;
+      if constexpr (PW <= 16)
+        hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->live,
+                           na, c->sc_part2, skip, (const PcgCtl*)c->pcgctl);
+    });
+    hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->live, c->sc_part2, ntile,
+                       c->sc_rz, c->sc_rr, c->sc_rr0, 0, c->pcgctl, c->pcg_ratio);
+    hipLaunchKernelGGL(pcg_check_kernel, dim3(1), dim3(256), 0, c->st, c->pcgctl, (volatile int*)c->d_hpcg, c->live,
+                       (const float*)c->pcg_ratio, (const float*)c->pcg_eta, c->pcg_inner_min);
+    if (device_stopped(c, it, 3)) break;
+  }
+  c->cur_ndev = nullptr;
+  c->live_gemm_collect = false;
+  CHK(dl_enqueue(c, &c->fused_ctl_host, c->pcgctl, sizeof(PcgCtl)));
+  HIPC(hipGetLastError());
+  nw.done_inner = -1;                                     // read from the control block with the step's scalars (read_step)
+  return 0;
+}
+
+// ---- inner solve with a host round trip per iteration: the path of small chunks and of the dense plan
+static int solve_round_trip(pgpfa_ctx* c, Chunk& ch, NewtonState& nw) {
+  const int nb = ch.nb, na = nw.na, nvec = c->n, p = c->p, T = c->T; const long long ld = c->ld;
+  CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, true, c->list_a, na));
+  hipLaunchKernelGGL(pcg_update_p_kernel, dim3(na), dim3(256), 0, c->st, c->Rv, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_rz, c->sc_rr0, 1);
+  for (int it = 0; it < c->pcg_inner_max; ++it) {
+    CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, nullptr, c->list_a, na));
+    int pq_tiles = 1;
+    dispatch_pw(p, [&](auto pw) {
+      constexpr int PW = decltype(pw)::value;
+      if constexpr (PW <= 16) {
+        pq_tiles = (T + 63) / 64;
+        hipLaunchKernelGGL(pcg_hessvec_dot_kernel<PW>, dim3(pq_tiles, na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv,
+                           c->Qv, ld, T, p, c->list_a, c->sc_pq);
+      } else {
+        hipLaunchKernelGGL(pcg_hessvec_dot_wide_kernel<PW>, dim3(na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv, c->Qv, ld,
+                           T, p, c->list_a, c->sc_pq);
+      }
+    });
+    hipLaunchKernelGGL(pcg_update_xr_kernel, dim3(na), dim3(256), 0, c->st, c->Dl, c->Rv, c->Pv, c->Qv, ld, nvec, c->list_a, c->sc_rz, c->sc_pq,
+                       pq_tiles);
+    CHK(shared_solve(c, nb, c->Rv, c->Zv, nullptr, true, true, c->list_a, na));
+    hipLaunchKernelGGL(pcg_update_p_kernel, dim3(na), dim3(256), 0, c->st, c->Rv, c->Zv, c->Pv, ld, nvec, c->list_a, c->sc_rz, c->sc_rr, 0);
+    nw.done_inner = it + 1;
+    if (nw.done_inner >= c->pcg_inner_min) {
+      CHK(download(c, nw.rr.data(), c->sc_rr, nb));
+      if (it == c->pcg_inner_min - 1) CHK(download(c, nw.rr0.data(), c->sc_rr0, nb));
+      double worst = 0.0;
+      for (int s : ch.active) worst = std::max(worst, nw.rr0[s] > 0.0 ? std::sqrt(nw.rr[s] / nw.rr0[s]) : 0.0);
+      if (worst <= nw.eta_target) break;
+    }
+  }
+  return 0;
+}
+
+// one inner solve H_r delta = -g of the active slots in the chunk's form, between the events that time it, and the statistics of the step
+static int inner_solve(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, NewtonState& nw, EstepStats& st) {
+  const int na = nw.na, nvec = c->n; const long long ld = c->ld;
+  nw.done_inner = 0;
+  c->fused_ctl_host = PcgCtl{};                      // (context member: a queued read-back must not point into a frame of this file)
+  if (!sf.f2) CHK(upload_nosync(c, c->list_a, ch.active.data(), sizeof(int) * ch.active.size()));
+  if (c->time_newton) {
+    st.newton_ev.emplace_back(prof_event(c->prof), prof_event(c->prof));
+    hipEventRecord(st.newton_ev.back().first, c->st);
+  }
+  if (!sf.f2) {
+    hipLaunchKernelGGL(grad_total_kernel, dim3((nvec + 255) / 256, na), dim3(256), 0, c->st, c->Gl, ld, c->KX, ld, c->Gt, ld, nvec, c->list_a);
+    hipLaunchKernelGGL(pcg_init_kernel, dim3((c->npad + 255) / 256, na), dim3(256), 0, c->st, c->Gt, c->Rv, c->Dl, ld, nvec, c->npad, c->list_a);
+  }
+  if (sf.onek) CHK(solve_two_kernel(c, ch, sf, nw));
+  else if (sf.fused) CHK(solve_split(c, ch, nw));
+  else CHK(solve_round_trip(c, ch, nw));
+  if (sf.onek && sf.rx32) {
+    // the step comes back in single precision on the solve's private rows: widened into Dl by the kernel that reads it first (inside the timed
+    // region of the solve: it is part of what the single-precision step costs)
+    hipLaunchKernelGGL(step_stats_x32_kernel, dim3(na), dim3(256), 0, c->st, c->Gt, reinterpret_cast<const float*>(c->Zv) + (size_t)ld * ((size_t)c->B + 128),
+                       c->Dl, ld, c->T, sf.Tl, c->p, c->list_a, c->sc_dec, c->sc_smax);
+    if (c->time_newton) hipEventRecord(st.newton_ev.back().second, c->st);
+  } else {
+    if (c->time_newton) hipEventRecord(st.newton_ev.back().second, c->st);
+    hipLaunchKernelGGL(step_stats_kernel, dim3(na), dim3(256), 0, c->st, c->Gt, c->Dl, ld, nvec, c->list_a, c->sc_dec, c->sc_smax);
+  }
+  return 0;
+}
+
+// bytes of the inner iterations just run, by three models (slot_iters: sum over the slots of the iterations each stayed live)
+static void account_bytes(const pgpfa_ctx* c, const SolveForm& sf, const NewtonState& nw, double slot_iters, EstepStats& st) {
+  const int nvec = c->n, p = c->p, T = c->T;
+  // mandatory HBM traffic of one PCG iteration (the bytes a perfect implementation still moves): per live slot
+  // 20 passes over an n-vector (H p = K^-1 p + W p: 5; x, r updates: 6; preconditioner G(eps r + F S F^T G r): 6; p = z + beta p: 3),
+  // 4 over an r-vector, the curvature blocks (packed FP32 lower triangles, or FP64 full blocks); once per iteration the operators
+  // K^-1 (p T^2), F and F^T (T r each) and S (r^2).  Dense plan: P^-1 (n^2) instead of F / S.
+  const double npk = (double)(p * (p + 1) / 2);
+  // Two-kernel step (pcg_cg_a/b_kernel): 17 passes (A reads r, y and writes z, s; B reads z, s, p, q, x, r and writes p, q, x, r, t; the
+  // products read t and write y), 4 over an r-vector, the packed FP32 curvature; once per step F, F^T, S and the packed triangles of Gb
+  // (FP64) and Wb (FP32).  No K^-1 in the loop.
+  const double vecs = (sf.onek ? 17.0 : 20.0) * nvec * 8.0 + (c->plan_lowrank ? 4.0 * c->rtot * 8.0 : 0.0);
+  const double curv = (sf.fused && c->pcg_w32) ? (double)T * npk * 4.0 : (double)T * p * p * 8.0;
+  const double ops = sf.onek ? (2.0 * T * c->rtot + (double)c->rtot * c->rtot + 1.5 * T * npk) * 8.0
+                             : (double)p * T * T * 8.0 + (c->plan_lowrank ? (2.0 * T * c->rtot + (double)c->rtot * c->rtot) * 8.0 : (double)nvec * nvec * 8.0);
+  st.newton_bytes += slot_iters * (vecs + curv) + (double)nw.done_inner * ops;
+  // (bytes per entry of an n-vector and slot-step: FP64 form 136 = 17 passes; z, s, p, q, t / y in single precision 88; r and x too 68 -
+  //  A reads r 4, y 4, writes z 4, s 4; B reads z 4, s 4, x 4, r 4, p 4, q 4, writes p 4, q 4, x 4, r 4, t 4; the products read t 4, write y 4 -
+  //  plus, once per solve and slot, the widening of the step: 4 read, 8 written)
+  const double vec_b = sf.rx32 ? 68.0 : (sf.v32 ? 88.0 : 0.0);
+  st.newton_bytes_moved += slot_iters * ((sf.v32 ? vec_b * nvec + (c->plan_lowrank ? 4.0 * c->rtot * 8.0 : 0.0) : vecs) + curv) + (double)nw.done_inner * ops
+                           + ((sf.onek && sf.rx32) ? 12.0 * nvec * (double)nw.na : 0.0);
+  st.newton_bytes_survey += slot_iters * ((double)c->q * T + 8.0 * (2.0 * p * T + (double)T * p * p));
+}
+
+// the step's scalars of every slot to the host (decrement, largest entry, the quadratic's pieces, residual norms), the solve's iteration counts
+static int read_step(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, NewtonState& nw, EstepStats& st) {
+  const int nb = ch.nb, na = nw.na, nvec = c->n; const long long ld = c->ld;
+  CHK(prior_mv_all(c, nb, c->Dl, c->KD));
+  hipLaunchKernelGGL(dots3_kernel, dim3(na), dim3(256), 0, c->st, c->Xc, ld, c->KX, ld, c->Dl, ld, c->KD, ld, nvec, c->list_a, c->sc_qxx,
+                     c->sc_qdx, c->sc_qdd);
+  HIPC(hipGetLastError());
+  const size_t nB = (size_t)c->B;
+  std::vector<double> pack(7 * nB);
+  CHK(download(c, pack.data(), c->sc_pack, 7 * nB));
+  std::copy(pack.begin(), pack.begin() + nb, ch.dec.begin());
+  std::copy(pack.begin() + nB, pack.begin() + nB + nb, ch.smax.begin());
+  std::copy(pack.begin() + 2 * nB, pack.begin() + 2 * nB + nb, ch.qxx.begin());
+  std::copy(pack.begin() + 3 * nB, pack.begin() + 3 * nB + nb, ch.qdx.begin());
+  std::copy(pack.begin() + 4 * nB, pack.begin() + 4 * nB + nb, ch.qdd.begin());
+  std::copy(pack.begin() + 5 * nB, pack.begin() + 5 * nB + nb, nw.rr.begin());
+  std::copy(pack.begin() + 6 * nB, pack.begin() + 6 * nB + nb, nw.rr0.begin());
+  double slot_iters = (double)na * nw.done_inner;
+  if (nw.done_inner < 0) {                                   // (the download above synchronised the stream)
+    nw.done_inner = c->fused_ctl_host.iters;
+    slot_iters = (double)c->fused_ctl_host.slot_iters;
+    if (c->prof.on)                                       // algorithmic flops of the live-list products: per column x slot-iterations
+      for (const auto& lg : c->live_gemms) {
+        c->prof.flops[TAG_GEMM] += lg.second * slot_iters;
+        c->prof.shapes[lg.first].flops += lg.second * slot_iters;
+      }
+  }
+  st.n_pcg += slot_iters;
+  if (c->pcg_trace) {
+    // achieved residual ratios of the live slots: worst, median, and how many already met the target
+    std::vector<double> ratio;
+    for (int s : ch.active) ratio.push_back(nw.rr0[s] > 0.0 ? std::sqrt(nw.rr[s] / nw.rr0[s]) : 0.0);
+    std::sort(ratio.begin(), ratio.end());
+    int met = 0;
+    for (double v : ratio) met += (v <= nw.eta_target) ? 1 : 0;
+    std::fprintf(stderr, "pcg_trace: outer %d live %d inner %d eta_target %.2e achieved worst %.2e median %.2e best %.2e met %d\n", nw.outer, na, nw.done_inner,
+                 nw.eta_target, ratio.back(), ratio[ratio.size() / 2], ratio.front(), met);
+  }
+  account_bytes(c, sf, nw, slot_iters, st);
+  return 0;
+}
+
+// line search along the step, then the verdict per slot: settled, another outer iteration, or the per-trial fallback
+static int judge_steps(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, NewtonState& nw, EstepStats& st) {
+  const int nb = ch.nb, nvec = c->n;
+  std::vector<int> cand, next, failed;
+  for (int s : ch.active) {
+    if (!(ch.dec[s] > 0.0) || !std::isfinite(ch.dec[s]) || !std::isfinite(ch.smax[s])) continue;   // leave to the fallback
+    cand.push_back(s);
+  }
+  CHK(line_search(c, ch, sf, cand, &failed));
+  std::vector<char> bad(nb, 0);
+  for (int s : failed) bad[s] = 1;
+  std::vector<double> gnew;
+  if (sf.onek) {
+    // The inner solve ran on H~ = Kt^-1 + fl32(W): its residual says how well H~ delta = -g was solved, not how far the step took the
+    // TRUE gradient down.  Measure that: |g(x + delta)| / |g(x)| of the accepted full steps (the committed Gl + KX; rr0 = |g(x)|^2) enters
+    // the error prediction next to the inner ratio, so the stopping rule never rests on the model matrix.
+    std::vector<int> okl;
+    for (int s : cand) if (!bad[s]) okl.push_back(s);
+    gnew.assign(nb, 0.0);
+    if (!okl.empty()) {
+      CHK(upload_nosync(c, c->list_b, okl.data(), sizeof(int) * okl.size()));
+      hipLaunchKernelGGL(grad_norm2_kernel, dim3((unsigned)okl.size()), dim3(256), 0, c->st, c->Gl, c->KX, (long long)c->ld, nvec, c->list_b, c->sc_f);
+      CHK(download(c, gnew.data(), c->sc_f, nb));
+    }
+  }
+  for (int s : cand) {
+    if (bad[s]) continue;
+    // inexact Newton: the error after the step is ~ max(eta, |step|) * |step|, eta = achieved relative residual
+    double eta = nw.rr0[s] > 0.0 ? std::sqrt(nw.rr[s] / nw.rr0[s]) : 0.0;
+    if (sf.onek && ch.alpha[s] == 1.0 && nw.rr0[s] > 0.0) eta = std::max(eta, std::sqrt(gnew[s] / nw.rr0[s]));
+    const double step = ch.alpha[s] * ch.smax[s];
+    if (ch.alpha[s] == 1.0 && 10.0 * step * std::max(eta, step) < c->chord_xtol) { ch.stat[s] = 0; continue; }
+    nw.err_pred[s] = (ch.alpha[s] == 1.0) ? step * std::max(eta, step) : step;
+    next.push_back(s);
+  }
+  // slots with a non-descent direction or an exhausted search drop to the per-trial fallback
+  std::vector<int> fallback;
+  std::vector<char> in_cand(nb, 0);
+  for (int s : cand) in_cand[s] = 1;
+  for (int s : ch.active) if (!in_cand[s] || bad[s]) { fallback.push_back(s); if (bad[s]) st.n_fb_search += 1; else st.n_fb_dir += 1; }
+  ch.active.swap(next);
+  ch.leftovers.insert(ch.leftovers.end(), fallback.begin(), fallback.end());
+  return 0;
+}
+
+// ---- phase 1: inexact Newton, all slots in lockstep, PCG on H_r delta = -g preconditioned by ONE shared factor
+// (the mean-trial Hessian: cond(P^-1 H_r) stays below ~4, measured).  Every preconditioner application is two
+// multi-RHS triangular sweeps run as GEMMs over the slots; no per-trial factorisation in this phase.
+static int newton_shared(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, EstepStats& st) {
+  PhaseRange range_newton("pgpfa.newton_pcg");
+  CHK(shared_factor(c, ch.nb));
+  st.n_shared += 1;
+  NewtonState nw(ch.nb);
+  for (nw.outer = 0; nw.outer < c->pcg_outer_max && !ch.active.empty(); ++nw.outer) {
+    nw.eta_target = c->pcg_eta0;
+    for (int s : ch.active) nw.eta_target = std::min(nw.eta_target, forcing_term(c, nw.err_pred[s]));
+    nw.na = (int)ch.active.size();
+    CHK(inner_solve(c, ch, sf, nw, st));
+    CHK(read_step(c, ch, sf, nw, st));
+    CHK(judge_steps(c, ch, sf, nw, st));
+    st.max_it_seen = std::max(st.max_it_seen, nw.outer + 1);
+  }
+  // anything still active after the outer cap also goes to the fallback
+  st.n_fb_cap += (double)ch.active.size();
+  ch.leftovers.insert(ch.leftovers.end(), ch.active.begin(), ch.active.end());
+  ch.active = ch.leftovers;
+  std::sort(ch.active.begin(), ch.active.end());
+  return 0;
+}
+
+// ---- phase 1b (fallback, and the only path when shared_pcg is off or the chunk is tiny): per-trial Newton with
+// factor reuse.  A slot factors H at its current point only when it has no factor yet or its chord steps (steps
+// with the stale factor, still descent directions since that factor is SPD) contract too slowly; otherwise the
+// resident factor is reused: one HBM-bound solve instead of n^3/3 flops.
+static int newton_per_trial(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, EstepStats& st) {
+  const int nb = ch.nb, nvec = c->n; const long long ld = c->ld;
+  std::vector<int>& active = ch.active;
+  if (c->plan_lowrank && !active.empty()) {
+    // the per-trial fallback needs full-size factor slabs: leave these trials to the dense retry pass of the caller
+    for (int s : active) ch.stat[s] = 4;
+    active.clear();
+  }
+  std::vector<char> has_factor(nb, 0), fresh(nb, 0), refactor(nb, 0);
+  std::vector<double> prev_step(nb, 0.0);
+  std::vector<int> n_chord(nb, 0);
+  for (int iter = 0; iter < c->max_iter && !active.empty(); ++iter) {
+    const int na = (int)active.size();
+    std::vector<int> need;
+    for (int s : active) {
+      if (!has_factor[s] || refactor[s] || !c->chord) need.push_back(s);
+      fresh[s] = 0;
+    }
+    if (!need.empty()) {
+      CHK(upload_list(c, c->list_a, need));
+      CHK(assemble(c, c->list_a, (int)need.size()));
+      CHK(factor(c, c->ws, c->list_a, (int)need.size()));
+      st.n_fact += (double)need.size();
+      for (int s : need) { has_factor[s] = 1; fresh[s] = 1; refactor[s] = 0; n_chord[s] = 0; ch.its[s] += 1; }
+    }
+    st.n_solve += na;
+    CHK(upload_list(c, c->list_a, active));
+    hipLaunchKernelGGL(grad_total_kernel, dim3((nvec + 255) / 256, na), dim3(256), 0, c->st, c->Gl, ld, c->KX, ld, c->Gt, ld, nvec, c->list_a);
+    prof_begin(c, TAG_SOLVE, 2.0 * na * (double)c->npad * c->npad);
+    hipLaunchKernelGGL(chol_solve_kernel, dim3(na), dim3(256), 0, c->st, c->ws.H, c->ws.sH, c->ld, c->npad, c->ws.Dinv, c->ws.sD, c->Gt, c->Dl,
+                       ld, c->list_a, c->sc_dec, c->sc_smax, nvec);
+    prof_end(c);
+    CHK(prior_mv(c, c->list_a, na, c->Dl, c->KD));
+    hipLaunchKernelGGL(dots3_kernel, dim3(na), dim3(256), 0, c->st, c->Xc, ld, c->KX, ld, c->Dl, ld, c->KD, ld, nvec, c->list_a, c->sc_qxx,
+                       c->sc_qdx, c->sc_qdd);
+    HIPC(hipGetLastError());
+    CHK(download(c, ch.dec.data(), c->sc_dec, nb));
+    CHK(download(c, ch.smax.data(), c->sc_smax, nb));
+    CHK(download(c, ch.qxx.data(), c->sc_qxx, nb));
+    CHK(download(c, ch.qdx.data(), c->sc_qdx, nb));
+    CHK(download(c, ch.qdd.data(), c->sc_qdd, nb));
+    CHK(dl_enqueue(c, ch.info.data(), c->ws.info, sizeof(int) * nb));
+    CHK(dl_flush(c));
+
+    std::vector<int> cand, failed;
+    for (int s : active) {
+      if (ch.info[s] != 0 || !std::isfinite(ch.dec[s])) { ch.stat[s] = 3; continue; }
+      cand.push_back(s);
+    }
+    CHK(line_search(c, ch, sf, cand, &failed));
+    for (int s : failed) ch.stat[s] = 2;   // line search exhausted
+    std::vector<int> next;
+    for (int s : active) {
+      if (ch.stat[s] == 2 || ch.stat[s] == 3) continue;
+      const double step = ch.alpha[s] * ch.smax[s];
+      if (fresh[s]) {
+        // true Newton step: quadratic convergence, the error after the step is ~step^2
+        if (step < c->xtol) { ch.stat[s] = 0; continue; }
+        if (step > c->chord_max_step) refactor[s] = 1;      // still far from the mode: keep factoring
+      } else {
+        // chord step: linear convergence with ratio rho, the error after the step is ~rho/(1-rho)*step
+        const double rho = prev_step[s] > 0.0 ? step / prev_step[s] : 1.0;
+        n_chord[s] += 1;
+        if (step < c->chord_xtol && rho < 0.5) { ch.stat[s] = 0; continue; }
+        if (rho > c->chord_rho || n_chord[s] >= c->chord_max) refactor[s] = 1;
+      }
+      prev_step[s] = step;
+      next.push_back(s);
+    }
+    active.swap(next);
+    st.max_it_seen = std::max(st.max_it_seen, iter + 1);
+  }
+  return 0;
+}
+
+// the mode search of one pass over the chunk from the points in Xc: evaluation there (first is true in pass 0), the slots still open, phases 1 and 1b
+static int mode_search(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, const VarState* vs, bool first, EstepStats& st) {
+  CHK(eval_start_guarded(c, ch, first && !vs && ch.any_warm && c->start_guard, st));
+  ch.active.clear();
+  for (int s = 0; s < ch.nb; ++s) {
+    if (first) ch.its[s] = 0;
+    if (vs && vs->stat[s] != 1) continue;         // (this slot's fixed point is settled)
+    ch.active.push_back(s);
+    ch.stat[s] = 1;
+  }
+  ch.leftovers.clear();
+  ch.w32_ok.assign(ch.nb, 0);                     // (the evaluation has rewritten W)
+  if (c->shared_pcg && (ch.nb >= c->shared_min || c->plan_lowrank)) CHK(newton_shared(c, ch, sf, st));
+  return newton_per_trial(c, ch, sf, st);
+}
+
+// ---- variational fixed point, pass vo: rates at the modes, their covariance blocks, new offsets; *any_open: some slot needs another pass
+// A mode search that did not settle (iteration cap 1, line search exhausted 2, factor failure 3 / 4) hands ITS trial back - status 2: the
+// caller finishes it with L-BFGS from the lambda of the point the search reached - and the other slots go on.  Only a non-finite state
+// (checked below on the offsets of every slot still open or handed back in this pass) fails the call.
+static int var_pass(pgpfa_ctx* c, Chunk& ch, const VarJob* var, VarState& vs, int vo, bool* any_open) {
+  const int nb = ch.nb;
+  std::vector<char> handed(nb, 0);
+  for (int s = 0; s < nb; ++s)
+    if (vs.stat[s] == 1 && ch.stat[s] != 0) { vs.stat[s] = 2; handed[s] = 1; vs.outer[s] = vo + 1; }
+  c->lam_out_active = true;
+  CHK(poisson(c, c->ident, nb, c->Xc, c->Glt, c->Wt, c->sc_f, 0));        // lambda = exp(C m + d + offset) -> c->lamd
+  c->lam_out_active = false;
+  if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }   // (c->W: curvature at the modes = C^T diag(lambda) C)
+  else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
+  CHK(dl_enqueue(c, ch.info.data(), c->ws.info, sizeof(int) * nb));
+  CHK(dl_flush(c));
+  for (int s = 0; s < nb; ++s)
+    if (ch.info[s] != 0) { var_superseded(c, ch.tos); return fail("variational fixed point: posterior precision of trial %d not positive definite", ch.tos[s]); }
+  CHK(var_offsets(c, nb, c->dgrad));
+  // change of the offsets first (step 0: nothing moves), the update afterwards and only for the slots that go on - a slot that settles
+  // keeps the offsets its lambda was computed with, so that (lambda, mode, offsets) stay one consistent triple
+  std::vector<double> zero(nb, 0.0);
+  CHK(upload_nosync(c, c->sc_alpha, zero.data(), sizeof(double) * nb));
+  hipLaunchKernelGGL(var_update_kernel, dim3(nb), dim3(256), 0, c->st, c->voff, (const double*)c->dgrad, vs.mlam, (const double*)c->sc_alpha, c->sc_f);
+  CHK(download(c, vs.delta.data(), c->sc_f, nb));
+  *any_open = false;
+  for (int s = 0; s < nb; ++s) {
+    if ((vs.stat[s] == 1 || handed[s]) && !std::isfinite(vs.delta[s])) { var_superseded(c, ch.tos); return fail("variational fixed point: non-finite offsets for trial %d", ch.tos[s]); }
+    if (vs.stat[s] != 1) continue;
+    vs.outer[s] = vo + 1;
+    if (vs.delta[s] <= var->tol) { vs.stat[s] = 0; continue; }
+    // the map contracts by about half the largest posterior variance of a log rate per pass; a pass that does not shrink the change
+    // halves the step, three such passes give the trial back to the caller (status 2: the L-BFGS driver takes it from this lambda)
+    if (vs.delta_prev[s] >= 0.0 && vs.delta[s] > 0.7 * vs.delta_prev[s]) { vs.damp[s] *= 0.5; if (++vs.slow[s] >= 3) { vs.stat[s] = 2; continue; } }
+    vs.delta_prev[s] = vs.delta[s];
+    if (vo + 1 >= var->max_outer) continue;       // (stays 1: iteration cap)
+    *any_open = true;
+  }
+  if (!*any_open) return 0;
+  std::vector<double> step(nb, 0.0);
+  for (int s = 0; s < nb; ++s) step[s] = (vs.stat[s] == 1) ? vs.damp[s] : 0.0;
+  CHK(upload_nosync(c, c->sc_alpha, step.data(), sizeof(double) * nb));
+  hipLaunchKernelGGL(var_update_kernel, dim3(nb), dim3(256), 0, c->st, c->voff, (const double*)c->dgrad, vs.mlam, (const double*)c->sc_alpha, c->sc_f);
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+// the chunk's counts and statuses into the caller's arrays
+static void report_slots(const Chunk& ch, int32_t* iters, int32_t* status) {
+  for (int s = 0; s < ch.nb; ++s) {
+    if (iters) iters[ch.c0 + s] = ch.its[s];
+    if (status) status[ch.c0 + s] = ch.stat[s];
+  }
+}
+
+// end of the fixed point: optimum out - rho = log lambda, the dual cost there (inference.py:196-213), statuses
+static int var_finish(pgpfa_ctx* c, Chunk& ch, const VarJob* var, const VarState& vs, int32_t* iters, int32_t* status, EstepStats& st) {
+  const int nb = ch.nb, c0 = ch.c0; const size_t mlam = vs.mlam;
+  c->var_active = false;
+  CHK(dual_eval_slots(c, nb, ch.tos, false, var->fopt + c0, false));
+  // the optimum stays on the device for pgpfa_dual_finalize(lam = NULL) and for blocks rebuilt on demand
+  if (!c->lam_keep) {
+    const size_t bytes = (size_t)c->R * mlam * sizeof(double);
+    if (hipMalloc((void**)&c->lam_keep, bytes) != hipSuccess) { (void)hipGetLastError(); c->lam_keep = nullptr; return fail("hipMalloc(%zu bytes) for the resident dual variables failed", bytes); }
+    c->bytes += bytes;
+  }
+  for (int s = 0; s < nb; ++s) {
+    CHK(copy_dev(c, c->lam_keep + (size_t)ch.tos[s] * mlam, c->lamd + (size_t)s * mlam, mlam * sizeof(double)));
+    c->lam_resident[ch.tos[s]] = 1; c->lam_valid[ch.tos[s]] = 1;
+    // (lam_keep also feeds the blocks rebuilt on demand of a dual posterior: whatever posterior the trial had is superseded until
+    // pgpfa_dual_finalize has run on the new optimum)
+    c->trial_dual[ch.tos[s]] = 0; c->trial_snap[ch.tos[s]] = -1; c->vsmgp_ok[ch.tos[s]] = 0;
+  }
+  if (var->lam_out) CHK(download(c, var->lam_out + (size_t)c0 * mlam, c->lamd, (size_t)nb * mlam));
+  if (var->rho) {
+    hipLaunchKernelGGL(var_log_kernel, dim3(2048), dim3(256), 0, c->st, (const double*)c->lamd, c->dgrad, (size_t)nb * mlam);
+    CHK(download(c, var->rho + (size_t)c0 * mlam, c->dgrad, (size_t)nb * mlam));
+  }
+  for (int s = 0; s < nb; ++s) {
+    if (var->outer) var->outer[c0 + s] = vs.outer[s];
+    var->vstatus[c0 + s] = vs.stat[s];
+  }
+  report_slots(ch, iters, status);
+  st.n_fact += nb;
+  return 0;
+}
+
+// end of a leave-one-out chunk: prediction of the held-out neurons from the modes in Xc (Xt and sc_f are free scratch here)
+static int loo_finish(pgpfa_ctx* c, Chunk& ch, const LooJob* loo, int32_t* iters, int32_t* status) {
+  const int nb = ch.nb, c0 = ch.c0, T = c->T; const long long ld = c->ld;
+  hipLaunchKernelGGL(loo_predict_kernel, dim3(nb), dim3(256), 0, c->st, c->Xc, ld, c->C, c->d, c->Y, c->Yhi, c->trial_of_slot, c->mask_of_slot,
+                     c->q, c->p, T, c->Xt, ld, c->sc_f);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpy2DAsync(loo->y_pred + (size_t)c0 * T, (size_t)T * sizeof(double), c->Xt, (size_t)ld * sizeof(double), (size_t)T * sizeof(double),
+                        nb, hipMemcpyDeviceToHost, c->st));
+  CHK(download(c, loo->err + c0, c->sc_f, nb));
+  HIPC(hipStreamSynchronize(c->st));
+  report_slots(ch, iters, status);
+  return 0;
+}
+
+// end of a Laplace chunk: posterior covariance blocks at the modes, the modes into the resident arrays, statuses; adds the chunk's objective to *total
+static int laplace_finish(pgpfa_ctx* c, Chunk& ch, double* total, int32_t* iters, int32_t* status, EstepStats& st) {
+  const int nb = ch.nb, nvec = c->n;
+  {
+    const bool sum_only = c->plan_lowrank && !c->keep_trial_vsmgp;
+    PhaseRange range_cov("pgpfa.covariance_blocks");
+    CHK(posterior_blocks(c, nb, 1.0, true, sum_only));
+    for (int t : ch.tos) c->vsmgp_ok[t] = sum_only ? 0 : 1;
+  }
+  st.n_fact += nb;
+  for (int s = 0; s < nb; ++s) ch.its[s] += 1;
+  // the mode a trial had before this E-step becomes its extrapolation base (once per E-step: a dense retry pass
+  // of the same E-step must not overwrite it with its own unfinished start point)
+  std::vector<int> rot(nb, 0);
+  for (int s = 0; s < nb; ++s) {
+    const int tr_ = ch.tos[s];
+    if (c->mode_serial[tr_] != c->estep_serial) {
+      rot[s] = 1;
+      c->prev_serial[tr_] = c->mode_serial[tr_];
+      c->mode_serial[tr_] = c->estep_serial;
+    }
+  }
+  CHK(upload_list(c, c->list_a, rot));
+  hipLaunchKernelGGL(scatter_rotate_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xc, (long long)c->ld, nvec, c->Xmode, c->Xprev,
+                     c->trial_of_slot, c->list_a);
+  CHK(dl_enqueue(c, ch.info.data(), c->ws.info, sizeof(int) * nb));
+  CHK(dl_flush(c));
+  HIPC(hipGetLastError());
+  for (int s = 0; s < nb; ++s) {
+    if (ch.info[s] != 0 && ch.stat[s] == 0) ch.stat[s] = 3;
+    *total += ch.f[s];
+  }
+  report_slots(ch, iters, status);
+  return 0;
+}
+
+// positions of the items the low-rank plan could not finish (status 4: its shared-preconditioner Newton gave up on them and the per-trial
+// fallback needs full-size slabs); the callers redo them under the dense plan
+static std::vector<int> unfinished_lowrank(const std::vector<int32_t>& st) {
+  std::vector<int> pos;
+  for (int i = 0; i < (int)st.size(); ++i) if (st[i] == 4) pos.push_back(i);
+  return pos;
+}
+
+}  // namespace
+
+int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, double* obj_sum, int32_t* iters, int32_t* status,
+               const LooJob* loo, const VarJob* var) {
+  PhaseRange range_estep(var ? "pgpfa.dual_fixed_point" : loo ? "pgpfa.loo_mode_search" : "pgpfa.estep_laplace");
+  c->want_slots = std::max(c->want_slots, std::min((int)tr.v.size(), c->R));
+  CHK(ready_estep(c, allow_lr));
+  MaskGuard mask_guard{c};
+  if (var) CHK(ensure_lambda(c));
+  const int N = (int)tr.v.size();
+  EstepStats st;
+  Chunk ch(c->B);
+  double total = 0.0;
+  for (int c0 = 0; c0 < N; c0 += c->B) {
+    CHK(bind_chunk(c, ch, tr, c0, loo));
+    VarState vs(ch.nb, (size_t)c->q * c->T);
+    if (var) CHK(start_variational(c, ch, var, vs));
+    else CHK(start_laplace(c, ch, warm_start));
+    const SolveForm sf = solve_form(c, ch.nb);
+    for (int vo = 0;; ++vo) {                     // (one pass for the Laplace E-step; the variational fixed point comes back here with new offsets)
+      CHK(mode_search(c, ch, sf, var ? &vs : nullptr, vo == 0, st));
+      if (!var) break;
+      bool any_open = false;
+      CHK(var_pass(c, ch, var, vs, vo, &any_open));
+      if (!any_open) break;
+    }
+    if (var) CHK(var_finish(c, ch, var, vs, iters, status, st));
+    else if (loo) CHK(loo_finish(c, ch, loo, iters, status));
+    else CHK(laplace_finish(c, ch, &total, iters, status, st));
+  }
+  if (obj_sum) *obj_sum = total;
+  st.publish(c);
   return 0;
 }
 
@@ -1285,12 +1429,10 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
   }
   CHK(estep_impl(c, tr, warm_start, true, &obj, it1.data(), st1.data()));
   c->info["last_retry_ms"] = 0.0;
-  // trials the low-rank plan could not finish (its shared-preconditioner Newton gave up on them and the per-trial
-  // fallback needs full-size slabs) are redone under the dense plan, warm-started from where they stopped
+  // trials the low-rank plan could not finish are redone under the dense plan, warm-started from where they stopped
   Trials retry;
-  std::vector<int> pos;
-  for (int i = 0; i < N; ++i)
-    if (st1[i] == 4) { retry.v.push_back(tr.v[i]); pos.push_back(i); }
+  const std::vector<int> pos = unfinished_lowrank(st1);
+  for (int i : pos) retry.v.push_back(tr.v[i]);
   if (!retry.v.empty()) {
     // their partial objective is replaced: recompute the total from scratch for them
     std::vector<int32_t> it2(retry.v.size()), st2(retry.v.size());
@@ -1307,7 +1449,7 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
       // the dense plan of this pass is sized for the retry list, not for the largest list the context has seen (a plan for 1024 dense slabs maps and
       // clears > 200 GB: seconds); the next E-step re-partitions the arena for its own plan
       const auto t_retry = std::chrono::steady_clock::now();
-      struct WantGuard { pgpfa_ctx* c; int keep; ~WantGuard() { c->want_slots = keep; } } want_guard{c, c->want_slots};
+      WantGuard want_guard{c, c->want_slots};
       c->want_slots = 0;
       CHK(estep_impl(c, retry, 1, false, &obj_redo, it2.data(), st2.data()));
       c->info["last_retry_ms"] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_retry).count();
@@ -1347,16 +1489,16 @@ int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, d
   CHK(estep_impl(c, items, 0, true, nullptr, it.data(), st.data(), &job));
   // items the low-rank plan could not finish are redone under the dense plan (as in pgpfa_estep_laplace)
   Trials redo;
-  std::vector<int> redo_mask, pos;
-  for (int i = 0; i < N; ++i)
-    if (st[i] == 4) { redo.v.push_back(items.v[i]); redo_mask.push_back(mask[i]); pos.push_back(i); }
+  std::vector<int> redo_mask;
+  const std::vector<int> pos = unfinished_lowrank(st);
+  for (int i : pos) { redo.v.push_back(items.v[i]); redo_mask.push_back(mask[i]); }
   if (!redo.v.empty()) {
     const int M = (int)redo.v.size();
     std::vector<double> yp2((size_t)M * T), err2(M);
     std::vector<int32_t> st2(M), it2(M);
     LooJob job2{&redo_mask, yp2.data(), err2.data()};
     {
-      struct WantGuard { pgpfa_ctx* c; int keep; ~WantGuard() { c->want_slots = keep; } } want_guard{c, c->want_slots};
+      WantGuard want_guard{c, c->want_slots};
       c->want_slots = 0;                    // (dense plan for the redo list only: see pgpfa_estep_laplace)
       CHK(estep_impl(c, redo, 0, false, nullptr, it2.data(), st2.data(), &job2));
     }

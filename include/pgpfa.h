@@ -72,6 +72,10 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * single-precision factorisation meets a non-positive pivot is redone in FP64 as a whole - info "last_cov_f32_fallbacks" - never an error.  The
  * dense engine ignores the option and "dual_f32" keeps its meaning for the dual's evaluations.  Measured error of the covariance outputs
  * against a dense FP64 inverse: docs/history/laplace_f32.md),
+ * "laplace_evidence" (0 - the default: nothing is launched or allocated for it, every output keeps its bits; 1: pgpfa_estep_laplace also produces the
+ * Laplace approximation of every processed trial's log evidence, see pgpfa_get_log_evidence - one reduction kernel per chunk behind the covariance
+ * phase's factorisation, read back with the pivots, no further host wait; any other value fails.  With "laplace_f32" != 0 pgpfa_estep_laplace fails:
+ * the log-determinant is taken from the FP64 factor only),
  * "pcg_fused" (1: inner PCG iterations without host round trips, pcg.h), "pcg_w32" (1: packed FP32 curvature blocks in the PCG
  * Hessian-vector product), "cd_mfma" (1: (C,d) sweep on the matrix cores, mstep.h), "cd_hess_mfma" (1: the Newton pass
  * of the (C,d) M-step - cost, gradient, per-neuron Hessians - on the matrix cores up to 10 latents; 0: the vector kernel), "vsm_mfma" (1: beyond 10 latents the per-bin
@@ -166,6 +170,8 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * "arena_bytes", "last_split_cov", "last_yt_mix_fused" (1 when the last covariance pass ran product and mixing as one kernel), "last_cov_f32" (1 when the last covariance pass ran the
  * single-precision r x r phase of "laplace_f32", else 0: set by every pass, as "last_split_cov"), "last_cov_f32_fallbacks" (chunks of the last
  * pgpfa_estep_laplace call redone in FP64 after a non-positive pivot of the single-precision factorisation; reset at the start of that call),
+ * "last_log_evidence_sum" (sum of the Laplace log evidence, pgpfa_get_log_evidence, over the trials of the last pgpfa_estep_laplace call; 0 when
+ * "laplace_evidence" was off),
  * "last_eps_wt_norm", "last_eps_wt_rms", "last_newton_solve_ms", "last_newton_solve_bytes",
  * "last_newton_solve_bytes_moved" (what the step's kernels really move: with "pcg_vec32" five of its vectors are single precision),
  * "last_newton_solve_bytes_survey" (the same slot-iterations priced at q T + 8 (2 p T + T p^2) bytes each: SURVEY 8(d)'s B_E per pass per trial),
@@ -227,6 +233,15 @@ int pgpfa_get_post_vsm(pgpfa_ctx* ctx, int n, const int32_t* idx, double* out /*
 int pgpfa_get_post_vsmgp(pgpfa_ctx* ctx, int n, const int32_t* idx, double* out /* [n][T][T][p] */);
 /* post_cov of one trial, recomputed on demand (inference.py:130-131,161-162). */
 int pgpfa_get_post_cov(pgpfa_ctx* ctx, int trial, double* out /* [pT][pT] */);
+/* Laplace approximation of the log evidence of the listed trials (idx NULL: all), one double each:
+ *   log Z_r = -f_r(x*_r) - 1/2 (log det H_r(x*_r) + sum_k log det K_k)
+ * with f_r = negLogPosteriorUnNorm (inference.py:12-32), H_r its Hessian (inference.py:50-65) and x*_r the mode the E-step returned
+ * (post_cov = H_r^-1, inference.py:130-131).  Normalisation: the reference's - f_r drops sum log y!, so log Z_r does too; the 2 pi factors of the
+ * prior and of the Laplace integral cancel.  Padded bins of a trial shorter than T (pgpfa_set_trial_lengths) change nothing: the value is that of
+ * the trial's own T_r-bin model.  Produced by pgpfa_estep_laplace while option "laplace_evidence" is 1, under both covariance engines; a
+ * trial's value stays valid as long as the posterior it belongs to is the resident one - a later E-step over the trial with the option off,
+ * pgpfa_dual_finalize, pgpfa_set_posterior, pgpfa_set_modes or new counts supersede it.  Fails, naming the first such trial, when a listed trial has no valid value. */
+int pgpfa_get_log_evidence(pgpfa_ctx* ctx, int n, const int32_t* idx, double* out /* [n] */);
 /* Upload E-step results produced elsewhere (e.g. a reference infRes dict) for the M-step. */
 int pgpfa_set_posterior(pgpfa_ctx* ctx, int n, const int32_t* idx, const double* post_mean,
                         const double* post_vsm, const double* post_vsmgp /* [n][T][T][p] */);

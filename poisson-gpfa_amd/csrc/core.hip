@@ -151,6 +151,7 @@ int free_workspace(pgpfa_ctx* c) {
   while (c->allocs.size() > c->ws_mark) { hipFree(c->allocs.back()); c->allocs.pop_back(); }
   c->B = 0;
   c->lamd = c->dgrad = c->dpart = c->ldet_buf = c->voff = nullptr;
+  c->evid_ld = nullptr;
   c->dual_scr = nullptr;
   c->commbuf = nullptr; c->commbuf_len = 0;
   c->mt_dirty = false;
@@ -915,6 +916,7 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   rc |= dmalloc(c, &c->Xmode, (size_t)R * c->n + 64, true);
   rc |= dmalloc(c, &c->Xprev, (size_t)R * c->n + 64, true);
   c->mode_serial.assign(R, -10); c->prev_serial.assign(R, -10);
+  c->info["last_log_evidence_sum"] = 0.0;
   rc |= dmalloc(c, &c->vsm, (size_t)R * T * p * p + 2048, true);
   // c->vsmgp (R*p blocks of T x T: 20 GB at config 3) is allocated on first use: the low-rank engine's default
   // sum-only output never touches it
@@ -1086,6 +1088,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "dual_lowrank") c->dual_lowrank = (v != 0.0);
   else if (k == "dual_f32") c->dual_f32 = (int)v;
   else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
+  else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
   else if (k == "dual_gemm") c->dual_gemm = (v != 0.0);

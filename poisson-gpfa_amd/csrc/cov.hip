@@ -89,13 +89,27 @@ int ensure_vsmgp_buffer(pgpfa_ctx* c) {
   return 0;
 }
 
-static int posterior_blocks_dense(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp) {
+// Buffers of the Laplace log evidence (option laplace_evidence): the per-bin log-dets of the low-rank engine (shared with the dual path, which
+// allocates it in ensure_lambda) and the per-slot result.  Workspace allocations: a re-plan frees them with the rest.
+int ensure_evidence_buffers(pgpfa_ctx* c) {
+  if (!c->ldet_buf) CHK(dmalloc(c, &c->ldet_buf, (size_t)c->B * c->T + 16));
+  if (!c->evid_ld) CHK(dmalloc(c, &c->evid_ld, (size_t)c->B));
+  return 0;
+}
+
+static int posterior_blocks_dense(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, double* ld_dev) {
   const int T = c->T, p = c->p;
   c->info["last_cov_f32"] = 0.0;                             // (option laplace_f32 is the low-rank engine's)
   CHK(ensure_mt_clean(c));
   c->last_cov_lowrank = false;
   CHK(assemble(c, c->ident, nb, diag_scale));
   CHK(factor(c, c->ws, c->ident, nb));
+  // log det H + sum_k log det K_k of the log evidence: from the factor, before the staging of post_vsmGP reuses its slab
+  if (ld_dev) {
+    double ldk = 0.0;
+    for (double v : c->logdetK) ldk += v;
+    hipLaunchKernelGGL(evidence_logdet_kernel, dim3(nb), dim3(256), 0, c->st, (const double*)nullptr, 0, c->ws.H, (long long)c->ws.sH, c->ld, c->npad, ldk, ld_dev);
+  }
   CHK(inverse_t(c, c->ws, c->ident, nb));
   if (want_vsmgp) {
     CHK(ensure_vsmgp_buffer(c));
@@ -327,14 +341,16 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
 // logdet_out (optional, host, nb entries): log det of the posterior precision K^-1 + scatter(W) of every slot,
 //   = -sum_k log det K_k + sum_t log det(I + eps W_t) + log det(I + F^T Wt F)   (Sylvester; K_k = eps I + F_k F_k^T)
 // (allow_lap32 = false: the FP64 pass that redoes a chunk whose single-precision factorisation failed under option laplace_f32)
-static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, bool allow_lap32) {
+// ld_dev (optional, device, nb entries; the Laplace log evidence): log det of the posterior precision + sum_k log det K_k = the last two terms above,
+//   reduced per slot by one kernel behind the factorisation; nothing is read back here.  FP64 factor only: the E-step refuses it under laplace_f32.
+static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, bool allow_lap32, double* ld_dev) {
   const int T = c->T, p = c->p, Tp = c->Tp, pp = p * p;
   const int rpad = c->rpad;
   const int ract = round_up(c->rtot, 16);          // columns of Yt that are not identically zero (rpad rounds to 128 for the factor)
   const long long sW = (long long)T * pp;
   c->last_cov_lowrank = true;
   // a. per-bin blocks G = (I + eps W)^-1, Wt = W G
-  CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, logdet_out ? c->ldet_buf : nullptr));
+  CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, (logdet_out || ld_dev) ? c->ldet_buf : nullptr));
   // sum-only accumulation by the split form (split.h)?  Decided by the relative size of the mixing correction of this chunk,
   // max_t eps ||Wt_t||_inf, measured here and read back just before the mixing pass (info key "last_eps_wt_norm")
   // (want_vsmgp passes run the FP64 engine whatever dual_f32 says - it only concerns the dual's evaluations - and under laplace_f32 everything the
@@ -415,6 +431,10 @@ static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, 
   } else {
     CHK(factor(c, lw, c->ident, nb));
   }
+  if (ld_dev) {
+    if (f32) return fail("internal: log evidence requested from a single-precision factor");
+    hipLaunchKernelGGL(evidence_logdet_kernel, dim3(nb), dim3(256), 0, c->st, (const double*)c->ldet_buf, T, lw.H, (long long)lw.sH, rpad, rpad, 0.0, ld_dev);
+  }
   if (logdet_out) {
     std::vector<double> a(nb), b2(nb);
     hipLaunchKernelGGL(sum_rows_kernel, dim3(nb), dim3(256), 0, c->st, c->ldet_buf, T, c->sc_f);
@@ -489,7 +509,7 @@ static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, 
     CHK(dl_flush(c));
     if (std::any_of(pivot.begin(), pivot.end(), [](int v) { return v != 0; })) {
       c->info["last_cov_f32_fallbacks"] += 1.0;
-      return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, false);
+      return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, false, ld_dev);
     }
   } else {
   // L^-T's slab holds whatever the last use left (another rank layout, the factor of a dense pass): clear what will be read and not written - all of it,
@@ -627,16 +647,16 @@ static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, 
   return 0;
 }
 
-int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out) {
-  return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, true);
+int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, double* ld_dev) {
+  return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, true, ld_dev);
 }
 
-int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate) {
+int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate, double* ld_dev) {
   if (c->plan_lowrank) {
     if (diag_scale != 1.0) return fail("internal: jittered covariance requested under the low-rank workspace plan");
-    return posterior_blocks_lowrank(c, nb, want_vsmgp, accumulate);
+    return posterior_blocks_lowrank(c, nb, want_vsmgp, accumulate, nullptr, ld_dev);
   }
-  return posterior_blocks_dense(c, nb, diag_scale, want_vsmgp);
+  return posterior_blocks_dense(c, nb, diag_scale, want_vsmgp, ld_dev);
 }
 
 

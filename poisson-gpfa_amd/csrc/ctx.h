@@ -146,6 +146,14 @@ struct pgpfa_ctx {
   float* Flr32 = nullptr; bool flr32_valid = false;   // single-precision copy of the low-rank factors
   int laplace_f32 = 0;                          // option laplace_f32: the same single-precision r x r phase for the want_vsmgp passes of the low-rank engine (Laplace E-step, blocks
                                                 // rebuilt on demand); everything behind L^-T stays FP64 (cov.hip).  1: B assembled in FP32, 2: assembled in FP64 and rounded once
+  // Laplace log evidence (option laplace_evidence): log Z_r = -f_r(x*_r) - 1/2 (log det H_r(x*_r) + sum_k log det K_k) of every trial the Laplace E-step
+  // processes.  The log-determinants are reduced on the device (evidence_logdet_kernel, one entry per slot in evid_ld) right behind the covariance
+  // phase's factorisation and come back with the read-back laplace_finish already does.  A trial's value belongs to the posterior of the E-step
+  // that wrote it: it is valid while evid_serial equals the trial's mode_serial.
+  int laplace_evidence = 0;
+  double* evid_ld = nullptr;                     // device [B] (workspace allocation, made on first use)
+  std::vector<double> log_evidence;              // [R]
+  std::vector<int> evid_serial;                  // [R] estep_serial of the E-step that wrote log_evidence (-1: none)
   bool keep_trial_vsmgp = false;
   bool pacc_used = false, pacc_valid = false;
   std::vector<char> vsmgp_ok;                    // per trial: c->vsmgp holds the blocks of the resident posterior
@@ -451,8 +459,10 @@ int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, do
 // cov.hip: posterior covariance blocks (dense and low-rank engines), blocks rebuilt on demand
 int ensure_mt_clean(pgpfa_ctx* c);
 int ensure_vsmgp_buffer(pgpfa_ctx* c);
-int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out = nullptr);
-int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate = false);
+// (ld_dev, optional, device, nb entries: log det of every slot's posterior precision + sum_k log det K_k, written in stream order - no host wait)
+int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out = nullptr, double* ld_dev = nullptr);
+int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate = false, double* ld_dev = nullptr);
+int ensure_evidence_buffers(pgpfa_ctx* c);
 int post_vsm_from_mt(pgpfa_ctx* c, int nslots);        // post_vsm[t] of the first nslots slots from their dense L^-T slabs
 int ensure_trial_vsmgp(pgpfa_ctx* c, const std::vector<int>& trials);
 // dual.hip

@@ -14,7 +14,7 @@ int ensure_lambda(pgpfa_ctx* c) {
   CHK(dmalloc(c, &c->dgrad, (size_t)c->B * c->q * c->T + lam_slack, true));
   CHK(dmalloc(c, &c->voff, (size_t)c->B * c->q * c->T + lam_slack, true));
   CHK(dmalloc(c, &c->dpart, (size_t)c->B * ((c->T + 63) / 64) * 2 + 16));
-  CHK(dmalloc(c, &c->ldet_buf, (size_t)c->B * c->T + 16));
+  if (!c->ldet_buf) CHK(dmalloc(c, &c->ldet_buf, (size_t)c->B * c->T + 16));      // (the Laplace log evidence may have made it: ensure_evidence_buffers)
   c->dual_sscr = (long long)c->T * std::max(c->dual_npd, c->p * c->p);
   CHK(dmalloc(c, &c->dual_scr, (size_t)c->B * c->dual_sscr + (size_t)256 * c->T + 4096, true));
   return 0;

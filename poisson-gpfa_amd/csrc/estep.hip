@@ -1317,10 +1317,14 @@ static int loo_finish(pgpfa_ctx* c, Chunk& ch, const LooJob* loo, int32_t* iters
 // end of a Laplace chunk: posterior covariance blocks at the modes, the modes into the resident arrays, statuses; adds the chunk's objective to *total
 static int laplace_finish(pgpfa_ctx* c, Chunk& ch, double* total, int32_t* iters, int32_t* status, EstepStats& st) {
   const int nb = ch.nb, nvec = c->n;
+  // option laplace_evidence: the covariance phase also reduces log det H + sum_k log det K_k of every slot into evid_ld, fetched with the pivots below
+  const bool evidence = c->laplace_evidence != 0;
+  std::vector<double> ld(evidence ? nb : 0);
+  if (evidence) CHK(ensure_evidence_buffers(c));
   {
     const bool sum_only = c->plan_lowrank && !c->keep_trial_vsmgp;
     PhaseRange range_cov("pgpfa.covariance_blocks");
-    CHK(posterior_blocks(c, nb, 1.0, true, sum_only));
+    CHK(posterior_blocks(c, nb, 1.0, true, sum_only, evidence ? c->evid_ld : nullptr));
     for (int t : ch.tos) c->vsmgp_ok[t] = sum_only ? 0 : 1;
   }
   st.n_fact += nb;
@@ -1340,11 +1344,21 @@ static int laplace_finish(pgpfa_ctx* c, Chunk& ch, double* total, int32_t* iters
   hipLaunchKernelGGL(scatter_rotate_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->Xc, (long long)c->ld, nvec, c->Xmode, c->Xprev,
                      c->trial_of_slot, c->list_a);
   CHK(dl_enqueue(c, ch.info.data(), c->ws.info, sizeof(int) * nb));
+  if (evidence) CHK(dl_enqueue(c, ld.data(), c->evid_ld, sizeof(double) * nb));
   CHK(dl_flush(c));
   HIPC(hipGetLastError());
   for (int s = 0; s < nb; ++s) {
     if (ch.info[s] != 0 && ch.stat[s] == 0) ch.stat[s] = 3;
     *total += ch.f[s];
+  }
+  if (evidence) {
+    // log Z_r = -f_r(x*_r) - 1/2 (log det H_r(x*_r) + sum_k log det K_k)   (a dense retry pass of the same E-step overwrites its trials' values)
+    if ((int)c->log_evidence.size() != c->R) { c->log_evidence.assign(c->R, 0.0); c->evid_serial.assign(c->R, -1); }
+    for (int s = 0; s < nb; ++s) {
+      const int tr_ = ch.tos[s];
+      c->log_evidence[tr_] = -ch.f[s] - 0.5 * ld[s];
+      c->evid_serial[tr_] = (ch.info[s] == 0 && std::isfinite(c->log_evidence[tr_])) ? c->estep_serial : -1;
+    }
   }
   report_slots(ch, iters, status);
   return 0;
@@ -1398,11 +1412,14 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
   const int N = (int)tr.v.size();
+  if (c->laplace_evidence && c->laplace_f32)
+    return fail("laplace_evidence = 1 with laplace_f32 = %d: the log evidence needs the FP64 factor of the covariance phase (a log det from a single-precision factor is not implemented)", c->laplace_f32);
   std::vector<int32_t> it1(N), st1(N);
   double obj = 0.0;
   HIPC(hipSetDevice(c->device));
   c->pacc_used = false; c->pacc_valid = false;
   c->estep_serial += 1;
+  c->info["last_log_evidence_sum"] = 0.0;
   c->info["last_eps_wt_norm"] = 0.0; c->info["last_eps_wt_rms"] = 0.0;      // maxima over the chunks of THIS call
   c->info["last_cov_f32_fallbacks"] = 0.0;                                  // (counted over the chunks of this call: cov.hip)
   HIPC(hipMemsetAsync(c->Pacc, 0, (size_t)c->Tp * c->Tp * c->p * sizeof(double), c->st));
@@ -1462,10 +1479,29 @@ int pgpfa_estep_laplace(pgpfa_ctx* c, int n, const int32_t* idx, int warm_start,
   }
   CHK(remember_trials(c, tr.v));
   c->pacc_valid = c->pacc_used && retry.v.empty();
+  if (c->laplace_evidence) {
+    double zsum = 0.0;
+    for (int t : tr.v) zsum += (c->evid_serial[t] == c->estep_serial) ? c->log_evidence[t] : std::numeric_limits<double>::quiet_NaN();
+    c->info["last_log_evidence_sum"] = zsum;
+  }
   if (obj_sum) *obj_sum = obj;
   for (int i = 0; i < N; ++i) {
     if (iters) iters[i] = it1[i];
     if (status) status[i] = st1[i];
+  }
+  return 0;
+}
+
+// The Laplace log evidence of the listed trials, as left by the last pgpfa_estep_laplace that ran over them with option laplace_evidence on
+int pgpfa_get_log_evidence(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {
+  if (!c || !out) return fail("null argument");
+  Trials tr;
+  CHK(resolve_trials(c, n, idx, &tr));
+  for (size_t i = 0; i < tr.v.size(); ++i) {
+    const int t = tr.v[i];
+    if ((int)c->evid_serial.size() != c->R || c->evid_serial[t] < 0 || c->evid_serial[t] != c->mode_serial[t])
+      return fail("no log evidence for trial %d: its resident posterior was not produced by a Laplace E-step with laplace_evidence = 1", t);
+    out[i] = c->log_evidence[t];
   }
   return 0;
 }

@@ -1809,6 +1809,24 @@ inline __global__ __launch_bounds__(256) void sum_rows_kernel(const double* __re
   }
   if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
+// Log-determinant of the Laplace log evidence (option laplace_evidence), both sums of one slot in one workgroup: out[slot] = add + sum of the nbin
+// entries of row `slot` of bins (the per-bin log det(I + eps W_t) of the low-rank engine; NULL under the dense engine) + 2 sum_i log L_ii of the
+// slot's n x n Cholesky factor (leading dimension ld: the diagonal has stride ld + 1).  grid = slots, block = 256.
+inline __global__ __launch_bounds__(256) void evidence_logdet_kernel(const double* __restrict__ bins, int nbin, const double* __restrict__ L, long long sL, int ld,
+                                                              int n, double add, double* __restrict__ out) {
+  __shared__ double red[2][4];
+  const size_t slot = blockIdx.x;
+  const double* Ls = L + slot * sL;
+  double a = 0.0, b = 0.0;
+  if (bins)
+    for (int i = threadIdx.x; i < nbin; i += 256) a += bins[slot * nbin + i];
+  for (int i = threadIdx.x; i < n; i += 256) b += log(Ls[(size_t)i * ld + i]);
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    out[slot] = add + ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) + 2.0 * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+}
 // x = -Kv  (VIPostMean, inference.py:193-194)
 inline __global__ void negate_rows_kernel(const double* __restrict__ src, long long sSrc, double* __restrict__ dst, long long sDst, int n,
                                    const int* __restrict__ slots) {

@@ -41,6 +41,7 @@ _SIGNATURES = {
     'pgpfa_get_post_vsm': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p],
     'pgpfa_get_post_vsmgp': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p],
     'pgpfa_get_post_cov': [ct.c_void_p, ct.c_int, c_double_p],
+    'pgpfa_get_log_evidence': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p],
     'pgpfa_set_posterior': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_mstep_cd_costgrad': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p],
     'pgpfa_mstep_cd_newton_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
@@ -282,6 +283,14 @@ class Context:
         n, ii = self._n_idx(idx)
         out = np.empty((n, self.p, self.T))
         check(self.lib.pgpfa_get_post_mean(self.h, n, iptr(ii), dptr(out)))
+        return out
+
+    def log_evidence(self, idx=None):
+        """Laplace log evidence log Z_r of the listed trials (all: None), float64 [n]: what the last estep_laplace over them left while option
+        'laplace_evidence' was 1 (include/pgpfa.h: pgpfa_get_log_evidence).  Raises HipBackendError for a trial without a valid value."""
+        n, ii = self._n_idx(idx)
+        out = np.empty(n)
+        check(self.lib.pgpfa_get_log_evidence(self.h, n, iptr(ii), dptr(out)))
         return out
 
     def post_vsm(self, idx=None):

@@ -237,6 +237,11 @@ class DeviceInfRes(dict):
     are lazy views of device-resident results.  Carries the session and the trial list so that
     learning.updateParams* can run the M-step without the data ever leaving HBM."""
 
+    # Laplace log evidence of the trials of this rank (float64 array, order of the entries) and its mean over all ranks' trials: host values that
+    # inference.laplace sets while inference.LAPLACE_EVIDENCE is on; None otherwise
+    log_evidence = None
+    mean_log_evidence = None
+
     def __init__(self, session, trial_idx, local_pos):
         super().__init__()
         self.session = session

@@ -32,17 +32,29 @@ class PPGPFAfit():
     Arguments and defaults are those of the reference (engine.py:107-128).  Result attributes:
     optimParams, paramSeq, infRes (of the last batch processed), posteriorLikelihood,
     variationalLowerBound, learningDetails, inferenceTime, learningTime, tauSeq, ... (engine.py:453-474).
+
+    Additions (keyword-only): trackEvidence=True (Laplace) runs every E-step with inference.LAPLACE_EVIDENCE on and leaves the mean Laplace log
+    evidence per trial of every EM iteration in self.logEvidence (Online: of that iteration's minibatch).  emTol (a positive float, Batch mode
+    only) ends the fit after iteration i >= 1 when |L_i - L_{i-1}| <= emTol |L_{i-1}|, L being that mean log evidence (Laplace; implies
+    trackEvidence) or the variational lower bound; self.emIterations is the number of iterations run (maxEMiter when the rule did not stop the
+    fit) and sizes every per-iteration result, self.maxEMiter stays the argument.
     """
 
     def __init__(self, experiment, initParams=None, xdim=2, inferenceMethod='laplace', maxEMiter=50, optimLogLamb=False,
                  CdOptimMethod='TNC', tauOptimMethod='TNC', verbose=False, EMmode='Online', batchSize=5,
                  onlineParamUpdateMethod='diag', hessTol=None, stepPow=0.75, updateCdJointly=True, fullyUpdateTau=False,
                  extractAllTraj=False, extractAllTraj_trueParams=False, getPredictionErr=False, CdMaxIter=None,
-                 tauMaxIter=None, *, quiet=False, onlineWarmStart=True):
+                 tauMaxIter=None, *, quiet=False, onlineWarmStart=True, trackEvidence=False, emTol=None):
         if EMmode not in ('Batch', 'Online'):
             raise ValueError("EMmode must be 'Batch' or 'Online'")
         if inferenceMethod not in ('laplace', 'variational'):
             raise ValueError("inferenceMethod must be 'laplace' or 'variational'")
+        if emTol is not None:
+            if EMmode != 'Batch':
+                raise ValueError("emTol needs EMmode='Batch': a minibatch's evidence is too noisy for a two-point stopping rule")
+            if not (isinstance(emTol, (int, float)) and not isinstance(emTol, bool) and emTol > 0):
+                raise ValueError('emTol must be a positive float')
+        trackEvidence = inferenceMethod == 'laplace' and (bool(trackEvidence) or emTol is not None)
         self.experiment = experiment
         ydim = np.shape(experiment.data[0]['Y'])[0]
         trialBins = [int(np.shape(tr['Y'])[1]) for tr in experiment.data]
@@ -53,7 +65,7 @@ class PPGPFAfit():
         else:
             xdim = np.shape(initParams['C'])[1]
 
-        posteriorLikelihood, variationalLowerBound, learningDetails = [], [], []
+        posteriorLikelihood, variationalLowerBound, learningDetails, logEvidence = [], [], [], []
         params = initParams
         paramSeq = [initParams]
         learningTime, inferenceTime = [], []
@@ -62,7 +74,16 @@ class PPGPFAfit():
 
         def e_step(exp_, params_, prev):
             if inferenceMethod == 'laplace':
-                infRes_, nll_, opt_ = inference.laplace(experiment=exp_, params=params_, prevOptimRes=prev, verbose=verbose)
+                if not trackEvidence:
+                    infRes_, nll_, opt_ = inference.laplace(experiment=exp_, params=params_, prevOptimRes=prev, verbose=verbose)
+                    return infRes_, nll_, None, opt_
+                switch = inference.LAPLACE_EVIDENCE             # (the module switch is the caller's: restored behind every E-step)
+                inference.LAPLACE_EVIDENCE = True
+                try:
+                    infRes_, nll_, opt_ = inference.laplace(experiment=exp_, params=params_, prevOptimRes=prev, verbose=verbose)
+                finally:
+                    inference.LAPLACE_EVIDENCE = switch
+                logEvidence.append(infRes_.mean_log_evidence)
                 return infRes_, nll_, None, opt_
             infRes_, nll_, vlb_, opt_ = inference.dualVariational(experiment=exp_, params=params_, optimizeLogLambda=optimLogLamb,
                                                                  prevOptimRes=prev, verbose=verbose)
@@ -74,6 +95,8 @@ class PPGPFAfit():
             if log_path:
                 rec = {'iteration': i + 1, 'of': maxEMiter, 'em_mode': EMmode, 'inference': inferenceMethod, 'nPLL': float(nll),
                        'VLB': None if vlb is None else float(vlb), 'estep_s': inferenceTime[-1], 'mstep_s': learningTime[-1]}
+                if trackEvidence:
+                    rec['log_evidence'] = float(logEvidence[-1])
                 sess = getattr(infRes, 'session', None)
                 if sess is not None:
                     for key in ('last_pcg_iterations', 'last_newton_factorizations', 'last_newton_max_iter', 'last_dense_retries',
@@ -91,7 +114,13 @@ class PPGPFAfit():
             else:
                 util.Printer('Iteration: %3d of %3d, nPLL: = %.4f, VLB = %.4f' % (i + 1, maxEMiter, nll, vlb))
 
+        def settled(i):
+            """emTol: has the fit's score - mean log evidence (Laplace) or lower bound (variational) - stopped moving between iterations i - 1 and i?"""
+            seq = logEvidence if inferenceMethod == 'laplace' else variationalLowerBound
+            return emTol is not None and i >= 1 and abs(seq[i] - seq[i - 1]) <= emTol * abs(seq[i - 1])
+
         infRes = None
+        emIterations = maxEMiter
         if EMmode == 'Batch':                                   # reference engine.py:154-240
             if not quiet:
                 _banner(rows)
@@ -110,6 +139,9 @@ class PPGPFAfit():
                 learningDetails.append(learnDet)
                 paramSeq.append(params)
                 report(i, nll, vlb)
+                if settled(i):
+                    emIterations = i + 1
+                    break
 
         if EMmode == 'Online':                                  # reference engine.py:243-449
             if not quiet:
@@ -183,6 +215,9 @@ class PPGPFAfit():
         self.meanT = T if min(trialBins) == T else float(np.mean(trialBins))
         self.trialDur, self.binSize, self.numTrials = experiment.trialDur, experiment.binSize, numTrials
         self.maxEMiter, self.EMmode, self.inferenceMethod = maxEMiter, EMmode, inferenceMethod
+        self.emIterations = emIterations
+        if trackEvidence:
+            self.logEvidence = logEvidence
         self.initParams, self.paramSeq, self.optimParams = initParams, paramSeq, params
         self.posteriorLikelihood, self.variationalLowerBound = posteriorLikelihood, variationalLowerBound
         self.learningDetails, self.infRes = learningDetails, infRes
@@ -201,7 +236,7 @@ class PPGPFAfit():
 
     # -- summaries of the parameter path (reference engine.py:541-597) -------------------------------------------
     def processParamResults(self):
-        n = self.maxEMiter
+        n = getattr(self, 'emIterations', self.maxEMiter)       # (iterations run: fewer than maxEMiter when emTol stopped the fit)
         seq = self.paramSeq
         self.tauSeq = np.zeros([self.xdim, n])
         self.expectedSpikeCountsEst = np.zeros([self.ydim, n])

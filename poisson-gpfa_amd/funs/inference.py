@@ -94,6 +94,8 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     """
     sess, trial_idx = _prepare(experiment, params)
     sess.ctx.set_option('laplace_f32', int(LAPLACE_F32))       # (True is 1; LAPLACE_F32 is defined next to DUAL_F32 below)
+    evidence = bool(LAPLACE_EVIDENCE)
+    sess.ctx.set_option('laplace_evidence', int(evidence))
     n_all = len(trial_idx)
     # default: every rank holds the same experiment and takes a contiguous slice of its trials;
     # experiment._pgpfa_local_shard = True says this rank's experiment already IS its shard
@@ -127,11 +129,16 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     if verbose:
         for i, (it, st) in enumerate(zip(iters, status)):
             print('laplace inference trajectory of trial %d: %d Newton factorizations, %s' % (lo + i + 1, it, STATUS_TEXT.get(int(st), '?')))
-    tot = sess.allreduce(np.array([obj, float(len(mine))]))
+    log_z = sess.ctx.log_evidence(mine) if (evidence and len(mine)) else np.zeros(0)
+    # (the evidence rides in the all-reduce of the objective: one collective per E-step either way)
+    tot = sess.allreduce(np.array([obj, float(len(mine))] + ([float(np.sum(log_z))] if evidence else [])))
     post_lik = tot[0] / tot[1]
     infRes = DeviceInfRes(sess, mine, (lo, hi))
     infRes.newton_iters = iters
     infRes.newton_status = status
+    # LAPLACE_EVIDENCE: log Z_r of this rank's trials in the order of infRes, and the mean over the trials of all ranks; None while it is off
+    infRes.log_evidence = log_z if evidence else None
+    infRes.mean_log_evidence = float(tot[2] / tot[1]) if evidence else None
     if returnOptimRes:
         return infRes, -post_lik, DeviceOptimRes(sess, mine)
     return infRes, -post_lik
@@ -394,6 +401,12 @@ DUAL_F32 = False
 # whose single-precision factorisation meets a non-positive pivot is redone in FP64 (info key last_cov_f32_fallbacks).  The dense engine
 # ignores the flag; laplace() sends it on every call, dualVariational always runs its own covariance passes without it.
 LAPLACE_F32 = False
+# Laplace approximation of every trial's log evidence, log Z_r = -f_r(x*_r) - 1/2 (log det H_r(x*_r) + sum_k log det K_k) in the reference's
+# normalisation (sum log y! dropped), computed next to the covariance blocks of the E-step (C-ABI option laplace_evidence).
+# True: laplace() returns it as infRes.log_evidence (this rank's trials) and infRes.mean_log_evidence (mean over all ranks' trials); False:
+# both are None and the E-step is the default one, bit for bit.  Not available together with LAPLACE_F32 (the call fails).  laplace() sends it
+# on every call; engine.PPGPFAfit(trackEvidence=True) and util.crossValidation(score='evidence') switch it on around their own E-steps.
+LAPLACE_EVIDENCE = False
 
 
 class _ConcurrentProblems:

@@ -129,15 +129,36 @@ def splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials):
     return trainingSet, testSet
 
 
+def negLogEvidencePerBin(params, experiment):
+    """- sum_r log Z_r / sum_r T_r over the experiment's trials: one Laplace E-step at `params` with inference.LAPLACE_EVIDENCE on (the
+    switch is restored).  Trials may differ in length."""
+    from . import inference
+    switch = inference.LAPLACE_EVIDENCE
+    inference.LAPLACE_EVIDENCE = True
+    try:
+        infRes, _ = inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
+    finally:
+        inference.LAPLACE_EVIDENCE = switch
+    bins = sum(int(np.shape(tr['Y'])[1]) for tr in experiment.data)
+    return -float(infRes.mean_log_evidence) * len(experiment.data) / bins
+
+
 class crossValidation:
     """reference util.py:180-249: for xdim = 1..maxXdim fit on the training split and score the leave-one-neuron-out
-    prediction error on the test split; optimXdim is the arg-min.  learningMethod: 'batch', 'diag', 'hess' or 'grad'."""
+    prediction error on the test split; optimXdim is the arg-min.  learningMethod: 'batch', 'diag', 'hess' or 'grad'.
+    score='evidence' (an addition; Laplace only) scores a fit by ONE Laplace E-step of its parameters on the test split instead of the
+    numTestTrials * ydim held-out mode searches: errs[i] = - sum_r log Z_r / sum_r T_r, the negative Laplace log evidence per bin (lower is
+    better, so optimXdim stays the arg-min).  It also takes test trials of unequal length, which the leave-one-out score refuses."""
 
     def __init__(self, experiment, numTrainingTrials=10, numTestTrials=2, maxXdim=6, maxEMiter=3, batchSize=5,
-                 inferenceMethod='laplace', learningMethod='batch', quiet=True):
+                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo'):
         from . import engine
         if learningMethod not in ('batch', 'diag', 'hess', 'grad'):
             raise ValueError("learningMethod must be 'batch', 'diag', 'hess' or 'grad'")
+        if score not in ('loo', 'evidence'):
+            raise ValueError("score must be 'loo' or 'evidence'")
+        if score == 'evidence' and inferenceMethod != 'laplace':
+            raise ValueError("score='evidence' is the Laplace log evidence: it needs inferenceMethod='laplace'")
         trainingSet, testSet = splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials)
         self.errs, self.fits = [], []
         for xdimFit in range(1, maxXdim + 1):
@@ -149,10 +170,13 @@ class crossValidation:
                 fit = engine.PPGPFAfit(experiment=trainingSet, initParams=initParams, inferenceMethod=inferenceMethod,
                                        EMmode='Online', onlineParamUpdateMethod=learningMethod, maxEMiter=maxEMiter,
                                        batchSize=batchSize, quiet=quiet)
-            _, predErr = leaveOneOutPrediction(fit.optimParams, testSet)
+            if score == 'evidence':
+                predErr = negLogEvidencePerBin(fit.optimParams, testSet)
+            else:
+                _, predErr = leaveOneOutPrediction(fit.optimParams, testSet)
             self.errs.append(predErr)
             self.fits.append(fit)
-        self.inferenceMethod, self.learningMethod = inferenceMethod, learningMethod
+        self.inferenceMethod, self.learningMethod, self.score = inferenceMethod, learningMethod, score
         self.optimXdim = int(np.argmin(self.errs)) + 1
         self.maxXdim = maxXdim
 

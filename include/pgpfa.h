@@ -156,7 +156,10 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * the first E-step), "workspace_granule_mb" (1024: size of the mapped chunks),
  * "chord_max" (most chord steps of the per-trial fallback Newton on one factor), "slab_row_align" (1: rows of latent k of the low-rank
  * slab start on 128-byte lines), "dual_gemm" (1: the neuron contractions of the dual evaluation as GEMMs against a pair / loading table),
- * "cd_debug" (0; measurement only: bit switches that drop the exp / the products / the staging of the (C,d) kernels, tools/cd_probe.py). */
+ * "cd_debug" (0; measurement only: bit switches that drop the exp / the products / the staging of the (C,d) kernels, tools/cd_probe.py),
+ * "rates_chunk_trials" (0 - the default: pgpfa_posterior_rates walks its trial list in chunks sized so that the device staging of the per-trial planes
+ * it was asked for stays within 256 MiB; > 0: that many trials per chunk.  No output depends on it, bit for bit - the group sums are carried from
+ * chunk to chunk in list order; it exists for the tests of exactly that). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
 /* Options that pgpfa_set_params builds from - "eps_noise" (Gram matrices, their inverses, the low-rank factors), "lowrank_tol" (the low-rank
  * factors), "rank_gran", "thin_products" and "use_mfma" (the rank tables: compact offsets need both) - re-run it with the stored parameters
@@ -245,6 +248,34 @@ int pgpfa_get_log_evidence(pgpfa_ctx* ctx, int n, const int32_t* idx, double* ou
 /* Upload E-step results produced elsewhere (e.g. a reference infRes dict) for the M-step. */
 int pgpfa_set_posterior(pgpfa_ctx* ctx, int n, const int32_t* idx, const double* post_mean,
                         const double* post_vsm, const double* post_vsmgp /* [n][T][T][p] */);
+
+/* ---- posterior firing rates --------------------------------------------------------------- */
+/* What the resident posterior of the listed trials (idx NULL: all; a trial may be listed more than once) says about the firing rates
+ *   lambda_n(t) = exp(d_n + c_n . x_t)
+ * under the parameters of the last pgpfa_set_params - the posterior being whatever is resident for the trial: the Laplace one, the variational
+ * one after pgpfa_dual_finalize, or one uploaded with pgpfa_set_posterior.  With m_t = post_mean[:, t] and Sigma_t = post_vsm[t]:
+ *   eta[i][n][t] = d_n + sum_k C_nk m_kt                  posterior mean of the log rate (the argument of exp(C x + d), util.py:289-334, which the
+ *                                                         reference only ever evaluates at a mode and without a variance)
+ *   var[i][n][t] = sum_ab C_na Sigma_t[a][b] C_nb         its posterior variance, stored as max(., 0) (twice the v = 1/2 diag(C Sigma C^T) of
+ *                                                         inference.py:215-219, which the variational fixed point computes and never hands out)
+ *   rate         = exp(eta + var / 2)                     posterior mean of the rate, spikes per bin; the central credible band of the rate at
+ *                                                         level L is exp(eta -+ z_L sqrt(var)) - the caller forms both from eta and var
+ *   ell[i][n]    = sum_{t < T_r} (y_nt eta - rate)        expected Poisson log likelihood per trial and neuron without sum log y!, as the reference
+ *                                                         drops it (inference.py:12-32); reads the resident counts, both byte planes
+ *   group_sum[g][n][t] = sum_{i: group[i] = g, t < T_r} rate[i][n][t],   group_count[g][t] = #{i: group[i] = g, t < T_r}
+ * for a trial -> group table group[n] with ids 0..n_groups-1 (experimental conditions: the mean rate of a condition is group_sum / group_count; a
+ * group without trials gives zeros and a count of 0, a trial listed twice counts twice).  Every output may be NULL; with only group outputs asked for
+ * no per-trial [q][T] plane is written to memory at all.  No floating-point atomics: a workgroup owns a (group, neuron tile, bin tile), walks the
+ * group's trials in list order and carries its sums in registers, so group_sum is reproducible from run to run and does not depend on how the list
+ * is cut into chunks (option "rates_chunk_trials").  Trials of unequal length (pgpfa_set_trial_lengths): ell, group_sum and group_count stop at
+ * T_r; eta and var are written for all T bins - the padded bins hold the prior conditional, so there they are the forecast of the log rate.
+ * Fails, naming the trial, when a listed trial has no posterior - no E-step, pgpfa_dual_finalize or pgpfa_set_posterior has written one since its
+ * counts were uploaded -; when a group id is outside 0..n_groups-1; when a group output is asked for without the table.  Touches no E-step or M-step
+ * state: the workspace plan, the arena, the per-trial serials and snapshots and every sum an M-step reads are what they were. */
+int pgpfa_posterior_rates(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all */,
+                          const int32_t* group /* [n], 0..n_groups-1, or NULL */, int n_groups,
+                          double* eta /* [n][q][T] */, double* var /* [n][q][T] */, double* ell /* [n][q] */,
+                          double* group_sum /* [n_groups][q][T] */, int32_t* group_count /* [n_groups][T] */);
 
 /* ---- M-step ----------------------------------------------------------------------- */
 /* MStepObservationCost(_grad) (learning.py:20-91) over the trials of the last E-step /
@@ -387,6 +418,10 @@ int pgpfa_bench_potrf_diag(pgpfa_ctx* ctx, int batch, int reps, int phases, doub
 /* Sustained v_mfma_f64_16x16x4_f64 rate of the device (register-only loop): the practical MFMA
  * ceiling under the clock the chip holds, reported next to the datasheet peak. */
 int pgpfa_bench_mfma_peak(pgpfa_ctx* ctx, int iters, double* tflops);
+/* The host half of pgpfa_posterior_rates' group table, no device and no context: the list positions first..last-1 of every group in list order as
+ * CSR - positions of group g are pos[start[g] .. start[g + 1]), pos holding last - first entries.  Fails on a group id outside 0..n_groups-1. */
+int pgpfa_rates_group_csr(int n, const int32_t* group /* [n] */, int n_groups, int first, int last, int32_t* start /* [n_groups + 1] */,
+                          int32_t* pos /* [last - first] */);
 
 #ifdef __cplusplus
 }

@@ -1089,6 +1089,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "dual_f32") c->dual_f32 = (int)v;
   else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
   else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
+  else if (k == "rates_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("rates_chunk_trials is a count of trials, or 0"); c->rates_chunk = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
   else if (k == "dual_gemm") c->dual_gemm = (v != 0.0);

@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, workspace, copies; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -311,6 +311,10 @@ struct pgpfa_ctx {
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
   double* commbuf = nullptr; size_t commbuf_len = 0;
+  // posterior rates (pgpfa_posterior_rates, rates.hip): the feature's own table of loadings and pair products, built on first use and again
+  // after every pgpfa_set_params (rates_tbl_params: the "set_params_calls" count it was built under); option rates_chunk_trials
+  double* rates_tbl = nullptr; double rates_tbl_params = -1.0;
+  int rates_chunk = 0;                            // trials per chunk of a call (0: from the 256 MiB bound on the staging of the per-trial planes)
 };
 
 template <typename T>

@@ -43,6 +43,8 @@ _SIGNATURES = {
     'pgpfa_get_post_cov': [ct.c_void_p, ct.c_int, c_double_p],
     'pgpfa_get_log_evidence': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p],
     'pgpfa_set_posterior': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p, c_double_p, c_double_p],
+    'pgpfa_posterior_rates': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p],
+    'pgpfa_rates_group_csr': [ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_int, c_int32_p, c_int32_p],
     'pgpfa_mstep_cd_costgrad': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p],
     'pgpfa_mstep_cd_newton_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
     'pgpfa_mstep_cd_chord_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
@@ -111,6 +113,16 @@ def load_library():
 def check(rc):
     if rc != 0:
         raise HipBackendError(load_library().pgpfa_last_error().decode('utf-8', 'replace'))
+
+
+def rates_group_csr(group, n_groups, first=0, last=None):
+    """(start[n_groups + 1], pos[last - first]): the list positions first..last-1 of every group, in list order (pgpfa_rates_group_csr; host only)."""
+    gg = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+    last = gg.size if last is None else int(last)
+    start = np.zeros(int(n_groups) + 1, dtype=np.int32)
+    pos = np.zeros(max(last - int(first), 0), dtype=np.int32)
+    check(load_library().pgpfa_rates_group_csr(gg.size, iptr(gg), int(n_groups), int(first), last, iptr(start), iptr(pos)))
+    return start, pos
 
 
 def device_count():
@@ -316,6 +328,28 @@ class Context:
         v = as_f64(post_vsm).reshape(n, self.T * self.p * self.p)
         g = None if post_vsmgp is None else as_f64(post_vsmgp).reshape(n, self.T * self.T * self.p)
         check(self.lib.pgpfa_set_posterior(self.h, n, iptr(ii), dptr(m), dptr(v), None if g is None else dptr(g)))
+
+    def posterior_rates(self, idx=None, group=None, n_groups=0, want=('eta', 'var')):
+        """Posterior log-rate moments of the listed trials under the resident posterior and parameters (include/pgpfa.h: pgpfa_posterior_rates).
+        want: any of 'eta' [n][q][T], 'var' [n][q][T], 'ell' [n][q], 'group_sum' [n_groups][q][T], 'group_count' [n_groups][T] (int32); group: one
+        id in 0..n_groups-1 per listed trial.  Returns a dict of exactly the arrays asked for; nothing else is computed or moved."""
+        n, ii = self._n_idx(idx)
+        unknown = set(want) - {'eta', 'var', 'ell', 'group_sum', 'group_count'}
+        if unknown:
+            raise ValueError('unknown output(s) %s' % sorted(unknown))
+        gg = None
+        if group is not None:
+            gg = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+            if gg.shape != (n,):
+                raise ValueError('one group id per listed trial expected (%d), got %d' % (n, gg.size))
+        shapes = {'eta': (n, self.q, self.T), 'var': (n, self.q, self.T), 'ell': (n, self.q), 'group_sum': (int(n_groups), self.q, self.T)}
+        out = {k: np.empty(shapes[k]) for k in shapes if k in want}
+        if 'group_count' in want:
+            out['group_count'] = np.empty((int(n_groups), self.T), dtype=np.int32)
+        ptr = lambda k: dptr(out[k]) if k in out else None
+        check(self.lib.pgpfa_posterior_rates(self.h, n, iptr(ii), iptr(gg), int(n_groups), ptr('eta'), ptr('var'), ptr('ell'), ptr('group_sum'),
+                                             iptr(out.get('group_count'))))
+        return out
 
     # -- dual variational ---------------------------------------------------------------------
     def dual_costgrad(self, trial, lam, want_grad=True):

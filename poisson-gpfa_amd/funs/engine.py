@@ -298,6 +298,15 @@ class PPGPFAfit():
         self._keep_inf_res()                # (the held-out searches re-plan the chunk workspace; per-trial state stays)
         self.y_pred_mode, self.pred_err_mode = util.leaveOneOutPrediction(self.optimParams, self.experiment)
 
+    def posteriorRates(self, **kw):
+        """util.posteriorRates at the fitted parameters -> self.rates (a dict; keywords as there: infRes, trials, conditions, level, forecast,
+        want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first, as before
+        every E-step that would supersede it."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.rates = util.posteriorRates(self.optimParams, self.experiment, **kw)
+        return self.rates
+
     def extractTrajectories(self, method='laplace'):
         """One more E-step over all trials with the fitted parameters (reference engine.py:523-532)."""
         self._keep_inf_res()

@@ -113,6 +113,115 @@ def leaveOneOutPrediction(params, experiment):
     return y_loc, float(err_loc)
 
 
+# -- posterior firing rates ---------------------------------------------------------------------------------
+_RATE_KEYS = ('rate', 'lower', 'upper', 'median', 'eta', 'var', 'ell')
+
+
+def _band_z(level):
+    """z of the central credible band at `level`: P(|N(0,1)| <= z) = level."""
+    from statistics import NormalDist
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError('level must lie strictly between 0 and 1, got %r' % (level,))
+    return NormalDist().inv_cdf(0.5 * (1.0 + level))
+
+
+def _condition_groups(conditions, n):
+    """One integer label per listed trial -> (sorted distinct labels, group id 0..G-1 of every listed trial)."""
+    lab = np.asarray(conditions)
+    if lab.shape != (n,):
+        raise ValueError('conditions: one label per listed trial expected (%d), got shape %s' % (n, lab.shape))
+    if not np.issubdtype(lab.dtype, np.integer):
+        if not np.all(lab == np.floor(lab)):
+            raise ValueError('conditions must be integer labels')
+        lab = lab.astype(np.int64)
+    labels, group = np.unique(lab, return_inverse=True)
+    return labels, group.reshape(-1).astype(np.int32)
+
+
+def _cut_planes(sess, idx, arr, forecast):
+    """Per-trial planes arr[n][ydim][T] of the session's trials idx as the caller sees them: each cut to the trial's own T_r bins unless
+    `forecast`; one array when the shapes agree, else a list of (ydim, T_r) arrays (as orthonormalizeTrajectories returns x_tilde)."""
+    if forecast or sess.lengths is None:
+        return arr
+    lens = [int(sess.lengths[int(t)]) for t in idx]
+    if all(L == sess.T for L in lens):
+        return arr
+    out = [np.ascontiguousarray(arr[i][:, :L]) for i, L in enumerate(lens)]
+    return np.stack(out) if len(set(lens)) == 1 else out
+
+
+def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None, level=0.95, forecast=False, want=('rate', 'lower', 'upper')):
+    """Denoised single-trial firing rates lambda_n(t) = exp(d_n + c_n . x_t) under the posterior of the latents, with a credible band, and
+    their averages over the trials of every experimental condition.  The reference stops at the latent posterior; its only rate-like
+    outputs are exp(C x + d) at a held-out mode (util.py:289-334) and a per-neuron scalar from the parameters.  Everything per (trial,
+    neuron, bin) is computed on the device from the resident posterior (pgpfa_posterior_rates); post_vsm never comes to the host.
+
+    infRes None: one Laplace E-step at `params` over the experiment first.  A DeviceInfRes of this experiment's session whose entries are
+    still the resident ones (inference.laplace, dualVariational): that posterior, with `params` set as the parameters.  Anything else -
+    superseded by a later E-step, of another session, host arrays - raises ValueError.
+    trials: positions in experiment.data (None: all; repeats allowed).  conditions: one integer label per listed trial.
+    want: any of 'rate' (posterior mean exp(eta + var/2)), 'lower' / 'upper' (the central `level` band exp(eta -+ z sqrt(var))), 'median'
+    (exp(eta)) - all four in spikes per SECOND -, 'eta' / 'var' (posterior mean and variance of the log rate per bin) and 'ell' ([n][ydim]:
+    expected Poisson log likelihood sum_t y eta - rate, without sum log y!).  Per-trial entries are [n][ydim][T]; with trials of unequal
+    length each is cut to its T_r bins - a list of (ydim, T_r) arrays - unless forecast=True, which keeps all T bins: behind T_r the
+    posterior is the GP's prediction from the trial's own bins.  With `conditions` the dict also holds 'condition_mean' [G][ydim][T] in
+    spikes per second (the mean over the condition's trials that have the bin; NaN where none has), 'condition_count' [G][T] and
+    'condition_labels' [G]; with want=() only these come back and no per-trial plane leaves the device."""
+    from . import _session, inference
+    want = tuple(want)
+    unknown = [k for k in want if k not in _RATE_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_RATE_KEYS)))
+    z = _band_z(level)
+    xdim = np.shape(params['C'])[1]
+    sess, trial_idx = _session.session_for(experiment, xdim)
+    if sess.comm_ready:
+        raise NotImplementedError('posteriorRates does not support sharded sessions yet: every rank holds the posterior of its own trials only')
+    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
+    if idx.size == 0:
+        raise ValueError('empty trial list')
+    if infRes is None:
+        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
+    else:
+        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
+            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
+        covered = set(infRes.trial_idx.tolist())
+        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
+        if stale:
+            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
+        sess.set_params({'C': params['C'], 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+    planes = any(k in want for k in ('rate', 'lower', 'upper', 'median', 'eta', 'var'))
+    ask = (['eta', 'var'] if planes else []) + (['ell'] if 'ell' in want else [])
+    group, labels = None, None
+    if conditions is not None:
+        labels, group = _condition_groups(conditions, idx.size)
+        ask += ['group_sum', 'group_count']
+    if not ask:
+        raise ValueError('nothing asked for: want is empty and there are no conditions')
+    dev = sess.ctx.posterior_rates(idx, group=group, n_groups=0 if labels is None else len(labels), want=ask)
+    per_s = 1000.0 / float(experiment.binSize)
+    out = {}
+    if planes:
+        eta, var = dev['eta'], dev['var']
+        sd = np.sqrt(var) if ('lower' in want or 'upper' in want) else None
+        made = {'eta': lambda: eta, 'var': lambda: var, 'median': lambda: np.exp(eta) * per_s, 'rate': lambda: np.exp(eta + 0.5 * var) * per_s,
+                'lower': lambda: np.exp(eta - z * sd) * per_s, 'upper': lambda: np.exp(eta + z * sd) * per_s}
+        for k in want:
+            if k in made:
+                out[k] = _cut_planes(sess, idx, made[k](), forecast)
+    if 'ell' in want:
+        out['ell'] = dev['ell']
+    if labels is not None:
+        cnt = dev['group_count']
+        with np.errstate(invalid='ignore', divide='ignore'):
+            out['condition_mean'] = np.where(cnt[:, None, :] > 0, dev['group_sum'] / cnt[:, None, :], np.nan) * per_s
+        out['condition_count'] = cnt
+        out['condition_labels'] = labels
+    return out
+
+
 # -- latent-dimensionality cross-validation (reference util.py:180-275) -------------------------------------
 def splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials):
     """First numTrainingTrials trials / the numTestTrials after them, as shallow copies (reference util.py:263-275)."""

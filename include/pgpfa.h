@@ -159,12 +159,14 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * "cd_debug" (0; measurement only: bit switches that drop the exp / the products / the staging of the (C,d) kernels, tools/cd_probe.py),
  * "rates_chunk_trials" (0 - the default: pgpfa_posterior_rates walks its trial list in chunks sized so that the device staging of the per-trial planes
  * it was asked for stays within 256 MiB; > 0: that many trials per chunk.  No output depends on it, bit for bit - the group sums are carried from
- * chunk to chunk in list order; it exists for the tests of exactly that). */
+ * chunk to chunk in list order; it exists for the tests of exactly that),
+ * "sample_chunk_trials" (0 - the default: pgpfa_posterior_sample walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
+ * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
 /* Options that pgpfa_set_params builds from - "eps_noise" (Gram matrices, their inverses, the low-rank factors), "lowrank_tol" (the low-rank
  * factors), "rank_gran", "thin_products" and "use_mfma" (the rank tables: compact offsets need both) - re-run it with the stored parameters
  * when they change after it, so an option set before or after pgpfa_set_params gives the same numbers. */
-/* Info: "chunk_trials", "plan_lowrank", "n_pad", "lowrank_rtot" (total rank of the r x r system), "lowrank_rtot16" (the same with every
+/* Info: "sample_noise_dim" (normals per draw of the next pgpfa_posterior_sample), "chunk_trials", "plan_lowrank", "n_pad", "lowrank_rtot" (total rank of the r x r system), "lowrank_rtot16" (the same with every
  * latent's rank rounded up to 16: roff16[p], the rows the products with F take), "lowrank_compact" (1: compact rank offsets are live,
  * "rank_gran" 4 or 8 - lowrank_rtot < lowrank_rtot16 when they save rows), "last_estep_ms", "last_newton_factorizations",
  * "last_newton_solves", "last_pcg_iterations", "last_shared_factorizations", "last_cov_lowrank",
@@ -276,6 +278,38 @@ int pgpfa_posterior_rates(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all
                           const int32_t* group /* [n], 0..n_groups-1, or NULL */, int n_groups,
                           double* eta /* [n][q][T] */, double* var /* [n][q][T] */, double* ell /* [n][q] */,
                           double* group_sum /* [n_groups][q][T] */, int32_t* group_count /* [n_groups][T] */);
+
+/* Joint posterior samples of the latents and posterior-predictive spike counts.  X[i][s] is draw s from the Gaussian posterior N(m_r, Sigma_r) resident
+ * for trial r = idx[i], under the parameters of the E-step that produced it (restored around the call when the context has moved on): the covariance is
+ * the one pgpfa_get_post_cov returns for that trial - for a Laplace trial the inverse Hessian at the resident mode, for a trial whose posterior came from
+ * pgpfa_dual_finalize the VIPostCov of the kept lambda with the reference's jitter.  The pT x pT matrix is never formed: the draw is a square root of
+ * Sigma applied to standard normals,
+ *   low-rank engine   x = m + G F L^-T z2 + sqrt(eps) chol(G) z1     (G = (I + eps W)^-1 per bin, B = I + F^T Wt F = L L^T)
+ *   dense engine      x = m + L^-T z                                  (H = L L^T)
+ * with nz normals per draw: nz = p T + lowrank_rtot under the low-rank engine - z1 latent-major [p][T], then z2 in the compact rank order - and p T
+ * under the dense one (info key "sample_noise_dim": the nz of the next call; the engine follows the plan as for every covariance pass, option
+ * "cov_mode", and "dual_lowrank" for variational trials).  noise_in given: X - m is a deterministic linear function of it.  noise_in NULL: the normals
+ * are drawn on the device, each a pure function of (seed, trial id, sample index, element, stream) - Philox4x32-10 with streams 4 (z1) and 5 (z2), apart
+ * from the 1..3 of pgpfa_generate - so sample s is the same whether 8 or 4096 are asked for, wherever the trial stands in the list and however the list
+ * is chunked; a trial listed twice gets the same draws twice.  noise_out receives exactly the normals that were used.
+ *   Y[i][s][n][t] ~ Poisson(exp(d_n + c_n . x_t)) for t < T_r, 0 at padded bins, keyed by (seed, trial, sample, neuron, bin);
+ *   count_sum[i][s][n] = sum_{t < T_r} Y (integers; with only count_sum asked for no [q][T] plane is written to memory).
+ * Trials of unequal length: X covers all T bins, the padded ones are draws of the forecast (W is zero there).  The pass is FP64 whatever
+ * "laplace_f32" says.  noise_in / noise_out are sized by the current parameters: when a trial's posterior was computed under timescales whose
+ * low-rank system has fewer rows the last entries of z2 are not used (noise_out reports zeros there); when it has more a call with noise arrays
+ * fails (set those parameters first) - without noise arrays every trial simply uses its own system.
+ * Fails, naming what is wrong: n_samples < 1; every output NULL; set_params not called; Y or count_sum without a counts table (the trial lengths are
+ * unknown); a trial without such a posterior - no E-step since its counts were uploaded, or one given by pgpfa_set_posterior, of which only blocks are
+ * known -, naming the trial; a draw above 65535, naming the trial; an asynchronous timescale pass in flight.
+ * Leaves untouched: post_mean, post_vsm, post_vsmGP and their resident marks, the sums pgpfa_mstep_precomp reads, mode serials, snapshots, log
+ * evidence and the resident counts.  Uses the chunk workspace as pgpfa_get_post_cov does. */
+int pgpfa_posterior_sample(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                           int n_samples, unsigned long long seed,
+                           const double* noise_in  /* [n][S][nz] or NULL: drawn on the device */,
+                           double*       noise_out /* [n][S][nz] or NULL: the normals that were used */,
+                           double*   X         /* [n][S][p][T] or NULL */,
+                           uint16_t* Y         /* [n][S][q][T] or NULL */,
+                           int32_t*  count_sum /* [n][S][q]    or NULL */);
 
 /* ---- M-step ----------------------------------------------------------------------- */
 /* MStepObservationCost(_grad) (learning.py:20-91) over the trials of the last E-step /

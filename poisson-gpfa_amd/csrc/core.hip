@@ -1089,6 +1089,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "dual_f32") c->dual_f32 = (int)v;
   else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
   else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
+  else if (k == "sample_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("sample_chunk_trials is a count of trials, or 0"); c->sample_chunk = (int)v; }
   else if (k == "rates_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("rates_chunk_trials is a count of trials, or 0"); c->rates_chunk = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
@@ -1169,6 +1170,11 @@ int pgpfa_get_info(pgpfa_ctx* c, const char* key, double* value) {
       if (k == base + "_max_flops") { *value = c->prof.max_flops[t]; return 0; }
     }
     return fail("unknown info key '%s'", key);
+  }
+  if (k == "sample_noise_dim") {                             // normals per draw of the next pgpfa_posterior_sample: p T, + the rank under the low-rank engine
+    if (!c->have_params) return fail("set_params has not been called");
+    *value = (double)(c->n + (want_lowrank(c) ? c->rtot : 0));
+    return 0;
   }
   if (k == "hbm_bytes_allocated") { *value = (double)c->bytes; return 0; }
   if (k == "hbm_bytes_free" || k == "hbm_bytes_total") {

@@ -660,6 +660,41 @@ int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, b
 }
 
 
+// Steps a - b of the covariance passes alone, for pgpfa_posterior_sample (psample.hip): from the curvature blocks c->W of the slots [0, nb) to L^-T, in
+// FP64 whatever laplace_f32 / dual_f32 say.  Low-rank plan: G_t into c->Gbin, and L^-T of B = I + F^T Wt F (rpad x rpad, ld = rpad, upper triangular,
+// the rest of the square cleared) into the Mt slabs.  Dense plan: L^-T of the Hessian (npad x npad, ld = c->ld) into the Mt slabs.  No posterior output
+// and no info key is written; the caller clears and reads ws.info.
+int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale) {
+  if (!c->plan_lowrank) {
+    CHK(ensure_mt_clean(c));
+    CHK(assemble(c, c->ident, nb, diag_scale));
+    CHK(factor(c, c->ws, c->ident, nb));
+    CHK(inverse_t(c, c->ws, c->ident, nb));
+    HIPC(hipGetLastError());
+    return 0;
+  }
+  if (diag_scale != 1.0) return fail("internal: jittered factor requested under the low-rank workspace plan");
+  const int T = c->T, p = c->p, Tp = c->Tp, rpad = c->rpad;
+  if (p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, p);
+  const long long sW = (long long)T * p * p;
+  CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, nullptr));
+  CholWS lw = c->ws;
+  lw.ld = rpad; lw.npad = rpad; lw.nact = round_up(c->rtot, 64);
+  const int nblk64 = c->rank_compact ? round_up(c->rtot16, 64) / 64 : rpad / 64, npairs = nblk64 * (nblk64 + 1) / 2;
+  const int* cmap = c->rank_compact ? c->d_cmap : nullptr;
+  hipLaunchKernelGGL(assemble_b_kernel_t<double>, dim3(npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad,
+                     nblk64, (const double*)c->Flr, Tp, T, p, c->d_blk_lat, c->d_blk_col, c->Wt, sW, c->ident, nb, cmap);
+  if (cmap && rpad > c->rtot)
+    hipLaunchKernelGGL(pad_identity_kernel<double>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad, c->rtot, rpad, lw.nact, (int)NB, c->ident);
+  HIPC(hipGetLastError());
+  CHK(factor(c, lw, c->ident, nb));
+  c->mt_dirty = true;
+  hipLaunchKernelGGL(fill_slabs_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.Mt, lw.sM, (size_t)rpad * rpad, 0.0);
+  CHK(inverse_t(c, lw, c->ident, nb));
+  HIPC(hipGetLastError());
+  return 0;
+}
+
 static int get_rows(pgpfa_ctx* c, int n, const int32_t* idx, const double* src, size_t len, double* out) {
   if (!c || !out) return fail("null argument");
   HIPC(hipSetDevice(c->device));

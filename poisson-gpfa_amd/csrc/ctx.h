@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, workspace, copies; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -315,6 +315,7 @@ struct pgpfa_ctx {
   // after every pgpfa_set_params (rates_tbl_params: the "set_params_calls" count it was built under); option rates_chunk_trials
   double* rates_tbl = nullptr; double rates_tbl_params = -1.0;
   int rates_chunk = 0;                            // trials per chunk of a call (0: from the 256 MiB bound on the staging of the per-trial planes)
+  int sample_chunk = 0;                           // option sample_chunk_trials: the same for pgpfa_posterior_sample (psample.hip); no output depends on it
 };
 
 template <typename T>
@@ -469,6 +470,7 @@ int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, b
 int ensure_evidence_buffers(pgpfa_ctx* c);
 int post_vsm_from_mt(pgpfa_ctx* c, int nslots);        // post_vsm[t] of the first nslots slots from their dense L^-T slabs
 int ensure_trial_vsmgp(pgpfa_ctx* c, const std::vector<int>& trials);
+int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale);      // steps a - b alone (per-bin blocks, B, factor, L^-T) in FP64: pgpfa_posterior_sample
 // dual.hip
 int ensure_lambda(pgpfa_ctx* c);
 int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<double>* sD, std::vector<double>* vKv);

@@ -1,0 +1,243 @@
+// libpgpfa_hip.so - psample.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): joint posterior samples of the latents and
+// posterior-predictive spike counts (pgpfa_posterior_sample)
+#include "ctx.h"
+#include "model.h"
+#include "sample.h"
+#include "psample.h"
+
+using namespace pgpfa;
+
+namespace {
+
+constexpr size_t SAMPLE_STAGE_BYTES = (size_t)256 << 20;     // bound on the device staging of one chunk (noise, U, trajectories, count planes)
+constexpr int GEMM_COL_SLACK = 128;                          // the GEMM stages whole column tiles of its second operand: columns past N are read, never used
+
+struct DevBufs {                                              // scratch of one call: freed on every way out
+  std::vector<void*> v;
+  ~DevBufs() { for (void* p : v) hipFree(p); }
+  template <typename T> int get(T** out, size_t count) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail("pgpfa_posterior_sample: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
+    v.push_back(p);
+    *out = reinterpret_cast<T*>(p);
+    return 0;
+  }
+};
+
+struct SampleArgs {
+  const std::vector<int>* trials;     // trial of every list position
+  int S; unsigned long long seed;
+  const double* noise_in; double* noise_out; double* X; uint16_t* Y; int32_t* count_sum;
+  bool lowrank;                       // engine the call's noise dimension was sized for
+  int nz;
+};
+
+// the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
+int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos, bool dual) {
+  CHK(ready_estep(c, dual ? c->dual_lowrank : true));
+  if (dual) CHK(ensure_lambda(c));
+  const int n = c->n, q = c->q, p = c->p, T = c->T, S = a.S, nz = a.nz;
+  const bool lr = c->plan_lowrank;
+  const int t_first = (*a.trials)[pos[0]];
+  if (lr != a.lowrank)
+    return fail("the posterior of trial %d takes the %s covariance engine, the noise of this call was sized for the %s one: sample those trials in a call of their own",
+                t_first, lr ? "low-rank" : "dense", a.lowrank ? "low-rank" : "dense");
+  const int rz = lr ? c->rtot : 0, rpad = c->rpad, npad = c->npad;
+  if (rz > nz - n && (a.noise_in || a.noise_out))          // (without noise arrays every group simply uses its own system's rows)
+    return fail("the posterior of trial %d was computed under timescales whose low-rank system has %d rows, the noise of this call has %d (the rank under the current "
+                "parameters): set the parameters of that E-step before sampling it", t_first, rz, nz - n);
+  const bool want_counts = a.Y || a.count_sum;
+
+  // chunks of the group: device staging per trial
+  const size_t ldz = lr ? (size_t)rpad : (size_t)npad;       // leading dimension of the GEMM's noise operand (z2 panel / dense z), zero below the rows in use
+  const size_t per_trial = (size_t)S * (((lr ? 2 * ldz + n : ldz) + n) * sizeof(double) + (a.Y ? (size_t)q * T * sizeof(uint16_t) : 0) + (want_counts ? (size_t)q * sizeof(int) : 0));
+  int chunk = (int)std::min<size_t>(pos.size(), (size_t)c->B);
+  if (c->sample_chunk > 0) chunk = std::min(chunk, c->sample_chunk);
+  else chunk = (int)std::min<size_t>((size_t)chunk, std::max<size_t>(1, SAMPLE_STAGE_BYTES / per_trial));
+  if ((long long)chunk * S > (1LL << 30)) return fail("pgpfa_posterior_sample: %d samples of %d trials exceed one chunk's columns", S, chunk);
+
+  DevBufs dev;
+  double *dX = nullptr, *dZ1 = nullptr, *dZ = nullptr, *dU = nullptr;
+  uint16_t* dY = nullptr;
+  int *dCs = nullptr, *dOver = nullptr;
+  const size_t cols = (size_t)chunk * S;
+  CHK(dev.get(&dX, cols * n));
+  CHK(dev.get(&dZ, (cols + GEMM_COL_SLACK) * ldz));
+  HIPC(hipMemsetAsync(dZ, 0, (cols + GEMM_COL_SLACK) * ldz * sizeof(double), c->st));      // rows past the ones in use stay zero for the whole call
+  if (lr) {
+    CHK(dev.get(&dZ1, cols * n));
+    CHK(dev.get(&dU, (cols + GEMM_COL_SLACK) * ldz));
+    HIPC(hipMemsetAsync(dU, 0, (cols + GEMM_COL_SLACK) * ldz * sizeof(double), c->st));
+  }
+  if (a.Y) CHK(dev.get(&dY, cols * q * T));
+  if (want_counts) { CHK(dev.get(&dCs, cols * q)); CHK(dev.get(&dOver, (size_t)chunk)); }
+  const int zused = lr ? rz : n;                               // rows of dZ a draw fills: z2, or the dense z
+  const size_t zoff = lr ? (size_t)n : 0;                      // where they sit in a draw's nz normals
+
+  std::vector<int> info(chunk), over(chunk), tos;
+  const size_t m = (size_t)q * T;
+  for (size_t c0 = 0; c0 < pos.size(); c0 += chunk) {
+    const int nb = (int)std::min<size_t>((size_t)chunk, pos.size() - c0);
+    tos.assign(nb, 0);
+    for (int s = 0; s < nb; ++s) tos[s] = (*a.trials)[pos[c0 + s]];
+    CHK(upload_list(c, c->trial_of_slot, tos));
+    HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
+    // curvature blocks of the slots, as materialize_impl (cov.hip) forms them, then steps a - b of the covariance pass
+    if (dual) {
+      for (int s = 0; s < nb; ++s)
+        HIPC(hipMemcpyAsync(c->lamd + (size_t)s * m, c->lam_keep + (size_t)tos[s] * m, m * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+      std::vector<double> sB, sD, vKv;
+      CHK(dual_common(c, nb, &sB, &sD, &vKv));
+      if (lr) { CHK(dual_jitter(c, nb)); CHK(posterior_factor_only(c, nb, 1.0)); }
+      else CHK(posterior_factor_only(c, nb, 1.0 + 1e-6));
+    } else {
+      hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, n, c->Xc, (long long)c->ld, c->trial_of_slot, 0);
+      CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
+      CHK(posterior_factor_only(c, nb, 1.0));
+    }
+    CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
+    CHK(dl_flush(c));
+    for (int s = 0; s < nb; ++s)
+      if (info[s] != 0) return fail("posterior precision of trial %d is not positive definite at the resident posterior", tos[s]);
+
+    // 1. the normals: copied in, or drawn
+    if (a.noise_in) {
+      for (int s = 0; s < nb; ++s) {
+        const double* src = a.noise_in + (size_t)pos[c0 + s] * S * nz;
+        if (lr) HIPC(hipMemcpy2DAsync(dZ1 + (size_t)s * S * n, (size_t)n * sizeof(double), src, (size_t)nz * sizeof(double), (size_t)n * sizeof(double), S, hipMemcpyHostToDevice, c->st));
+        if (zused > 0)
+          HIPC(hipMemcpy2DAsync(dZ + (size_t)s * S * ldz, ldz * sizeof(double), src + zoff, (size_t)nz * sizeof(double), (size_t)zused * sizeof(double), S, hipMemcpyHostToDevice, c->st));
+      }
+    } else {
+      if (lr) {
+        const int nblk = (n + 511) / 512;
+        hipLaunchKernelGGL(psample_noise_kernel, dim3((unsigned)S * nblk, nb), dim3(256), 0, c->st, dZ1, (long long)n, n, S, nblk, a.seed, PS_STREAM_Z1, c->trial_of_slot);
+      }
+      if (zused > 0) {
+        const int nblk = (zused + 511) / 512;
+        hipLaunchKernelGGL(psample_noise_kernel, dim3((unsigned)S * nblk, nb), dim3(256), 0, c->st, dZ, (long long)ldz, zused, S, nblk, a.seed, lr ? PS_STREAM_Z2 : PS_STREAM_Z1,
+                           c->trial_of_slot);
+      }
+      HIPC(hipGetLastError());
+    }
+    if (lr) {
+      // 2. U = L^-T Z2 per slot, then Yv_k = F_k U_k per latent over the S columns of every slot: the library's GEMM.  L^-T is upper triangular: tile row
+      //    ti starts its k loop at its first row (KF_BEGIN_ROW), which skips the zero half in 64-row steps and keeps the launch off the split-K path - the
+      //    number of k parts there follows the number of tiles, i.e. the chunk and the sample count, and the bits of a draw must not.  The products with F
+      //    stay off it the same way (a one-level batch declared as the low half of a two-level one).
+      GemmP u{};
+      u.A = c->ws.Mt; u.sA = c->ws.sM; u.lda = rpad;
+      u.B = dZ; u.sB = (long long)S * ldz; u.ldb = (int)ldz;
+      u.C = dU; u.sC = (long long)S * ldz; u.ldc = (int)ldz;
+      u.M = rpad; u.N = S; u.K = rpad; u.alpha = 1.0; u.beta = 0.0;
+      u.slots = c->ident; u.nbatch = nb; u.mode = GEMM_FULL; u.kflags = KF_BEGIN_ROW;
+      CHK(gemm(c, true, u));
+      for (int k = 0; k < p; ++k) {
+        GemmP g{};
+        g.A = c->Flr + (size_t)k * c->Tp * c->Tp; g.sA = 0; g.lda = c->Tp;
+        g.B = dU + c->roff[k]; g.sB = (long long)S * ldz; g.ldb = (int)ldz;
+        g.C = dX + (size_t)k * T; g.sC = (long long)S * n; g.ldc = n;
+        g.M = T; g.N = S; g.K = c->rk[k]; g.alpha = 1.0; g.beta = 0.0;
+        g.slots = c->ident; g.nbatch = nb; g.nb_lo = nb; g.mode = GEMM_FULL; g.kflags = 0;
+        CHK(gemm(c, true, g));
+      }
+      // 3. x = m + G yv + sqrt(eps) chol(G) z1, in place
+      PsMixP mx{};
+      mx.X = dX; mx.Z1 = dZ1; mx.G = c->Gbin; mx.Xmode = c->Xmode; mx.trial_of_slot = c->trial_of_slot;
+      mx.S = S; mx.p = p; mx.T = T; mx.sqrt_eps = std::sqrt(c->eps);
+      int rc = 0;
+      dispatch_pw(p, [&](auto pw) {
+        constexpr int PW = decltype(pw)::value;
+        const size_t lds = psample_mix_lds(PW);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&psample_mix_kernel<PW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { rc = 1; return; }
+        hipLaunchKernelGGL(psample_mix_kernel<PW>, dim3((T + psample_bt(PW) - 1) / psample_bt(PW), nb), dim3(256), lds, c->st, mx);
+      });
+      if (rc) { (void)hipGetLastError(); return fail("pgpfa_posterior_sample: the mixing kernel's LDS size was refused"); }
+    } else {
+      // 5. dense engine: X = m + L^-T Z
+      GemmP g{};
+      g.A = c->ws.Mt; g.sA = c->ws.sM; g.lda = c->ld;
+      g.B = dZ; g.sB = (long long)S * ldz; g.ldb = (int)ldz;
+      g.C = dX; g.sC = (long long)S * n; g.ldc = n;
+      g.M = n; g.N = S; g.K = npad; g.alpha = 1.0; g.beta = 0.0;
+      g.slots = c->ident; g.nbatch = nb; g.mode = GEMM_FULL; g.kflags = KF_BEGIN_ROW;
+      CHK(gemm(c, true, g));
+      const int nblk = (n + 255) / 256;
+      hipLaunchKernelGGL(psample_add_mean_kernel, dim3((unsigned)S * nblk, nb), dim3(256), 0, c->st, dX, c->Xmode, n, S, nblk, c->trial_of_slot);
+    }
+    HIPC(hipGetLastError());
+    // 4. predictive counts
+    if (want_counts) {
+      HIPC(hipMemsetAsync(dOver, 0, sizeof(int) * nb, c->st));
+      PsCountP cp{};
+      cp.X = dX; cp.C = c->C; cp.d = c->d; cp.len = c->trial_len; cp.trial_of_slot = c->trial_of_slot;
+      cp.Y = dY; cp.csum = a.count_sum ? dCs : nullptr; cp.over = dOver;
+      cp.S = S; cp.q = q; cp.p = p; cp.T = T; cp.seed = a.seed;
+      hipLaunchKernelGGL(psample_counts_kernel, dim3((unsigned)S, nb), dim3(256), 0, c->st, cp);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(over.data(), dOver, sizeof(int) * nb, hipMemcpyDeviceToHost, c->st));
+    }
+    // results of the chunk, by list position
+    for (int s = 0; s < nb; ++s) {
+      const size_t ps = (size_t)pos[c0 + s];
+      if (a.X) HIPC(hipMemcpyAsync(a.X + ps * S * n, dX + (size_t)s * S * n, (size_t)S * n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+      if (a.Y) HIPC(hipMemcpyAsync(a.Y + ps * S * m, dY + (size_t)s * S * m, (size_t)S * m * sizeof(uint16_t), hipMemcpyDeviceToHost, c->st));
+      if (a.count_sum) HIPC(hipMemcpyAsync(a.count_sum + ps * S * q, dCs + (size_t)s * S * q, (size_t)S * q * sizeof(int), hipMemcpyDeviceToHost, c->st));
+      if (a.noise_out) {
+        double* dst = a.noise_out + ps * S * nz;
+        if (lr) HIPC(hipMemcpy2DAsync(dst, (size_t)nz * sizeof(double), dZ1 + (size_t)s * S * n, (size_t)n * sizeof(double), (size_t)n * sizeof(double), S, hipMemcpyDeviceToHost, c->st));
+        if (zused > 0)
+          HIPC(hipMemcpy2DAsync(dst + zoff, (size_t)nz * sizeof(double), dZ + (size_t)s * S * ldz, ldz * sizeof(double), (size_t)zused * sizeof(double), S, hipMemcpyDeviceToHost, c->st));
+      }
+    }
+    HIPC(hipStreamSynchronize(c->st));                         // the staging is reused by the next chunk
+    HIPC(hipGetLastError());
+    if (a.noise_out && (int)zoff + zused < nz)                // normals of the call's z2 this snapshot's smaller system has no row for: not used, reported as zeros
+      for (int s = 0; s < nb; ++s)
+        for (int j = 0; j < S; ++j) {
+          double* dst = a.noise_out + ((size_t)pos[c0 + s] * S + j) * nz;
+          std::fill(dst + zoff + zused, dst + nz, 0.0);
+        }
+    if (want_counts)
+      for (int s = 0; s < nb; ++s)
+        if (over[s]) return fail("a predictive count of trial %d exceeds 65535: the rates exp(d + C x) of its draws do not fit the uint16 output", tos[s]);
+  }
+  return 0;
+}
+
+}  // namespace
+
+int pgpfa_posterior_sample(pgpfa_ctx* c, int n, const int32_t* idx, int n_samples, unsigned long long seed, const double* noise_in, double* noise_out, double* X,
+                           uint16_t* Y, int32_t* count_sum) {
+  if (!c) return fail("null context");
+  if (n_samples < 1) return fail("pgpfa_posterior_sample: n_samples = %d, at least one draw per trial is needed", n_samples);
+  if (!noise_out && !X && !Y && !count_sum) return fail("pgpfa_posterior_sample: no output asked for (noise_out, X, Y and count_sum are all NULL)");
+  if (!c->have_params) return fail("set_params has not been called");
+  if ((Y || count_sum) && !c->have_counts)
+    return fail("spike counts have not been uploaded: predictive counts stop at every trial's own length, which is unknown without the counts table");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  Trials tr;
+  CHK(resolve_trials(c, n, idx, &tr));
+  // a posterior that can be sampled: one an E-step or pgpfa_dual_finalize of this context wrote (its parameter snapshot) - of an uploaded one only blocks are known
+  for (int t : tr.v)
+    if (c->trial_snap[t] < 0 || (c->trial_dual[t] && !c->lam_keep))
+      return fail("no posterior to sample for trial %d: no E-step has written one since its counts were uploaded (a posterior given by pgpfa_set_posterior "
+                  "cannot be sampled, only its blocks are known)", t);
+  SampleArgs a{};
+  a.trials = &tr.v; a.S = n_samples; a.seed = seed; a.noise_in = noise_in; a.noise_out = noise_out; a.X = X; a.Y = Y; a.count_sum = count_sum;
+  // engine and noise dimension under the current parameters (info key "sample_noise_dim"); variational trials follow option dual_lowrank
+  bool any_laplace = false;
+  for (int t : tr.v) any_laplace = any_laplace || !c->trial_dual[t];
+  a.lowrank = want_lowrank(c) && (any_laplace || c->dual_lowrank);
+  a.nz = c->n + (a.lowrank ? c->rtot : 0);
+  std::map<std::pair<int, int>, std::vector<int>> groups;     // positions by (snapshot, kind of posterior), as ensure_trial_vsmgp groups its rebuilds
+  for (size_t i = 0; i < tr.v.size(); ++i) groups[std::make_pair(c->trial_snap[tr.v[i]], (int)c->trial_dual[tr.v[i]])].push_back((int)i);
+  for (auto& kv : groups) {
+    const std::vector<int>& pos = kv.second;
+    const bool dual = kv.first.second != 0;
+    CHK(with_snapshot(c, kv.first.first, [&]() { return sample_group(c, a, pos, dual); }));
+  }
+  return 0;
+}

@@ -44,6 +44,7 @@ _SIGNATURES = {
     'pgpfa_get_log_evidence': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p],
     'pgpfa_set_posterior': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_rates': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p],
+    'pgpfa_posterior_sample': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p, ct.POINTER(ct.c_uint16), c_int32_p],
     'pgpfa_rates_group_csr': [ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_int, c_int32_p, c_int32_p],
     'pgpfa_mstep_cd_costgrad': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p],
     'pgpfa_mstep_cd_newton_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
@@ -349,6 +350,37 @@ class Context:
         ptr = lambda k: dptr(out[k]) if k in out else None
         check(self.lib.pgpfa_posterior_rates(self.h, n, iptr(ii), iptr(gg), int(n_groups), ptr('eta'), ptr('var'), ptr('ell'), ptr('group_sum'),
                                              iptr(out.get('group_count'))))
+        return out
+
+    def posterior_sample(self, idx=None, n_samples=1, seed=0, noise=None, want=('x',)):
+        """Joint draws from the resident posterior of the listed trials (repeats allowed) and posterior-predictive counts (include/pgpfa.h:
+        pgpfa_posterior_sample).  want: any of 'x' [n][S][p][T], 'y' [n][S][q][T] (uint16), 'count_sum' [n][S][q] (int32), 'noise' [n][S][nz] - the
+        standard normals that were used, nz = info('sample_noise_dim').  noise: those normals given by the caller ([n][S][nz]) instead of drawn on the
+        device from `seed`.  Returns a dict of exactly the arrays asked for."""
+        n, ii = self._n_idx(idx)
+        unknown = set(want) - {'x', 'y', 'count_sum', 'noise'}
+        if unknown:
+            raise ValueError('unknown output(s) %s' % sorted(unknown))
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError('n_samples = %d: at least one draw per trial is needed' % S)
+        if not want:
+            raise ValueError('no output asked for')
+        zin = None
+        nz = None
+        if noise is not None or 'noise' in want:
+            nz = int(self.info('sample_noise_dim'))
+        if noise is not None:
+            zin = as_f64(noise)
+            if zin.shape != (n, S, nz):
+                raise ValueError('noise must have shape (n, n_samples, nz) = %s, got %s' % ((n, S, nz), zin.shape))
+        shapes = {'x': ((n, S, self.p, self.T), np.float64), 'y': ((n, S, self.q, self.T), np.uint16), 'count_sum': ((n, S, self.q), np.int32),
+                  'noise': ((n, S, nz), np.float64)}
+        out = {k: np.empty(shapes[k][0], dtype=shapes[k][1]) for k in shapes if k in want}
+        y = out.get('y')
+        check(self.lib.pgpfa_posterior_sample(self.h, n, iptr(ii), S, ct.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), None if zin is None else dptr(zin),
+                                              dptr(out['noise']) if 'noise' in out else None, dptr(out['x']) if 'x' in out else None,
+                                              None if y is None else y.ctypes.data_as(ct.POINTER(ct.c_uint16)), iptr(out.get('count_sum'))))
         return out
 
     # -- dual variational ---------------------------------------------------------------------

@@ -307,6 +307,14 @@ class PPGPFAfit():
         self.rates = util.posteriorRates(self.optimParams, self.experiment, **kw)
         return self.rates
 
+    def posteriorSamples(self, **kw):
+        """util.posteriorSamples at the fitted parameters -> self.samples (a dict; keywords as there: infRes, trials, nSamples, seed, want).
+        Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.samples = util.posteriorSamples(self.optimParams, self.experiment, **kw)
+        return self.samples
+
     def extractTrajectories(self, method='laplace'):
         """One more E-step over all trials with the fitted parameters (reference engine.py:523-532)."""
         self._keep_inf_res()

@@ -222,6 +222,60 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     return out
 
 
+_SAMPLE_KEYS = ('x', 'y', 'count_sum', 'noise')
+
+
+def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100, seed=0, want=('x',)):
+    """Joint draws of whole latent trajectories from the posterior of every listed trial, and posterior-predictive spike counts of every draw.
+    The reference hands out the marginals of the posterior only; whatever depends on the joint uncertainty of a trajectory - a peak time, a
+    path length, a band for a time-integrated rate, Fano factors of predicted counts, over-dispersed starts for funs.mcmc - needs draws.  They
+    are made on the device from a square root of the posterior covariance the covariance pass builds anyway (pgpfa_posterior_sample); the
+    (xdim T) x (xdim T) matrix is never formed.
+
+    infRes None: one Laplace E-step at `params` over the experiment first.  A DeviceInfRes of this experiment's session whose entries are still
+    the resident ones (inference.laplace, dualVariational): that posterior, under the parameters of the E-step that produced it.  Anything else
+    raises ValueError.  trials: positions in experiment.data (None: all; repeats allowed - a repeated trial gets the same draws).
+    want: any of 'x' [n][nSamples][xdim][T], 'y' [n][nSamples][ydim][T] (uint16: y ~ Poisson(exp(d + C x)) per bin), 'count_sum'
+    [n][nSamples][ydim] (the counts of a draw summed over the trial's bins) and 'noise' (the standard normals used).  With trials of unequal
+    length 'x' and 'y' are lists of arrays cut to each trial's own T_r bins.  Draw s of a trial is a pure function of (seed, trial, s)."""
+    from . import _session, inference
+    want = tuple(want)
+    unknown = [k for k in want if k not in _SAMPLE_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_SAMPLE_KEYS)))
+    if not want:
+        raise ValueError('nothing asked for: want is empty')
+    if int(nSamples) != nSamples or int(nSamples) < 1:
+        raise ValueError('nSamples = %r: a count of draws per trial, at least 1' % (nSamples,))
+    xdim = np.shape(params['C'])[1]
+    sess, trial_idx = _session.session_for(experiment, xdim)
+    if sess.comm_ready:
+        raise NotImplementedError('posteriorSamples does not support sharded sessions: every rank holds the posterior of its own trials only')
+    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
+    if idx.size == 0:
+        raise ValueError('empty trial list')
+    if infRes is None:
+        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
+    else:
+        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
+            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
+        covered = set(infRes.trial_idx.tolist())
+        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
+        if stale:
+            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
+    dev = sess.ctx.posterior_sample(idx, n_samples=int(nSamples), seed=int(seed), want=want)
+    out = {}
+    for k in want:
+        arr = dev[k]
+        if k in ('x', 'y') and sess.lengths is not None:
+            lens = [int(sess.lengths[int(t)]) for t in idx]
+            if any(L != sess.T for L in lens):
+                arr = [np.ascontiguousarray(arr[i][:, :, :L]) for i, L in enumerate(lens)]
+        out[k] = arr
+    return out
+
+
 # -- latent-dimensionality cross-validation (reference util.py:180-275) -------------------------------------
 def splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials):
     """First numTrainingTrials trials / the numTestTrials after them, as shallow copies (reference util.py:263-275)."""

@@ -186,7 +186,8 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * "last_cold_restarts", "last_retry_ms" (time of the dense retry pass), "last_fallback_no_descent" / "last_fallback_line_search" /
  * "last_fallback_outer_cap" (slots the shared-preconditioner Newton phase gave up on, by reason); of the context: "plans" and "plan_ms_total"
  * (workspace plans made and their time), "arena_grow_ms_total" (of it: mapping memory), "set_params_calls"; "trial_lengths_set" (1 while
- * pgpfa_set_trial_lengths has given the trials bin counts of their own, 0 when every trial has T bins). */
+ * pgpfa_set_trial_lengths has given the trials bin counts of their own, 0 when every trial has T bins); "observed_set" (1 while pgpfa_set_observed has marked (trial, neuron) pairs as not recorded, else 0);
+ * "last_cd_unobserved_neurons" (neurons without an observed trial in the list of the last (C,d) M-step pass). */
 int pgpfa_get_info(pgpfa_ctx* ctx, const char* key, double* value);
 
 /* ---- data ---------------------------------------------------------------------- */
@@ -206,6 +207,15 @@ int pgpfa_upload_counts_u16(pgpfa_ctx* ctx, const uint16_t* Y);
  * dual-variational entry points, pgpfa_loo_predict and pgpfa_generate do not know the lengths and fail while a table is set (info key
  * "trial_lengths_set"). */
 int pgpfa_set_trial_lengths(pgpfa_ctx* ctx, const int32_t* len /* [R], NULL: all T */);
+/* Neurons unobserved on some trials (sessions that share only part of their population): obs[R][q], non-zero = neuron n was recorded on trial r;
+ * NULL: every neuron is observed on every trial again (drops the table).  Called after the counts are uploaded.  The call fails, naming the first
+ * offender, when a trial has no observed neuron, a neuron is observed on no trial, or a count at an unobserved (trial, neuron) row is non-zero; counts
+ * uploaded while a table is set are checked again.  An unobserved pair carries no likelihood term: the Laplace posterior, objective and evidence of
+ * trial r are those of the model with only the observed rows of C, d and Y; the (C,d) M-step sums run over observed pairs (and keep the 1/numTrials
+ * of the reference); the timescale M-step is untouched.  A neuron without an observed trial in the list of an M-step pass has zero gradient, Hessian and
+ * step (only a prior moves it).  With no table every kernel takes the branch it took before.  The dual-variational entry points, pgpfa_loo_predict and
+ * pgpfa_generate do not know the table and fail while it is set (info key "observed_set"). */
+int pgpfa_set_observed(pgpfa_ctx* ctx, const uint8_t* obs /* [R][q], non-zero = observed; NULL: all observed, drops the table */);
 /* resident counts of the listed trials (idx NULL: all) as uint16 [n][q][T] */
 int pgpfa_get_counts_u16(pgpfa_ctx* ctx, int n, const int32_t* idx, uint16_t* out);
 /* params = {'C': [q][p], 'd': [q], 'tau': [p] seconds} (engine.py:40-44).  Builds the p Gram

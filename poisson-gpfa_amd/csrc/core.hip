@@ -981,6 +981,8 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   c->info["n_pad"] = c->npad;
   c->info["counts_two_bytes"] = 0.0;
   c->info["trial_lengths_set"] = 0.0;
+  c->info["observed_set"] = 0.0;
+  c->info["last_cd_unobserved_neurons"] = 0.0;
   c->info["arena_bytes"] = 0.0;
   c->info["last_eps_wt_norm"] = 0.0;
   c->info["last_eps_wt_rms"] = 0.0;
@@ -1006,6 +1008,7 @@ int pgpfa_destroy(pgpfa_ctx* c) {
   if (c->split_buf) hipFree(c->split_buf);
   if (c->Yhi) hipFree(c->Yhi);
   if (c->trial_len) hipFree(c->trial_len);
+  if (c->obs) hipFree(c->obs);
   arena_release(c);
   if (c->hbuf) hipHostFree(c->hbuf);
   if (c->dl_stage) hipHostFree(c->dl_stage);
@@ -1295,6 +1298,100 @@ int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
   return 0;
 }
 
+// ---- neurons unobserved on some trials -------------------------------------------------------------------------------------------
+static void drop_observed(pgpfa_ctx* c) {
+  if (c->obs) {
+    hipStreamSynchronize(c->st);
+    hipFree(c->obs);
+    c->bytes -= (size_t)c->R * c->q;
+    c->obs = nullptr;
+  }
+  c->obs_h.clear();
+  c->info["observed_set"] = 0.0;
+}
+
+int refuse_observed(const pgpfa_ctx* c, const char* entry) {
+  if (c && c->obs)
+    return fail("%s does not support unobserved neurons yet: an observation table is set (pgpfa_set_observed) and the unobserved rows "
+                "would be treated as silent neurons", entry);
+  return 0;
+}
+
+// cnt[r] = number of non-zero counts of trial r at rows n with obs[r][n] == 0 (either byte plane).  grid = R, block = 256 (a wave per neuron row)
+static __global__ __launch_bounds__(256) void unobserved_counts_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const uint8_t* __restrict__ obs,
+                                                                       int q, int T, int* __restrict__ cnt) {
+  __shared__ int red[4];
+  const size_t r = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bad = 0;
+  for (int n = wave; n < q; n += 4) {
+    if (obs[r * q + n]) continue;                           // (uniform over the wave)
+    const size_t base = (r * q + n) * T;
+    for (int t = lane; t < T; t += 64) bad += (Y[base + t] != 0) || (Yhi && Yhi[base + t] != 0);
+  }
+  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
+  if (lane == 0) red[wave] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[r] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// the resident counts against a device table: fails, naming the first trial, on a non-zero count at an unobserved row
+static int check_unobserved_counts(pgpfa_ctx* c, const uint8_t* dobs) {
+  int* dcnt = nullptr;
+  if (hipMalloc((void**)&dcnt, (size_t)c->R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail("hipMalloc failed"); }
+  std::vector<int> bad(c->R, 0);
+  hipLaunchKernelGGL(unobserved_counts_kernel, dim3(c->R), dim3(256), 0, c->st, c->Y, c->Yhi, dobs, c->q, c->T, dcnt);
+  hipMemcpyAsync(bad.data(), dcnt, (size_t)c->R * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  const hipError_t e = hipStreamSynchronize(c->st);
+  hipFree(dcnt);
+  if (e != hipSuccess || hipGetLastError() != hipSuccess) return fail("pgpfa_set_observed: %s", hipGetErrorString(e));
+  for (int r = 0; r < c->R; ++r)
+    if (bad[r]) return fail("trial %d: %d non-zero counts at unobserved neurons: the count tensor must be zero at the rows the table marks as not recorded", r, bad[r]);
+  return 0;
+}
+
+int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
+  if (!c) return fail("null context");
+  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_observed checks them");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  if (!obs) {                                               // back to fully observed trials; what was computed under the table is stale
+    if (c->obs) { drop_observed(c); counts_changed(c, nullptr); }
+    return 0;
+  }
+  const size_t nq = (size_t)c->R * c->q;
+  std::vector<uint8_t> ov(nq);
+  for (size_t i = 0; i < nq; ++i) ov[i] = obs[i] ? 1 : 0;
+  for (int r = 0; r < c->R; ++r) {
+    int seen = 0;
+    for (int n = 0; n < c->q; ++n) seen += ov[(size_t)r * c->q + n];
+    if (!seen) return fail("trial %d has no observed neuron", r);
+  }
+  for (int n = 0; n < c->q; ++n) {
+    int seen = 0;
+    for (int r = 0; r < c->R; ++r) seen += ov[(size_t)r * c->q + n];
+    if (!seen) return fail("neuron %d is observed on no trial", n);
+  }
+  uint8_t* dobs = nullptr;
+  HIPC(hipMalloc((void**)&dobs, nq));
+  hipMemcpyAsync(dobs, ov.data(), nq, hipMemcpyHostToDevice, c->st);
+  if (check_unobserved_counts(c, dobs)) { hipFree(dobs); return 1; }
+  drop_observed(c);
+  c->obs = dobs;
+  c->bytes += nq;
+  c->obs_h.swap(ov);
+  c->info["observed_set"] = 1.0;
+  counts_changed(c, nullptr);                               // sums and posteriors computed under another table are stale
+  return 0;
+}
+
+// counts uploaded while a table is set must be zero at its unobserved rows; on failure the context has no counts (the caller uploads again)
+static int recheck_observed(pgpfa_ctx* c) {
+  if (!c->obs) return 0;
+  if (check_unobserved_counts(c, c->obs)) { c->have_counts = false; return 1; }
+  return 0;
+}
+
 int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
   if (!c || !Y) return fail("null argument");
   HIPC(hipSetDevice(c->device));
@@ -1305,7 +1402,7 @@ int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = 0.0;
-  return 0;
+  return recheck_observed(c);
 }
 
 // counts from a host array of TS (double or uint16): validated and split into byte planes on the device, staged in pieces
@@ -1353,7 +1450,7 @@ static int upload_counts_wide(pgpfa_ctx* c, const TS* Y) {
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = c->Yhi ? 1.0 : 0.0;
-  return 0;
+  return recheck_observed(c);
 }
 
 int pgpfa_upload_counts_f64(pgpfa_ctx* c, const double* Y) {

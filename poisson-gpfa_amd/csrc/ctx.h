@@ -99,6 +99,10 @@ struct pgpfa_ctx {
   // Poisson pass and the (C,d) passes; the GP prior, the solvers and the covariance engines still span all T bins.  NULL: every trial has T bins.
   int* trial_len = nullptr;                      // device [R]
   std::vector<int> trial_len_h;                  // host copy (count_moments); empty while trial_len is NULL
+  // Neurons not recorded on some trials (pgpfa_set_observed): obs[r * q + n] == 0 marks a (trial, neuron) pair without a likelihood term - zero counts
+  // (checked), no rate in the Poisson pass, the cold objective and the (C,d) passes.  NULL: every neuron is observed on every trial.
+  uint8_t* obs = nullptr;                        // device [R][q]
+  std::vector<uint8_t> obs_h;                    // host copy (neurons without an observed trial in an M-step list); empty while obs is NULL
   double *C = nullptr, *d = nullptr, *tau = nullptr;
   double *Kpad = nullptr, *Kinv = nullptr;      // [p][Tp][Tp]
   double* Xmode = nullptr;                       // [R][p][T]   post_mean / warm start
@@ -439,6 +443,7 @@ int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
 int resolve_trials(pgpfa_ctx* c, int n, const int32_t* idx, Trials* out, bool distinct = false);
 void counts_changed(pgpfa_ctx* c, const std::vector<int>* trials);
+int refuse_observed(const pgpfa_ctx* c, const char* entry);           // fails while an observation table is set: entry points that do not know it
 int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry);      // fails while per-trial bin counts are set: entry points that do not know them
 int ensure_high_plane(pgpfa_ctx* c);
 int ready(pgpfa_ctx* c);

@@ -62,12 +62,13 @@ inline __global__ __launch_bounds__(256) void dual_pre_kernel(const uint8_t* __r
 // Rates pass of the GEMM form of the Poisson pass (latent widths beyond the matrix-core kernel's 16): for the listed slots
 //   h = C x + d [+ off],  lam = exp(h),  lmy = lam - y,  partial objective sum_n,t lam - y h per (slot, 64-bin tile)
 // - the q x p x T product as a vector kernel (2 % of the flops of the pass: W_t = C^T diag(lam_t) C and C^T (lam - y) follow as the GEMMs of the dual
-// evaluation against the pair / loading table).  len (may be NULL): per-trial bin counts, bins behind them get lam = lmy = 0.  grid = (ceil(T/64), nslots), block = 256 (lanes = bins, the 4 waves take interleaved neurons).
+// evaluation against the pair / loading table).  len (may be NULL): per-trial bin counts, bins behind them get lam = lmy = 0; obs (may be NULL): [R][q] bytes,
+// rows of neurons not recorded on the trial get lam = lmy = 0 likewise.  grid = (ceil(T/64), nslots), block = 256 (lanes = bins, the 4 waves take interleaved neurons).
 inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C,
                                                          const double* __restrict__ d, const double* __restrict__ X, long long sX,
                                                          const double* __restrict__ off, double* __restrict__ lam, double* __restrict__ lmy,
                                                          double* __restrict__ fpart, const int* __restrict__ slots,
-                                                         const int* __restrict__ trial_of_slot, const int* __restrict__ len, int q, int p, int T) {
+                                                         const int* __restrict__ trial_of_slot, const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int p, int T) {
   extern __shared__ double rw_x[];                 // [p][64]
   __shared__ double red[4];
   const size_t slot = slots[blockIdx.y];
@@ -76,6 +77,7 @@ inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* _
   const int t0 = blockIdx.x * 64, t = t0 + lane;
   const bool valid = t < T;
   const int Tl = len ? len[trial] : T;             // bins of this trial with a likelihood term (no table: all T)
+  const uint8_t* ob = obs ? obs + trial * q : nullptr;   // (uniform over the workgroup; no table: every neuron observed)
   for (int e = threadIdx.x; e < p * 64; e += 256) {
     const int l = e >> 6, tt = t0 + (e & 63);
     rw_x[e] = tt < T ? X[slot * sX + (size_t)l * T + tt] : 0.0;
@@ -85,7 +87,7 @@ inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* _
   if (valid) {
     for (int n = wave; n < q; n += 4) {
       const size_t e = slot * (size_t)q * T + (size_t)n * T + t;
-      if (t >= Tl) {                                // a padded bin: no rate and no count - zero rows of the products that follow
+      if (t >= Tl || (ob && ob[n] == 0)) {          // a padded bin or an unobserved neuron: no rate and no count - zero rows of the products that follow
         lam[e] = 0.0;
         lmy[e] = 0.0;
         continue;

@@ -64,6 +64,7 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
 
 int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost, double* grad) {
   CHK(refuse_trial_lengths(c, "pgpfa_dual_costgrad"));
+  CHK(refuse_observed(c, "pgpfa_dual_costgrad"));
   if (c && c->have_counts && c->have_params && c->dual_lowrank && want_lowrank(c)) {
     // the low-rank engine is the batched evaluation with one trial
     const int32_t t = trial;
@@ -108,6 +109,7 @@ int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost
 // VIPostMean (inference.py:193-194): -K_big C_big (lambda - y) for one trial, latent-major [p*T].
 int pgpfa_dual_post_mean(pgpfa_ctx* c, int trial, const double* lam, double* mean) {
   CHK(refuse_trial_lengths(c, "pgpfa_dual_post_mean"));
+  CHK(refuse_observed(c, "pgpfa_dual_post_mean"));
   CHK(ready(c));
   if (!lam || !mean) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
@@ -157,6 +159,7 @@ static int dual_post_cov_dev(pgpfa_ctx* c, double* cov, double* prec) {
 
 int pgpfa_dual_post_cov(pgpfa_ctx* c, int trial, const double* lam, double* cov, double* prec) {
   CHK(refuse_trial_lengths(c, "pgpfa_dual_post_cov"));
+  CHK(refuse_observed(c, "pgpfa_dual_post_cov"));
   CHK(ready(c));
   if (!lam || !cov) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
@@ -311,6 +314,7 @@ int pgpfa_dual_fixed_point(pgpfa_ctx* c, int n, const int32_t* idx, double* rho,
                            int32_t* vstatus, double* lam_out) {
   if (!c) return fail("null context");
   CHK(refuse_trial_lengths(c, "pgpfa_dual_fixed_point"));
+  CHK(refuse_observed(c, "pgpfa_dual_fixed_point"));
   if (!fopt || !vstatus) return fail("null argument");
   if (max_outer < 1 || !(tol > 0.0)) return fail("max_outer and tol must be positive");
   if (start < 0 || start > 3) return fail("start must be 0 (cold), 1 (rho is the start), 2 (rho is a previous optimum) or 3 (the resident optimum)");
@@ -350,6 +354,7 @@ int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const dou
   PhaseRange range_phase("pgpfa.dual_costgrad_batch");
   if (!c) return fail("null context");
   CHK(refuse_trial_lengths(c, "pgpfa_dual_costgrad_batch"));
+  CHK(refuse_observed(c, "pgpfa_dual_costgrad_batch"));
   if (!lam || !cost) return fail("null argument");
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
@@ -382,6 +387,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
   PhaseRange range_phase("pgpfa.dual_lbfgs");
   if (!c) return fail("null context");
   CHK(refuse_trial_lengths(c, "pgpfa_dual_lbfgs"));
+  CHK(refuse_observed(c, "pgpfa_dual_lbfgs"));
   if (!rho || !fopt) return fail("null argument");
   if (max_iter < 1) return fail("max_iter must be positive");
   Trials tr;
@@ -598,6 +604,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
 int pgpfa_get_dual_lambda(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {
   if (!c || !out) return fail("null argument");
   CHK(refuse_trial_lengths(c, "pgpfa_get_dual_lambda"));
+  CHK(refuse_observed(c, "pgpfa_get_dual_lambda"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   HIPC(hipSetDevice(c->device));
@@ -615,6 +622,7 @@ int pgpfa_dual_finalize(pgpfa_ctx* c, int n, const int32_t* idx, const double* l
   PhaseRange range_phase("pgpfa.dual_finalize");
   if (!c) return fail("null context");
   CHK(refuse_trial_lengths(c, "pgpfa_dual_finalize"));
+  CHK(refuse_observed(c, "pgpfa_dual_finalize"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
   const int N = (int)tr.v.size();

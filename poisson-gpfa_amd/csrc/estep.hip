@@ -16,6 +16,10 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   a.fpart = c->fpart; a.slots = d_list; a.trial_of_slot = c->trial_of_slot;
   a.mask = c->mask_active ? c->mask_of_slot : nullptr;
   a.len = c->trial_len;                                          // NULL unless pgpfa_set_trial_lengths gave the trials bin counts of their own
+  // NULL unless pgpfa_set_observed marked (trial, neuron) pairs as not recorded.  Only the kernels that evaluate exp(h) read the table: the counts at
+  // unobserved rows are zero (checked when the table is set), so the count terms (cd_ym_*, count_moments_kernel) and everything behind this pass - the
+  // PCG, both covariance engines, the evidence, the single-precision covariance phase, rates and samples - see G, W and the objective of the reduced model.
+  a.obs = c->obs;
   a.off = c->var_active ? c->voff : nullptr; a.sOff = (long long)c->q * c->T;
   a.lam_out = c->lam_out_active ? c->lamd : nullptr; a.sLam = (long long)c->q * c->T;
   a.q = c->q; a.p = c->p; a.T = c->T; a.ntile = (c->T + 63) / 64; a.full = full;
@@ -31,7 +35,7 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
     CHK(ensure_lambda(c));
     prof_begin(c, TAG_POISSON, fl);
     hipLaunchKernelGGL(rates_wide_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
-                       a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->q, c->p, c->T);
+                       a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->obs, c->q, c->p, c->T);
     prof_end(c);
     if (full) {
       const int np = c->p * (c->p + 1) / 2;
@@ -61,14 +65,21 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
     dispatch_pw(c->p, [&](auto pm) {
       constexpr int PW = decltype(pm)::value;
       if constexpr (PW <= 10) {
-        if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        if (a.obs) {                                              // (the instantiations that read the observation table)
+          if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+          else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        } else if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
         else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
       } else if constexpr (PW <= 16) {
-        hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        if (a.obs) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
       }
     });
   } else {
-    dispatch_pw(c->p, [&](auto pm) { hipLaunchKernelGGL(poisson_pass_kernel<decltype(pm)::value>, grid, block, 0, c->st, a); });
+    dispatch_pw(c->p, [&](auto pm) {
+      if (a.obs) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, true>), grid, block, 0, c->st, a);
+      else hipLaunchKernelGGL(poisson_pass_kernel<decltype(pm)::value>, grid, block, 0, c->st, a);
+    });
   }
   prof_end(c);
   hipLaunchKernelGGL(sum_tiles_kernel, dim3((nl + 255) / 256), dim3(256), 0, c->st, c->fpart, a.ntile, d_list, nl, flik);
@@ -376,10 +387,11 @@ static int shared_factor(pgpfa_ctx* c, int nb) {
 // The reference's negative log-posterior (inference.py:12-32) of a slot's trial AT x = 0: f0 = sum_n (T exp(d_n) - d_n sum_t y_nt), the objective of
 // the cold start - what a warm start has to beat (estep_impl: a start point that does worse is replaced by zero).  One pass over the slot's count
 // rows (q T bytes).  grid = (slots), block = 256 (a wave per neuron row); mask (may be null): the neuron a leave-one-out item leaves out;
-// len (may be null): per-trial bin counts - a trial of T_r bins has f0 = sum_n (T_r exp(d_n) - d_n sum_t y_nt).
+// len (may be null): per-trial bin counts - a trial of T_r bins has f0 = sum_n (T_r exp(d_n) - d_n sum_t y_nt);
+// obs (may be null): [R][q] bytes - the sum runs over the neurons recorded on the trial.
 static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ d,
                                                                     const int* __restrict__ trial_of_slot, const int* __restrict__ mask,
-                                                                    const int* __restrict__ len, int q, int T, double* __restrict__ f0) {
+                                                                    const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int T, double* __restrict__ f0) {
   __shared__ double red[4];
   const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t base = (size_t)trial_of_slot[s] * q * T;
@@ -388,6 +400,7 @@ static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_
   double acc = 0.0;
   for (int n = wave; n < q; n += 4) {
     if (n == skip) continue;
+    if (obs && obs[(size_t)trial_of_slot[s] * q + n] == 0) continue;   // (uniform over the wave)
     unsigned cnt = 0;
     const uint8_t* row = Y + base + (size_t)n * T;
     for (int t = lane; t < T; t += 64) cnt += row[t];
@@ -616,7 +629,7 @@ static int eval_start_guarded(pgpfa_ctx* c, Chunk& ch, bool guard, EstepStats& s
   if (guard) {
     // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
     hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
-                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->q, c->T, c->sc_alpha);
+                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->obs, c->q, c->T, c->sc_alpha);
     CHK(dl_enqueue(c, ch.ftry.data(), c->sc_alpha, nb * sizeof(double)));
   }
   CHK(eval_start(c, ch));
@@ -1511,6 +1524,7 @@ int pgpfa_get_log_evidence(pgpfa_ctx* c, int n, const int32_t* idx, double* out)
 int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, double* err_sum) {
   if (!c || !y_pred || !err_sum) return fail("null argument");
   CHK(refuse_trial_lengths(c, "pgpfa_loo_predict"));
+  CHK(refuse_observed(c, "pgpfa_loo_predict"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   const int q = c->q, T = c->T;

@@ -185,11 +185,16 @@ struct PoissonArgs {
   const double* off; long long sOff;
   double* lam_out; long long sLam;
   int q, p, T, ntile, full;
+  // optional [R][q], beside len: non-zero = the neuron was recorded on the trial (NULL: all); an unobserved row has no rate and no count.
+  // (Last in the struct: the kernel-argument offsets of the fields above, and with them the code of the kernels without a table, stay what they were.)
+  const uint8_t* obs;
 };
 
 constexpr int PNC = 32;
 
-template <int PMAX>
+// OBS: the instantiation launched while an observation table is set (pgpfa_set_observed); without one the kernel is the code it was (the narrow widths
+// sit at the scalar-register class of their occupancy, which a run-time test of one more pointer costs them)
+template <int PMAX, bool OBS = false>
 __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(PoissonArgs a) {
   constexpr int NK = (PMAX > 16) ? 2 : 1;
   __shared__ double E[PNC][64];
@@ -227,7 +232,11 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
     for (int nn = ty; nn < PNC; nn += KY) {
       const int n = n0 + nn;
       double e = 0.0, r = 0.0;
-      if (n < q && lik && n != held_out) {
+      // a neuron not recorded on the trial has no rate and no count: e = r = 0 and no objective term (a wave holds one neuron - blockDim.x = 64 - so the
+      // table's byte is a scalar and the test a uniform branch)
+      bool seen = true;
+      if (OBS && n < q) seen = __builtin_amdgcn_readfirstlane((int)a.obs[(size_t)trial * q + __builtin_amdgcn_readfirstlane(n)]) != 0;
+      if (n < q && lik && n != held_out && seen) {
         double h = a.d[n];
         if (a.off) h += a.off[(size_t)slot * a.sOff + (size_t)n * T + t];
         const double* Cn = a.C + (size_t)n * p;
@@ -280,6 +289,10 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
       }
     }
   }
+  // the rate plane of an unobserved row is 0 (written here, behind the accumulators' last use, so that the neuron loop keeps its registers)
+  if (OBS && a.lam_out && lik)
+    for (int n = ty; n < q; n += KY)
+      if (a.obs[(size_t)trial * q + n] == 0) a.lam_out[(size_t)slot * a.sLam + (size_t)n * T + t] = 0.0;
   // deterministic block reduction of the objective partial: lanes, then waves in order
   for (int off = 32; off > 0; off >>= 1) facc += __shfl_down(facc, off);
   if (tx == 0) fred[ty] = facc;
@@ -320,7 +333,8 @@ inline __global__ void poisson_tables_kernel(const double* __restrict__ C, int q
 // 0.58 ms at NBT = 2.  (One copy of the neuron tile's tables per WORKGROUP in LDS on top of that - 10 KB, double-buffered, one barrier per neuron
 // tile, every fragment read conflict-free - ran 0.60 ms: at two tiles per wave the fragments are no longer what bounds the pass.  Dropped.)
 // grid = (ceil(T / (64 NBT)), nslots); fpart holds gridDim.x partial sums per slot.
-template <int PW, int NBT>
+// OBS: the instantiation launched while an observation table is set (pgpfa_set_observed); without one the kernel is the code it was, register for register
+template <int PW, int NBT, bool OBS = false>
 __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, const double* __restrict__ CCu, const double* __restrict__ C16, int qpad) {
   constexpr int NP = PW * (PW + 1) / 2, NT = (NP + 15) / 16, NC = NT * 16, KS = (PW + 3) / 4;
   __shared__ double Wl[4][16 * PW * PW];
@@ -336,6 +350,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
   const double* X = a.X + (size_t)slot * a.sX;
   const uint8_t* Y = a.Y + (size_t)trial * q * T;
   const uint8_t* Yh = a.Yhi ? a.Yhi + (size_t)trial * q * T : nullptr;
+  const uint8_t* ob = OBS ? a.obs + (size_t)trial * q : nullptr;    // the trial's row of the observation table
 
   double xb[NBT][KS];
   int tcl[NBT];
@@ -379,11 +394,13 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
       double dv[NBT][4];
       unsigned yv[NBT][4];
       double ch[KS];
+      unsigned seen = 0xfu;                                       // bit r: this lane's neuron of register r was recorded on the trial (one register per lane)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = nb0 + l4 + 4 * r;
         const int nc = n < q ? n : q - 1;
         dn[r] = a.d[nc];
+        if constexpr (OBS) seen &= ~((unsigned)(ob[nc] == 0) << r);   // (the byte rides with the tile's other clamped loads: once per neuron tile and lane)
 #pragma unroll
         for (int bt = 0; bt < NBT; ++bt) {
           dv[bt][r] = dn[r];
@@ -415,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = nb0 + l4 + 4 * r;
-          const bool ok = (n < q) && (sbase0 + 16 * bt + l15 < Tl) && (n != held_out);
+          const bool ok = (n < q) && (sbase0 + 16 * bt + l15 < Tl) && (n != held_out) && (!OBS || ((seen >> r) & 1u));
           const double y = ok ? (double)yv[bt][r] : 0.0;
           const double ev = ok ? exp(h[r]) : 0.0;
           e[r] = ev;
@@ -1052,13 +1069,24 @@ struct CdArgs {
   double* part;          // [gridDim.y][p+2][q]
   int q, p, T;
   int dbg;               // timing experiments only (option cd_debug): bit 0 no exp, bit 1 no second product, bit 2 no first product, bit 3 no staging
+  // optional [R][q], beside len: non-zero = the neuron was recorded on the trial (NULL: all); an unobserved (trial, neuron) pair adds nothing to any sum.
+  // (Last in the struct: the kernel-argument offsets of the fields above, and with them the code of the kernels without a table, stay what they were.)
+  const uint8_t* obs;
 };
+// `live` of a lane's neuron for one (trial, tile) item.  OBS - the instantiations launched while an observation table is set (pgpfa_set_observed): the
+// neuron must also be recorded on the item's trial, one byte per item behind a wave-uniform row base.  Without a table the kernels are the code they
+// were, register for register: most of them sit at the 102-SGPR ceiling, where the two scalars of a run-time test of the pointer spill into vector registers.
+template <bool OBS>
+__device__ __forceinline__ bool cd_item_live(const CdArgs& a, size_t r, int n, bool live) {
+  if constexpr (!OBS) return live;
+  else return live && (a.obs + (size_t)__builtin_amdgcn_readfirstlane((int)r) * a.q)[n] != 0;
+}
 constexpr int CD_KY = 8;
 // waves per workgroup of mstep_cd_kernel: 8 up to 16 latents (128-register budget), 4 beyond (c, acc, u of 20+ doubles each need the 256 budget)
 template <int PW> struct CdKy { static constexpr int v = (PW <= 16) ? 8 : 4; };
 template <int PW> struct CdTile { static constexpr int TT = (PW <= 10) ? 64 : (PW <= 16) ? 32 : (PW <= 20) ? 16 : 8; };
 
-template <int PW>
+template <int PW, bool OBS = false>
 __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
   constexpr int KYW = CdKy<PW>::v;
   constexpr int TT = CdTile<PW>::TT;
@@ -1109,6 +1137,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
       Yt[nn * YS + t] = (n0 + nn < q && t < tn) ? (uint16_t)count_at(Y, Yh, (size_t)(n0 + nn) * T + t0 + t) : (uint16_t)0;
     }
     __syncthreads();
+    const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
     for (int t = ty; t < tn; t += KYW) {
       // u = V_t c from the lower triangle only (V_t is symmetric): p(p+1)/2 LDS reads instead of p^2
       double u[PW];
@@ -1133,7 +1162,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
       const double rs = y - yh;
-      if (live) {
+      if (on) {
         cost += y * hh - yh;
         dd += rs;
 #pragma unroll
@@ -1170,7 +1199,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
 // part layout per block: [NH][q], NH = 1 + (p+1) + (p+1)(p+2)/2 : cost | grad (c.., d) | packed lower Hessian
 // --------------------------------------------------------------------------------------------------
 constexpr int CDH_KY = 4;      // 4 waves per block: the whole 512-register file per lane for the (p+1)(p+2)/2 Hessian accumulators
-template <int PW>
+template <int PW, bool OBS = false>
 __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
   constexpr int TT = CdTile<PW>::TT;
   constexpr int YS = TT + 4;
@@ -1223,6 +1252,7 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
       Yt[nn * YS + t] = (n0 + nn < q && t < tn) ? (uint16_t)count_at(Y, Yh, (size_t)(n0 + nn) * T + t0 + t) : (uint16_t)0;
     }
     __syncthreads();
+    const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
     for (int t = ty; t < tn; t += CDH_KY) {
       double w[D];
       double hh = dn, rho = 0.0;
@@ -1249,7 +1279,7 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
       w[PW] = 1.0;
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
-      if (live) {
+      if (on) {
         cost += y * hh - yh;
 #pragma unroll
         for (int k = 0; k < PW; ++k) gacc[k] -= y * Mt[k][t] - yh * w[k];
@@ -1319,7 +1349,7 @@ constexpr int cd_group_entries(int D, int NG, int G) {
   return n;
 }
 
-template <int PW, int NG, int G>
+template <int PW, int NG, int G, bool OBS>
 __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[PW * PW], double (*Mt)[CdTile<PW>::TT], uint16_t* Yt,
                                                   double (*red)[64]) {
   constexpr int TT = CdTile<PW>::TT;
@@ -1370,6 +1400,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
       Yt[nn * YS + t] = (n0 + nn < q && t < tn) ? (uint16_t)count_at(Y, Yh, (size_t)(n0 + nn) * T + t0 + t) : (uint16_t)0;
     }
     __syncthreads();
+    const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
     for (int t = ty; t < tn; t += CDH_KY) {
       double w[D];
       double hh = dn, rho = 0.0;
@@ -1395,7 +1426,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
       w[PW] = 1.0;
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
-      if (live) {
+      if (on) {
         if (G == 0) {
           cost += y * hh - yh;
 #pragma unroll
@@ -1457,7 +1488,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
   }
 }
 
-template <int PW, int NG>
+template <int PW, int NG, bool OBS = false>
 __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_rows_kernel(CdArgs a) {
   constexpr int TT = CdTile<PW>::TT;
   __shared__ __attribute__((aligned(16))) double Vt[TT][PW * PW];
@@ -1466,28 +1497,28 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_rows_kernel(CdArgs 
   __shared__ double red[CDH_KY][64];
   const int g = blockIdx.z;
   if constexpr (NG == 2) {
-    if (g == 0) cd_hess_rows_body<PW, NG, 0>(a, Vt, Mt, Yt, red);
-    else cd_hess_rows_body<PW, NG, 1>(a, Vt, Mt, Yt, red);
+    if (g == 0) cd_hess_rows_body<PW, NG, 0, OBS>(a, Vt, Mt, Yt, red);
+    else cd_hess_rows_body<PW, NG, 1, OBS>(a, Vt, Mt, Yt, red);
   } else if constexpr (NG == 3) {
-    if (g == 0) cd_hess_rows_body<PW, NG, 0>(a, Vt, Mt, Yt, red);
-    else if (g == 1) cd_hess_rows_body<PW, NG, 1>(a, Vt, Mt, Yt, red);
-    else cd_hess_rows_body<PW, NG, 2>(a, Vt, Mt, Yt, red);
+    if (g == 0) cd_hess_rows_body<PW, NG, 0, OBS>(a, Vt, Mt, Yt, red);
+    else if (g == 1) cd_hess_rows_body<PW, NG, 1, OBS>(a, Vt, Mt, Yt, red);
+    else cd_hess_rows_body<PW, NG, 2, OBS>(a, Vt, Mt, Yt, red);
   } else if constexpr (NG == 4) {
-    if (g == 0) cd_hess_rows_body<PW, NG, 0>(a, Vt, Mt, Yt, red);
-    else if (g == 1) cd_hess_rows_body<PW, NG, 1>(a, Vt, Mt, Yt, red);
-    else if (g == 2) cd_hess_rows_body<PW, NG, 2>(a, Vt, Mt, Yt, red);
-    else cd_hess_rows_body<PW, NG, 3>(a, Vt, Mt, Yt, red);
+    if (g == 0) cd_hess_rows_body<PW, NG, 0, OBS>(a, Vt, Mt, Yt, red);
+    else if (g == 1) cd_hess_rows_body<PW, NG, 1, OBS>(a, Vt, Mt, Yt, red);
+    else if (g == 2) cd_hess_rows_body<PW, NG, 2, OBS>(a, Vt, Mt, Yt, red);
+    else cd_hess_rows_body<PW, NG, 3, OBS>(a, Vt, Mt, Yt, red);
   } else {
     static_assert(NG == 8, "row groups: 2, 3, 4 or 8");
     switch (g) {
-      case 0: cd_hess_rows_body<PW, NG, 0>(a, Vt, Mt, Yt, red); break;
-      case 1: cd_hess_rows_body<PW, NG, 1>(a, Vt, Mt, Yt, red); break;
-      case 2: cd_hess_rows_body<PW, NG, 2>(a, Vt, Mt, Yt, red); break;
-      case 3: cd_hess_rows_body<PW, NG, 3>(a, Vt, Mt, Yt, red); break;
-      case 4: cd_hess_rows_body<PW, NG, 4>(a, Vt, Mt, Yt, red); break;
-      case 5: cd_hess_rows_body<PW, NG, 5>(a, Vt, Mt, Yt, red); break;
-      case 6: cd_hess_rows_body<PW, NG, 6>(a, Vt, Mt, Yt, red); break;
-      default: cd_hess_rows_body<PW, NG, 7>(a, Vt, Mt, Yt, red); break;
+      case 0: cd_hess_rows_body<PW, NG, 0, OBS>(a, Vt, Mt, Yt, red); break;
+      case 1: cd_hess_rows_body<PW, NG, 1, OBS>(a, Vt, Mt, Yt, red); break;
+      case 2: cd_hess_rows_body<PW, NG, 2, OBS>(a, Vt, Mt, Yt, red); break;
+      case 3: cd_hess_rows_body<PW, NG, 3, OBS>(a, Vt, Mt, Yt, red); break;
+      case 4: cd_hess_rows_body<PW, NG, 4, OBS>(a, Vt, Mt, Yt, red); break;
+      case 5: cd_hess_rows_body<PW, NG, 5, OBS>(a, Vt, Mt, Yt, red); break;
+      case 6: cd_hess_rows_body<PW, NG, 6, OBS>(a, Vt, Mt, Yt, red); break;
+      default: cd_hess_rows_body<PW, NG, 7, OBS>(a, Vt, Mt, Yt, red); break;
     }
   }
 }
@@ -1521,6 +1552,13 @@ inline __global__ void cd_newton_step_kernel(const double* __restrict__ sums, in
       if (i == j) h += (center ? inv_s2 : 0.0);
       A[i * D + j] = h;
     }
+  }
+  // A neuron without an observed trial among those of the sums (pgpfa_set_observed, an online minibatch) and without a prior: sum yhat = H_dd = 0, the
+  // whole block and the gradient are zero - the step is zero, nothing is divided by the singular block.  (With a prior only the prior acts, below.)
+  if (A[(D - 1) * D + (D - 1)] == 0.0 && !(center && inv_s2 > 0.0)) {
+    for (int i = 0; i < D; ++i) delta[(size_t)i * q + n] = 0.0;
+    dec[n] = 0.0;
+    return;
   }
   // Cholesky (lower) with a relative ridge if a pivot is not positive
   for (int j = 0; j < D; ++j) {

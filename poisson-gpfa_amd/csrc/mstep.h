@@ -227,7 +227,8 @@ struct CdK {
   static constexpr int NV = (NV0 <= 4) ? NV0 : 0;                     // leftover rows (vector ALU)
 };
 
-template <int PW>
+// OBS: the instantiation launched while an observation table is set (cd_item_live, model.h)
+template <int PW, bool OBS = false>
 __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_per_group) {
   using M = CdM<PW>;
   using K = CdK<PW>;
@@ -347,11 +348,13 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
     const int t0 = c_ti * BT;
     const int Tl = a.len ? a.len[a.trials[c_tr]] : T;
     const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;      // bins of this item inside the trial's length (<= 0: the item does nothing)
+    const int tr_item = OBS ? a.trials[c_tr] : 0;         // (the item's trial, for the observation table; read before the counters move on)
     const bool more = item + (int)gridDim.x < nitems;
     c_tr += step_tr; c_ti += step_ti;
     if (c_ti >= ntt) { c_ti -= ntt; c_tr += 1; }
     if (more && !(a.dbg & 8)) prefetch(c_tr, c_ti);     // global loads in flight while this stage is multiplied
     const double* st = lds + cur * M::LDS_DOUBLES;
+    const bool seen = cd_item_live<OBS>(a, (size_t)tr_item, nc, live);   // this lane's neuron was recorded on the item's trial (no table: live)
     if (active_wave) {
 #pragma unroll
       for (int sub = 0; sub < BT / 16; ++sub) {
@@ -373,7 +376,7 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
           double hv = h[r] + h2[r];
 #pragma unroll
           for (int i = 0; i < KV; ++i) hv += bin[4 * KSM + i] * thv[i];
-          const double e = (live && sub * 16 + 4 * r + l4 < tn) ? ((a.dbg & 1) ? 1.0 + 1e-3 * hv : exp(hv)) : 0.0;
+          const double e = (seen && sub * 16 + 4 * r + l4 < tn) ? ((a.dbg & 1) ? 1.0 + 1e-3 * hv : exp(hv)) : 0.0;
           yh[r] = e;
 #pragma unroll
           for (int i = 0; i < NV; ++i) accv[i] += bin[16 * NTM + i] * e;
@@ -501,7 +504,7 @@ __device__ __forceinline__ void cdh_swap32(double& a, double& b) {
   a = __hiloint2double((int)r1[0], (int)r0[0]); b = __hiloint2double((int)r1[1], (int)r0[1]);
 }
 
-template <int PW>
+template <int PW, bool OBS = false>
 __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs a, int tiles_per_group) {
   using M = CdM<PW>;
   using H = CdH<PW>;
@@ -616,6 +619,7 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
     const int t0 = c_ti * BT;
     const int Tl = a.len ? a.len[a.trials[c_tr]] : T;
     const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;      // bins of this item inside the trial's length (<= 0: the item does nothing)
+    const bool seen = cd_item_live<OBS>(a, (size_t)(OBS ? a.trials[c_tr] : 0), nc, live);   // this lane's neuron was recorded on the item's trial (no table: live)
     const bool more = item + (int)gridDim.x < nitems;
     c_tr += step_tr; c_ti += step_ti;
     if (c_ti >= ntt) { c_ti -= ntt; c_tr += 1; }
@@ -650,7 +654,7 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
         cdh_swap16(sb[2], sb[3]);
         double t01 = sb[0] + sb[1], t23 = sb[2] + sb[3];
         cdh_swap32(t01, t23);
-        const bool on = live && tb0 + l4 < tn;
+        const bool on = seen && tb0 + l4 < tn;
         const double yh = exp(on ? dn + (t01 + t23) : -1000.0);      // (exp(-1000) = 0: masked bins and neurons drop out of every sum)
         const double sq = sqrt(yh);
         double sqb[4];

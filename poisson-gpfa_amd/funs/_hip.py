@@ -29,6 +29,7 @@ _SIGNATURES = {
     'pgpfa_upload_counts_u8': [ct.c_void_p, c_uint8_p],
     'pgpfa_upload_counts_u16': [ct.c_void_p, ct.POINTER(ct.c_uint16)],
     'pgpfa_set_trial_lengths': [ct.c_void_p, c_int32_p],
+    'pgpfa_set_observed': [ct.c_void_p, c_uint8_p],
     'pgpfa_get_counts_u16': [ct.c_void_p, ct.c_int, c_int32_p, ct.POINTER(ct.c_uint16)],
     'pgpfa_set_params': [ct.c_void_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_get_gram': [ct.c_void_p, c_double_p],
@@ -210,6 +211,17 @@ class Context:
         if ln.shape != (self.R,):
             raise ValueError('one length per trial expected (R=%d), got %d' % (self.R, ln.size))
         check(self.lib.pgpfa_set_trial_lengths(self.h, iptr(ln)))
+
+    def set_observed(self, observed):
+        """Observation table (R, q): non-zero = neuron n was recorded on trial r; None: every neuron on every trial again.  Unobserved (trial, neuron)
+        pairs then carry no likelihood term (pgpfa_set_observed); their resident counts must be zero."""
+        if observed is None:
+            check(self.lib.pgpfa_set_observed(self.h, None))
+            return
+        ob = np.ascontiguousarray(np.asarray(observed) != 0, dtype=np.uint8)
+        if ob.shape != (self.R, self.q):
+            raise ValueError('observation table must have shape (R,q)=%s, got %s' % ((self.R, self.q), ob.shape))
+        check(self.lib.pgpfa_set_observed(self.h, ob.ctypes.data_as(c_uint8_p)))
 
     def set_params(self, C, d, tau):
         C, d, tau = as_f64(C), as_f64(d).reshape(-1), as_f64(tau).reshape(-1)

@@ -358,7 +358,7 @@ class DeviceDualOptimRes(LazyTrialList):
 
 # ----------------------------------------------------------------------------------------------
 class Session:
-    def __init__(self, Y, p, bin_ms, lengths=None):
+    def __init__(self, Y, p, bin_ms, lengths=None, observed=None):
         R, q, T = Y.shape
         self.R, self.q, self.T, self.p = R, q, T, p
         # per-trial bin counts, or None when every trial has T bins (then nothing below differs from a context without the table)
@@ -367,10 +367,16 @@ class Session:
             self.lengths = np.asarray(lengths, dtype=np.int32).reshape(-1)
             if self.lengths.shape != (R,):
                 raise ValueError('one length per trial expected')
+        # observation table (R, q) of booleans, or None when every neuron was recorded on every trial (then no table is set: the equal path)
+        self.observed = None
+        if observed is not None and not np.all(observed):
+            self.observed = check_observed(observed, R, q)
         self.ctx = _hip.Context(q, p, T, R, bin_ms, device=WORLD.device())
         self.ctx.upload_counts(Y)
         if self.lengths is not None:
             self.ctx.set_trial_lengths(self.lengths)
+        if self.observed is not None:
+            self.ctx.set_observed(self.observed)
         self.post_stamp = 0
         self.mode_stamp = 0
         self.trial_stamp = np.zeros(R, dtype=np.int64)      # post_stamp of the E-step that last wrote each trial's posterior
@@ -443,6 +449,12 @@ class Session:
             raise NotImplementedError('%s does not support trials of unequal length yet (this experiment has %d..%d bins per trial); '
                                       'only the Laplace EM path does' % (what, int(self.lengths.min()), int(self.lengths.max())))
 
+    def refuse_unobserved(self, what):
+        """Entry points that do not know the observation table must not treat the zero-filled rows of unrecorded neurons as silence."""
+        if getattr(self, 'observed', None) is not None:
+            raise NotImplementedError('%s does not support unobserved neurons yet (this experiment has %d unobserved (trial, neuron) pairs); '
+                                      'only the Laplace EM path does' % (what, int((~self.observed).sum())))
+
     def mark_dual_written(self, trial_idx):
         """A variational E-step has just overwritten the resident dual variables of these trials."""
         self.dual_stamp += 1
@@ -464,11 +476,60 @@ class Session:
 _sessions = weakref.WeakKeyDictionary()
 
 
+def check_observed(observed, R, q):
+    """The observation table as a boolean (R, q) array; ValueError on a wrong shape, a trial without an observed neuron or a neuron that no
+    trial observes (nothing has been uploaded yet when this runs)."""
+    ob = np.asarray(observed)
+    if ob.shape != (R, q):
+        raise ValueError('observation table must have shape (trials, ydim) = (%d, %d), got %s' % (R, q, ob.shape))
+    ob = ob != 0
+    empty = np.flatnonzero(~ob.any(axis=1))
+    if empty.size:
+        raise ValueError('trial %d has no observed neuron' % int(empty[0]))
+    never = np.flatnonzero(~ob.any(axis=0))
+    if never.size:
+        raise ValueError('neuron %d is observed on no trial' % int(never[0]))
+    return np.ascontiguousarray(ob)
+
+
+def _stack_observed(experiment):
+    """Observation table (R, ydim) of experiment.data, booleans: row r is data[r]['observed'] (all True for a trial without the key), or None
+    when no trial carries the key.  Raises ValueError for a wrong shape, a trial without an observed neuron or a neuron never observed."""
+    rows = [tr.get('observed') if hasattr(tr, 'get') else None for tr in experiment.data]
+    if all(o is None for o in rows):
+        return None
+    q = np.asarray(experiment.data[0]['Y']).shape[0]
+    table = np.ones((len(rows), q), dtype=bool)
+    for r, o in enumerate(rows):
+        if o is None:
+            continue
+        o = np.asarray(o)
+        if o.shape != (q,):
+            raise ValueError("trial %d: 'observed' must have shape (ydim,) = (%d,), got %s" % (r, q, o.shape))
+        table[r] = o != 0
+    return check_observed(table, len(rows), q)
+
+
+def _observed_filled(tr, y):
+    """y with the rows that data[r]['observed'] marks as not recorded set to zero (a copy; NaN is accepted in those rows only)."""
+    o = tr.get('observed') if hasattr(tr, 'get') else None
+    if o is None:
+        return y
+    o = np.asarray(o)
+    if o.shape != (y.shape[0],) or np.all(o != 0):
+        return y                                         # (a wrong shape is reported by _stack_observed)
+    y = np.array(y, copy=True)
+    y[o == 0] = 0
+    return y
+
+
 def _stack_counts(experiment):
     """(counts [R][q][T], lengths [R]) of experiment.data: T is the longest trial, shorter trials are padded with zeros behind their
     own T_r bins.  Raises ValueError for a trial without bins or trials with different numbers of neurons."""
     trials = [np.asarray(tr['Y']) for tr in experiment.data]
     for r, y in enumerate(trials):
+        if y.ndim == 2:
+            trials[r] = y = _observed_filled(experiment.data[r], y)      # the resident copy holds zeros where a neuron was not recorded
         if y.ndim != 2:
             raise ValueError("trial %d: 'Y' must be (ydim, T), got shape %s" % (r, y.shape))
         if y.shape[0] != trials[0].shape[0]:
@@ -507,8 +568,9 @@ def session_for(experiment, p):
     n_trials = len(experiment.data)
     sess = per_exp.get(p)
     if sess is None or sess.R != n_trials:
+        observed = _stack_observed(experiment)            # (before anything is uploaded: a bad table raises ValueError here)
         Y, lengths = _stack_counts(experiment)
-        sess = Session(Y, p, float(experiment.binSize), lengths)
+        sess = Session(Y, p, float(experiment.binSize), lengths, observed)
         per_exp[p] = sess
     return sess, np.arange(n_trials, dtype=np.int32)
 

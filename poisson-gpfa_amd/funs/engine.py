@@ -250,7 +250,8 @@ class PPGPFAfit():
         # per-neuron total counts / number of trials: from the device's integer sums, not from a host raster
         _, _, totals, _ = util.countMoments(self.experiment, self.xdim)
         self._count_totals = totals
-        self.sampleMeanSpikeCounts = totals / self.numTrials
+        # (neurons unobserved on some trials: a neuron's mean is over the trials that recorded it)
+        self.sampleMeanSpikeCounts = totals / util.observedTrialCounts(self.experiment, self.xdim)
         self.sampleMeanSpikeCountsVar = np.var(self.sampleMeanSpikeCounts)
         if hasattr(self.experiment, 'params'):
             Ct = np.asarray(self.experiment.params['C'], dtype=np.float64)

@@ -91,6 +91,8 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     'resident' starts every trial from the mode an earlier E-step left on the device, if any (minibatch EM).
     Trials may differ in length (experiment.data[r]['Y'] of shape (ydim, T_r)): entries of trial r then have T_r bins, lapOptimRes[r]
     xdim*T_r values, and bins past T_r carry no likelihood term on the device.
+    Neurons may be unobserved on some trials (experiment.data[r]['observed'], an optional boolean (ydim,)): trial r's posterior is then that of
+    the model with only its observed rows of C, d and Y; the values of 'Y' in unobserved rows are ignored (NaN is accepted there).
     """
     sess, trial_idx = _prepare(experiment, params)
     sess.ctx.set_option('laplace_f32', int(LAPLACE_F32))       # (True is 1; LAPLACE_F32 is defined next to DUAL_F32 below)
@@ -496,6 +498,7 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     import scipy.optimize as op
     sess, trial_idx = _prepare(experiment, params)
     sess.refuse_unequal('dualVariational')
+    sess.refuse_unobserved('dualVariational')
     n_all = len(trial_idx)
     local_shard = bool(getattr(experiment, '_pgpfa_local_shard', False))
     lo, hi = (0, n_all) if local_shard else sess.local_slice(n_all)

@@ -18,6 +18,7 @@ def PosteriorMCMC(experiment, params, maxSampleIter, trial):
     T = int(experiment.T)
     sess, trial_idx = inference._prepare(experiment, params)
     sess.refuse_unequal('PosteriorMCMC')
+    sess.refuse_unobserved('PosteriorMCMC')
     tr = trial_idx[np.asarray([trial])]
     # chol(K_big) is block diagonal: one T x T Cholesky factor per latent (mcmc.py:29)
     K = sess.ctx.gram()
@@ -80,6 +81,7 @@ def PosteriorMCMC_batch(experiment, params, maxSampleIter, trials, seeds):
         raise ValueError('one seed per chain')
     sess, trial_idx = inference._prepare(experiment, params)
     sess.refuse_unequal('PosteriorMCMC_batch')
+    sess.refuse_unobserved('PosteriorMCMC_batch')
     dev = trial_idx[trials]
     K = sess.ctx.gram()
     chol = [np.linalg.cholesky(K[k]) for k in range(xdim)]

@@ -96,6 +96,7 @@ def leaveOneOutPrediction(params, experiment):
     xdim = np.shape(params['C'])[1]
     sess, trial_idx = _session.session_for(experiment, xdim)
     sess.refuse_unequal('leaveOneOutPrediction')
+    sess.refuse_unobserved('leaveOneOutPrediction')
     lo, hi = (0, len(trial_idx)) if getattr(experiment, '_pgpfa_local_shard', False) else sess.local_slice(len(trial_idx))
     sess.set_params(params)
     y_loc, err_loc = sess.ctx.loo_predict(trial_idx[lo:hi])
@@ -163,7 +164,8 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     trials: positions in experiment.data (None: all; repeats allowed).  conditions: one integer label per listed trial.
     want: any of 'rate' (posterior mean exp(eta + var/2)), 'lower' / 'upper' (the central `level` band exp(eta -+ z sqrt(var))), 'median'
     (exp(eta)) - all four in spikes per SECOND -, 'eta' / 'var' (posterior mean and variance of the log rate per bin) and 'ell' ([n][ydim]:
-    expected Poisson log likelihood sum_t y eta - rate, without sum log y!).  Per-trial entries are [n][ydim][T]; with trials of unequal
+    expected Poisson log likelihood sum_t y eta - rate, without sum log y!; NaN where the neuron was not observed on the trial - the planes cover
+    all neurons there: an unobserved neuron's rate is the model's prediction from the observed ones).  Per-trial entries are [n][ydim][T]; with trials of unequal
     length each is cut to its T_r bins - a list of (ydim, T_r) arrays - unless forecast=True, which keeps all T bins: behind T_r the
     posterior is the GP's prediction from the trial's own bins.  With `conditions` the dict also holds 'condition_mean' [G][ydim][T] in
     spikes per second (the mean over the condition's trials that have the bin; NaN where none has), 'condition_count' [G][T] and
@@ -213,6 +215,9 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
                 out[k] = _cut_planes(sess, idx, made[k](), forecast)
     if 'ell' in want:
         out['ell'] = dev['ell']
+        observed = getattr(sess, 'observed', None)
+        if observed is not None:                       # no counts, no likelihood: an unobserved (trial, neuron) pair has no ell
+            out['ell'] = np.where(observed[idx], out['ell'], np.nan)
     if labels is not None:
         cnt = dev['group_count']
         with np.errstate(invalid='ignore', divide='ignore'):
@@ -274,6 +279,97 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
                 arr = [np.ascontiguousarray(arr[i][:, :, :L]) for i, L in enumerate(lens)]
         out[k] = arr
     return out
+
+
+# -- co-smoothing: held-out neurons predicted from the others -------------------------------------------------
+def coSmoothing(params, experiment, heldOut, trials=None):
+    """Predict the neurons `heldOut` on the listed trials from the trials' other neurons and score the prediction: the held-out neurons are
+    marked unobserved on those trials (on top of experiment.data[r]['observed']), ONE Laplace E-step gives the posterior of the latents
+    without them, and their rate is the posterior mean rate exp(eta + var / 2) that posteriorRates documents.  No ydim mode searches per
+    trial, as leaveOneOutPrediction runs them.
+
+    Runs on a context of its own that holds the listed trials (and one silent, fully observed trial that no E-step touches: a neuron
+    masked on every listed trial is otherwise observed nowhere, which the observation table refuses), so the experiment, its session, the
+    session's table and its resident posterior stay as they were.
+
+    trials: positions in experiment.data (None: all).  Returns a dict: 'rate' - a list with one (len(heldOut), T_r) array per listed trial, in
+    spikes per second; 'bitsPerSpike' - sum over the scored (trial, neuron, bin) of [y log lam - lam] - [y log lbar_n - lbar_n], divided by
+    log 2 times the spikes scored, lam the predicted count per bin, lbar_n the mean count per bin of neuron n over its scored bins;
+    'bitsPerSpikePerNeuron' [len(heldOut)] (NaN for a neuron without a scored spike).  A (trial, neuron) pair is scored when the experiment
+    itself observed the neuron on that trial: the score is computed on the host from the rate plane and the caller's true counts."""
+    from . import _session
+    C = np.asarray(params['C'], dtype=np.float64)
+    ydim, xdim = C.shape
+    held = np.unique(np.asarray(heldOut, dtype=np.int64).reshape(-1))
+    if held.size == 0 or held[0] < 0 or held[-1] >= ydim:
+        raise ValueError('heldOut: neuron indices in 0..%d expected' % (ydim - 1))
+    if WORLD_sharded():
+        raise NotImplementedError('coSmoothing does not support sharded sessions yet')
+    n_all = len(experiment.data)
+    pos = np.arange(n_all) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    if pos.size == 0:
+        raise ValueError('empty trial list')
+    table = _session._stack_observed(experiment)
+    Y, lengths = _session._stack_counts(experiment)
+    if Y.shape[1] != ydim:
+        raise ValueError("params['C'] has %d rows but the experiment has %d neurons" % (ydim, Y.shape[1]))
+    own = np.ones((n_all, ydim), dtype=bool) if table is None else table
+    n = pos.size
+    masked = np.ones((n + 1, ydim), dtype=bool)
+    masked[:n] = own[pos]
+    masked[:n, held] = False
+    empty = np.flatnonzero(~masked[:n].any(axis=1))
+    if empty.size:
+        raise ValueError('trial %d has no observed neuron left once the held-out ones are masked' % int(pos[empty[0]]))
+    Yt = np.zeros((n + 1,) + Y.shape[1:], dtype=Y.dtype)
+    Yt[:n] = Y[pos]
+    Yt[:n, held] = 0
+    len_t = np.concatenate([np.asarray(lengths, dtype=np.int32)[pos], [Y.shape[2]]]).astype(np.int32)
+    sess = _session.Session(Yt, xdim, float(experiment.binSize), len_t, masked)
+    try:
+        sess.set_params({'C': C, 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+        idx = np.arange(n, dtype=np.int32)
+        _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
+        if np.any(status > 1):
+            raise _hip.HipBackendError('coSmoothing: the Laplace mode search failed for %d trial(s)' % int(np.sum(status > 1)))
+        dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
+        lam = np.exp(dev['eta'][:, held] + 0.5 * dev['var'][:, held])          # predicted counts per bin [n][held][T]
+    finally:
+        sess.ctx.close()
+    per_s = 1000.0 / float(experiment.binSize)
+    rates = [lam[i, :, :int(len_t[i])] * per_s for i in range(n)]
+    # the score, on the host: the caller's true counts at the pairs the experiment observed
+    ll = np.zeros(held.size)
+    spikes = np.zeros(held.size)
+    tot_y = np.zeros(held.size)
+    tot_bins = np.zeros(held.size)
+    truth = []
+    for i, r in enumerate(pos):
+        y = np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64)[held]
+        scored = own[int(r)][held]
+        truth.append((y, scored))
+        tot_y += np.where(scored, np.where(scored[:, None], y, 0.0).sum(axis=1), 0.0)
+        tot_bins += scored * y.shape[1]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        lbar = np.where(tot_bins > 0, tot_y / tot_bins, 0.0)
+    for i, (y, scored) in enumerate(truth):
+        L = y.shape[1]
+        y = np.where(scored[:, None], y, 0.0)
+        lm = lam[i, :, :L]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            null = np.where(y > 0, y * np.log(lbar)[:, None], 0.0) - lbar[:, None]
+        model = y * np.log(lm) - lm
+        ll += np.where(scored, (model - null).sum(axis=1), 0.0)
+        spikes += y.sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        per_neuron = np.where(spikes > 0, ll / (np.log(2.0) * spikes), np.nan)
+        total = float(ll.sum() / (np.log(2.0) * spikes.sum())) if spikes.sum() > 0 else float('nan')
+    return {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+
+
+def WORLD_sharded():
+    from . import _session
+    return bool(_session.WORLD.enabled)
 
 
 # -- latent-dimensionality cross-validation (reference util.py:180-275) -------------------------------------
@@ -468,9 +564,39 @@ def countMoments(experiment, xdim):
     if sess.comm_ready:
         red = sess.allreduce(np.concatenate([s, S.reshape(-1), [ns]]))
         s, S, ns = red[:s.size], red[s.size:-1].reshape(S.shape), float(red[-1])
+    observed = getattr(sess, 'observed', None)
+    if observed is not None:
+        mean, cov = _observed_moments(s, S, observed, sess.lengths, sess.T, trial_idx)
+        return mean, cov, s, int(ns)
     mean = s / ns
     cov = (S - np.outer(s, s) / ns) / (ns - 1.0)
     return mean, cov, s, int(ns)
+
+
+def observedTrialCounts(experiment, xdim):
+    """Per neuron, the number of the experiment's trials that observed it (experiment.data[r]['observed']); the trial count where no table is set."""
+    from . import _session
+    sess, trial_idx = _session.session_for(experiment, xdim)
+    observed = getattr(sess, 'observed', None)
+    if observed is None:
+        return float(len(trial_idx))
+    return observed[np.asarray(trial_idx, dtype=np.int64)].sum(axis=0).astype(np.float64)
+
+
+def _observed_moments(s, S, observed, lengths, T, trial_idx):
+    """Count moments under an observation table (host arithmetic on the device's integer sums s[q], S[q][q] over the listed trials, whose rows of
+    unobserved neurons are zero): n_i = sum_r O[r][i] T_r samples of neuron i, n_ij = sum_r O[r][i] O[r][j] T_r co-observed samples of a pair;
+    mean_i = s_i / n_i, cov_ij = (S_ij - s_i s_j n_ij / (n_i n_j)) / (n_ij - 1), and cov_ij = 0 where n_ij < 2 (the initialiser then treats the
+    pair as uncorrelated).  A neuron without a sample among the listed trials has mean 0."""
+    idx = np.asarray(trial_idx, dtype=np.int64)
+    O = np.asarray(observed)[idx].astype(np.float64)
+    Tr = np.full(len(idx), float(T)) if lengths is None else np.asarray(lengths, dtype=np.float64)[idx]
+    n_i = O.T @ Tr
+    n_ij = (O * Tr[:, None]).T @ O
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = np.where(n_i > 0, s / n_i, 0.0)
+        cov = (S - np.outer(s, s) * n_ij / np.outer(n_i, n_i)) / (n_ij - 1.0)
+    return mean, np.where(n_ij >= 2, cov, 0.0)
 
 
 def getMeanCovYfromParams(params, experiment=None):

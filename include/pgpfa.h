@@ -172,7 +172,10 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * "last_newton_solves", "last_pcg_iterations", "last_shared_factorizations", "last_cov_lowrank",
  * "last_dense_retries", "hbm_bytes_allocated", "hbm_bytes_free" / "hbm_bytes_total" (hipMemGetInfo of the context's device, now), "n_trials_global", "prof_<tag>_{ms,flops,launches}" (tags gemm, potrf, solve, poisson, assemble, vsm, cd, mix; "prof_mix_flops" counts BYTES for the stand-alone mixing
  * passes and FLOPs - products + mixing - when "last_yt_mix_fused" is 1), "counts_two_bytes",
- * "arena_bytes", "last_split_cov", "last_yt_mix_fused" (1 when the last covariance pass ran product and mixing as one kernel), "last_cov_f32" (1 when the last covariance pass ran the
+ * "arena_bytes", "last_split_cov"; the path the split form of the last covariance pass took (set by every pass of the low-rank engine, as "last_split_cov";
+ * all 0 when the split form did not run): "last_syrk_tile" (128 or 256: the kernel of the FP16 term), "last_split_sps" (slots per group of its partial
+ * sums), "last_cross_kernel" (1: cross_term_kernel, 0: the segmented-K GEMM), "last_mix_form" (the mixing pass: 0 mix_vsm_split_kernel, 1 / 2 / 3
+ * mix_slot_kernel / mix_slot2_kernel / mix_slot3_kernel, 4 the fused yt_mix_kernel, 5 mix_vsm_wide2_kernel); "last_yt_mix_fused" (1 when the last covariance pass ran product and mixing as one kernel), "last_cov_f32" (1 when the last covariance pass ran the
  * single-precision r x r phase of "laplace_f32", else 0: set by every pass, as "last_split_cov"), "last_cov_f32_fallbacks" (chunks of the last
  * pgpfa_estep_laplace call redone in FP64 after a non-positive pivot of the single-precision factorisation; reset at the start of that call),
  * "last_log_evidence_sum" (sum of the Laplace log evidence, pgpfa_get_log_evidence, over the trials of the last pgpfa_estep_laplace call; 0 when
@@ -449,6 +452,23 @@ int pgpfa_test_gemm_nt_f32(pgpfa_ctx* ctx, int M, int N, int K, double alpha, co
                            const double* B, double beta, double* C);
 int pgpfa_test_gemm_nn_f32(pgpfa_ctx* ctx, int M, int N, int K, double alpha, const double* A,
                            const double* B, double beta, double* C);
+/* The two kernel stages of the split covariance sum (csrc/split.h) on caller data, through the launch code of the E-step; the hooks allocate device
+ * buffers of their own.  Every output buffer is uploaded before the launch, so entries no kernel stores come back as the caller left them, and the hooks
+ * fail when a kernel wrote behind an output.
+ * pgpfa_test_split_syrk: the single-precision term on the FP16 matrix cores.  D is float [nslots][round_up(ract, 32) * ldd], laid out as the E-step lays it
+ * out: D_k[t, b] of a slot at (k * ts + t) + b * ldd, ts >= T, ldd >= p * ts (neither has to be a multiple of 4: the kernel then takes its slow loads);
+ * columns b >= ract, rows t in [T, ts) and the floats between p * ts and ldd must not reach the result.  sps = 0: groups of max(1, ceil(nslots / 64)) slots,
+ * the E-step's rule; sps > 0: groups of sps slots.  tile is option "syrk_tile" (128 or 256); *tile_used is the kernel that ran (256 only where T > 256,
+ * round_up(T, 256) <= ts and ts, ldd are multiples of 4).  part comes back as [p][*ngroups][T][T], column-major, of which the entries (i, j) with i >= j hold
+ * sum over the group's slots and b < ract of D_k[i, b] D_k[j, b] (entries above the diagonal are written in whole 64 x 64 blocks that meet it, or not at all). */
+int pgpfa_test_split_syrk(pgpfa_ctx* ctx, int nslots, int T, int p, int ract, int ldd, int ts, int sps, int tile, const float* D, double* part, int* tile_used,
+                          int* ngroups);
+/* pgpfa_test_split_latent_sums: one latent's S = sum_s A_s A_s^T (rk x rk, full after the mirror) and X = sum_s A_s D_s^T (rk x T), both column-major with
+ * leading dimension rk.  A_s[i][b] = A[s * sM + row_off + i + b * lda] (FP64; rk, kw multiples of 16, lda >= row_off + rk, sM >= kw * lda),
+ * D_s[b][t] = D[s * sD + b * ldd + t] (float; ldd >= T, sD >= kw * ldd).  cross_kernel 1: X through cross_term_kernel in launches of 128 rows, 0: through
+ * the segmented-K GEMM (option "cross_kernel").  Groups as in the E-step: X in groups of sps slots (0: its rule, as above), S in at most 256 groups. */
+int pgpfa_test_split_latent_sums(pgpfa_ctx* ctx, int nslots, int rk, int kw, int T, int lda, long long sM, int row_off, int ldd, long long sD, int sps,
+                                 int cross_kernel, const double* A, const float* D, double* Ssum, double* Xsum);
 /* Times `reps` launches of the dominant kernel (batched trailing SYRK update, K=512) with HIP
  * events on the context stream; returns average ms per launch and the flops of one launch. */
 int pgpfa_bench_syrk(pgpfa_ctx* ctx, int batch, int n, int k, int reps, double* ms_per_launch,

@@ -987,6 +987,10 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   c->info["last_eps_wt_norm"] = 0.0;
   c->info["last_eps_wt_rms"] = 0.0;
   c->info["last_split_cov"] = 0.0;
+  c->info["last_syrk_tile"] = 0.0;
+  c->info["last_split_sps"] = 0.0;
+  c->info["last_cross_kernel"] = 0.0;
+  c->info["last_mix_form"] = 0.0;
   c->info["last_yt_mix_fused"] = 0.0;
   c->info["last_cov_f32"] = 0.0;
   c->info["last_cov_f32_fallbacks"] = 0.0;

@@ -136,6 +136,100 @@ static int posterior_blocks_dense(pgpfa_ctx* c, int nb, double diag_scale, bool 
 }
 
 
+constexpr int SPLIT_NS = 256;     // groups of the S sums of the split form (a partition of their own: S_k costs r_k^2 per group, not r_k T)
+
+// Step 2 of the split form (accumulate_split; also behind pgpfa_test_split_syrk): the full-width term on the FP16 matrix cores,
+//   part[(k * ngroups + g)][T x T] = sum over the slots of group g and the columns b < ract of D_k[:, b] D_k[:, b]^T   (lower 64 x 64 wave tiles),
+// D_k[t, b] = D[slot * sD + (k * Ts + t) + b * ldd].  sps_req = 0: groups of max(1, ceil(nb / PACC_SPLITS)) slots.  tile_req is option syrk_tile; the
+// 256 x 256 kernel runs where T spans more than one such tile and the 16-byte loads of the fast path are allowed.
+static int split_syrk_launch(pgpfa_ctx* c, const float* D, long long sD, int ldd, int Ts, int T, int p, int ract, int nb, int sps_req, int tile_req, double* part,
+                             int* tile_used, int* sps_out, int* ngroups_out) {
+  const int sps = sps_req > 0 ? sps_req : std::max(1, (nb + PACC_SPLITS - 1) / PACC_SPLITS);
+  const int ngroups = (nb + sps - 1) / sps;
+  SyrkF16Args a{};
+  a.D = D; a.sD = sD; a.ldd = ldd; a.ts = Ts; a.part = part;
+  a.T = T; a.p = p; a.ract = ract; a.nslots = nb; a.sps = sps; a.ngroups = ngroups;
+  a.dbg = c->syrk_dbg;
+  // 256 x 256 tiles (half the reads of D per output) where T spans more than one of them and the 16-byte loads of the fast path are allowed
+  const int t256 = (T + 255) / 256;
+  const bool big = tile_req >= 256 && T > 256 && (Ts & 3) == 0 && (ldd & 3) == 0 && t256 * 256 <= Ts && (((size_t)D) & 15) == 0 && (sD & 3) == 0;
+  a.tiles = big ? t256 : (T + 127) / 128; a.ntiles = a.tiles * (a.tiles + 1) / 2;
+  const long long blocks = (long long)a.ntiles * ngroups * p;
+  prof_begin(c, TAG_VSM, 3.0 * (double)nb * ract * T * T * p);
+  if (big) {
+    const size_t lds = (size_t)4 * 2 * 256 * 32 * sizeof(_Float16);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk256_f16x2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(syrk256_f16x2_kernel, dim3((unsigned)blocks), dim3(512), lds, c->st, a);
+  } else {
+    hipLaunchKernelGGL(syrk_f16x2_kernel, dim3((unsigned)blocks), dim3(256), 0, c->st, a);
+  }
+  prof_end(c);
+  *tile_used = big ? 256 : 128;
+  *sps_out = sps;
+  *ngroups_out = ngroups;
+  return 0;
+}
+
+// Step 3 of the split form for one latent (accumulate_split; also behind pgpfa_test_split_latent_sums):
+//   Ssum (rk x rk, full) = sum over the slots of A_s A_s^T,   Xsum (rk x T, ld = rk) = sum over the slots of A_s D_s^T,
+// A_s[i][b] = A0[s * sM + i + b * lda] (FP64, kw columns), D_s[b][t] = Dk[s * sD + b * ldd + t] (single precision).  Both as segmented-K products over
+// groups of slots - S in SPLIT_NS groups, X in groups of sps slots, through cross_term_kernel in launches of 128 rows when `cross` is set and the shapes allow -
+// reduced by sum_groups_kernel.  Spart holds ceil(nb / spsS) * rk^2 doubles, Xpart ceil(nb / sps) * rk * T.
+static int split_latent_sums(pgpfa_ctx* c, const double* A0, long long sM, int lda, const float* Dk, long long sD, int ldd, int rk, int kw, int T, int nb, int sps,
+                             bool cross, double* Spart, double* Xpart, double* Ssum, double* Xsum, int* cross_used) {
+  const int ngroups = (nb + sps - 1) / sps;
+  const int spsS = std::max(1, (nb + SPLIT_NS - 1) / SPLIT_NS);
+  auto seg = [&](int sper, bool is_x, double* out) -> int {                   // groups of `sper` slots (the last one may be short)
+    const int nfull = nb / sper, rem = nb - nfull * sper;
+    for (int part = 0; part < 2; ++part) {
+      const int first = part ? nfull * sper : 0, per = part ? rem : sper, ng = part ? (rem ? 1 : 0) : nfull;
+      if (ng == 0 || per == 0) continue;
+      GemmP g{};
+      g.A = A0 + (size_t)first * sM; g.sA = (long long)per * sM; g.lda = lda;
+      g.kseg = kw; g.sAseg = sM;
+      g.K = per * kw; g.alpha = 1.0; g.beta = 0.0; g.slots = nullptr; g.nbatch = ng; g.kflags = 0; g.bm = 64;
+      g.M = rk;
+      if (is_x) {
+        g.B = reinterpret_cast<const double*>(Dk + (size_t)first * sD);
+        g.sB = (long long)per * sD; g.ldb = ldd; g.sBseg = sD; g.b_f32 = 1;
+        g.N = T; g.mode = GEMM_FULL;
+        g.C = out + (size_t)(part ? nfull : 0) * rk * T; g.sC = (long long)rk * T; g.ldc = rk;
+      } else {
+        g.B = g.A; g.sB = g.sA; g.ldb = lda; g.sBseg = sM;
+        g.N = rk; g.mode = GEMM_LOWER;
+        g.C = out + (size_t)(part ? nfull : 0) * rk * rk; g.sC = (long long)rk * rk; g.ldc = rk;
+      }
+      CHK(gemm(c, false, g));
+    }
+    return 0;
+  };
+  CHK(seg(spsS, false, Spart));
+  // (the S sums stay with the general kernel: through cross_term_kernel<.., double, true> - lower 16 x 16 tiles only - they ran no faster)
+  const bool use_cross = cross && c->mfma && rk % 16 == 0 && kw % 16 == 0;
+  if (use_cross) {
+    // the cross term with (up to 128) rows of the latent in one workgroup (split.h): no padded row tiles on the matrix cores
+    for (int row0 = 0; row0 < rk; row0 += 128) {
+      CrossArgs ca{};
+      ca.A = A0; ca.sM = sM; ca.lda = lda;
+      ca.D = Dk; ca.sD = sD; ca.ldd = ldd;
+      ca.C = Xpart; ca.sC = (long long)rk * T;
+      ca.rk = std::min(128, rk - row0); ca.T = T; ca.kw = kw; ca.nslots = nb; ca.sps = sps;
+      ca.row0 = row0; ca.ldc = rk;
+      prof_begin(c, TAG_GEMM, 2.0 * (double)nb * ca.rk * (double)kw * T);
+      cross_term_launch<float, false>(ca, dim3((T + 63) / 64, ngroups), c->st);
+      prof_end(c);
+    }
+    HIPC(hipGetLastError());
+  } else {
+    CHK(seg(sps, true, Xpart));
+  }
+  const int ngS = (nb + spsS - 1) / spsS;
+  hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)(((size_t)rk * rk + 63) / 64)), dim3(256), 0, c->st, Spart, ngS, rk, rk, 32, Ssum);
+  hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)(((size_t)rk * T + 63) / 64)), dim3(256), 0, c->st, Xpart, ngroups, rk, T, 0, Xsum);
+  *cross_used = use_cross ? 1 : 0;
+  return 0;
+}
+
 // Sum-only covariance output by the exact split form (split.h): Pacc[k] += sum over the chunk's slots of Y~_k Y~_k^T + eps diag(G_t[k][k])
 // from L^-T (lw.Mt), Yt (lw.H) and the per-bin blocks G (c->Gbin), without the full-width FP64 product.  Also writes post_vsm.
 static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, int Ts, bool skip_zero_cols, int ctile, bool fused) {
@@ -145,7 +239,7 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
   (void)skip_zero_cols;
   // scratch: S parts [NS][r_k^2] | X parts [NG][r_k T] | Ssum | Xsum | Z | T1 [p][T^2] | Xfull [p][T^2]; a latent's padded rank r_k can reach
   // T rounded up to 16, so the first five are laid out in units of tq = round_up(T, 16)^2
-  constexpr int NS = 256, NG = PACC_SPLITS + 1;
+  constexpr int NS = SPLIT_NS, NG = PACC_SPLITS + 1;
   const size_t tq = (size_t)round_up(T, 16) * round_up(T, 16);
   if (!c->split_buf) {
     const size_t len = ((size_t)NS + NG + 3) * tq + 2 * (size_t)p * tt + 1024;
@@ -163,6 +257,7 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
   const long long sD = 2 * (long long)lw.sH;                                   // slab stride in floats
   const int ldd = c->ld;
   // 1. mixing pass: post_vsm and the correction D = eps Wt Yt (single precision); Yt itself stays
+  int mix_form = 0;                                        // info key "last_mix_form": which of the kernels below ran
   double mix_cols = 0.0;                                   // columns of Yt a latent's rows really hold: left of its first column tile nothing was written
   for (int k = 0; k < p; ++k) mix_cols += std::max(0, ract - (ctile > 0 ? (c->roff[k] / ctile) * ctile : 0));
   // (bytes: the columns of Yt that hold something read once in FP64; D - dense, the mixing couples the latents - written once in FP32)
@@ -194,8 +289,10 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
       }
     });
     prof_end(c);
+    mix_form = 4;
   } else {
   prof_begin(c, TAG_MIX, (double)nb * T * (mix_cols * 8.0 + (double)p * ract * 4.0));
+  mix_form = p > 16 ? 5 : 0;
   if (p > 16)                                               // (17..20 latents: split_candidate admits no others beyond 16)
     hipLaunchKernelGGL((mix_vsm_wide2_kernel<20, true>), dim3((T + 63) / 64, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, c->ld, c->Gbin, sW, T, p, ract, c->eps,
                        c->vsm, c->ident, c->trial_of_slot, Ts, c->sink, D, sD, ldd);
@@ -207,18 +304,21 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mix_slot3_kernel<PW, 128, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mix_slot_lds(PW, 128));
         hipLaunchKernelGGL((mix_slot3_kernel<PW, 128, 2>), dim3((T + 127) / 128, nb), dim3(256), mix_slot_lds(PW, 128), c->st, (const double*)lw.H, (long long)lw.sH, c->ld, D, sD, ldd,
                            c->Gbin, sW, T, ract, c->eps, c->vsm, c->ident, c->trial_of_slot, c->d_roff, ctile, Ts);
+        mix_form = 3;
         return;
       }
       if (c->mix_slot >= 2 && p == PW && ract % 4 == 0) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mix_slot2_kernel<PW, 256, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mix_slot_lds(PW, 256));
         hipLaunchKernelGGL((mix_slot2_kernel<PW, 256, 2>), dim3((T + 255) / 256, nb), dim3(256), mix_slot_lds(PW, 256), c->st, (const double*)lw.H, (long long)lw.sH, c->ld, D, sD, ldd,
                            c->Gbin, sW, T, ract, c->eps, c->vsm, c->ident, c->trial_of_slot, c->d_roff, ctile, Ts);
+        mix_form = 2;
         return;
       }
       if (c->mix_slot) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mix_slot_kernel<PW, 256, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mix_slot_lds(PW, 256));
         hipLaunchKernelGGL((mix_slot_kernel<PW, 256, 2>), dim3((T + 255) / 256, nb), dim3(256), mix_slot_lds(PW, 256), c->st, (const double*)lw.H, (long long)lw.sH, c->ld, D, sD, ldd,
                            c->Gbin, sW, T, p, ract, c->eps, c->vsm, c->ident, c->trial_of_slot, c->d_roff, ctile, Ts);
+        mix_form = 1;
         return;
       }
     }
@@ -228,32 +328,15 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
   });
   prof_end(c);
   }
+  c->info["last_mix_form"] = (double)mix_form;
   // 2. the full-width term on the FP16 matrix cores: partial sums per (latent, group of slots) into c->ppart
-  const int sps = std::max(1, (nb + PACC_SPLITS - 1) / PACC_SPLITS);
-  const int ngroups = (nb + sps - 1) / sps;
-  {
-    SyrkF16Args a{};
-    a.D = D; a.sD = sD; a.ldd = ldd; a.ts = Ts; a.part = c->ppart;
-    a.T = T; a.p = p; a.ract = ract; a.nslots = nb; a.sps = sps; a.ngroups = ngroups;
-    a.dbg = c->syrk_dbg;
-    // 256 x 256 tiles (half the reads of D per output) where T spans more than one of them and the 16-byte loads of the fast path are allowed
-    const int t256 = (T + 255) / 256;
-    const bool big = c->syrk_tile >= 256 && T > 256 && (Ts & 3) == 0 && (ldd & 3) == 0 && t256 * 256 <= Ts && (((size_t)D) & 15) == 0 && (sD & 3) == 0;
-    a.tiles = big ? t256 : (T + 127) / 128; a.ntiles = a.tiles * (a.tiles + 1) / 2;
-    const long long blocks = (long long)a.ntiles * ngroups * p;
-    prof_begin(c, TAG_VSM, 3.0 * (double)nb * ract * T * T * p);
-    if (big) {
-      const size_t lds = (size_t)4 * 2 * 256 * 32 * sizeof(_Float16);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk256_f16x2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(syrk256_f16x2_kernel, dim3((unsigned)blocks), dim3(512), lds, c->st, a);
-    } else {
-      hipLaunchKernelGGL(syrk_f16x2_kernel, dim3((unsigned)blocks), dim3(256), 0, c->st, a);
-    }
-    prof_end(c);
-  }
+  int sps = 0, ngroups = 0, tile_used = 0;
+  CHK(split_syrk_launch(c, D, sD, ldd, Ts, T, p, ract, nb, 0, c->syrk_tile, c->ppart, &tile_used, &sps, &ngroups));
+  c->info["last_syrk_tile"] = (double)tile_used;
+  c->info["last_split_sps"] = (double)sps;
   // 3. per latent: S_k = sum_r A A^T (r_k x r_k), X_k = sum_r A D_k^T (r_k x T) with A = rows of latent k of L^-T right of column
-  //    roff_k (it is upper triangular), both as segmented-K products over groups of slots; then T1 = F S F^T and Xfull = F X
-  const int spsS = std::max(1, (nb + NS - 1) / NS);
+  //    roff_k (it is upper triangular), both as segmented-K products over groups of slots (split_latent_sums); then T1 = F S F^T and Xfull = F X
+  bool cross_ran = false;
   for (int k = 0; k < p; ++k) {
     // (compact rank offsets: the rk rows taken from r0 on end in the next latent's first rows - they meet zero columns of F_k in T1 and Xfull
     //  below - and the columns start at r0 rounded down to 16, so that their count stays a multiple of 16: the entries left of r0 are below the
@@ -267,52 +350,10 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
       continue;
     }
     const double* A0 = lw.Mt + rrow + (size_t)r0 * rpad;
-    auto seg = [&](int sper, bool is_x, double* out) -> int {                   // groups of `sper` slots (the last one may be short)
-      const int nfull = nb / sper, rem = nb - nfull * sper;
-      for (int part = 0; part < 2; ++part) {
-        const int first = part ? nfull * sper : 0, per = part ? rem : sper, ng = part ? (rem ? 1 : 0) : nfull;
-        if (ng == 0 || per == 0) continue;
-        GemmP g{};
-        g.A = A0 + (size_t)first * lw.sM; g.sA = (long long)per * lw.sM; g.lda = rpad;
-        g.kseg = kw; g.sAseg = lw.sM;
-        g.K = per * kw; g.alpha = 1.0; g.beta = 0.0; g.slots = nullptr; g.nbatch = ng; g.kflags = 0; g.bm = 64;
-        g.M = rk;
-        if (is_x) {
-          g.B = reinterpret_cast<const double*>(D + (size_t)first * sD + (size_t)k * Ts + (size_t)r0 * ldd);
-          g.sB = (long long)per * sD; g.ldb = ldd; g.sBseg = sD; g.b_f32 = 1;
-          g.N = T; g.mode = GEMM_FULL;
-          g.C = out + (size_t)(part ? nfull : 0) * rk * T; g.sC = (long long)rk * T; g.ldc = rk;
-        } else {
-          g.B = g.A; g.sB = g.sA; g.ldb = rpad; g.sBseg = lw.sM;
-          g.N = rk; g.mode = GEMM_LOWER;
-          g.C = out + (size_t)(part ? nfull : 0) * rk * rk; g.sC = (long long)rk * rk; g.ldc = rk;
-        }
-        CHK(gemm(c, false, g));
-      }
-      return 0;
-    };
-    CHK(seg(spsS, false, Spart));
-    // (the S sums stay with the general kernel: through cross_term_kernel<.., double, true> - lower 16 x 16 tiles only - they ran no faster)
-    if (c->cross_kernel && c->mfma && rk % 16 == 0 && kw % 16 == 0) {
-      // the cross term with (up to 128) rows of the latent in one workgroup (split.h): no padded row tiles on the matrix cores
-      for (int row0 = 0; row0 < rk; row0 += 128) {
-        CrossArgs ca{};
-        ca.A = A0; ca.sM = lw.sM; ca.lda = rpad;
-        ca.D = D + (size_t)k * Ts + (size_t)r0 * ldd; ca.sD = sD; ca.ldd = ldd;
-        ca.C = Xpart; ca.sC = (long long)rk * T;
-        ca.rk = std::min(128, rk - row0); ca.T = T; ca.kw = kw; ca.nslots = nb; ca.sps = sps;
-        ca.row0 = row0; ca.ldc = rk;
-        prof_begin(c, TAG_GEMM, 2.0 * (double)nb * ca.rk * (double)kw * T);
-        cross_term_launch<float, false>(ca, dim3((T + 63) / 64, ngroups), c->st);
-        prof_end(c);
-      }
-      HIPC(hipGetLastError());
-    } else {
-      CHK(seg(sps, true, Xpart));
-    }
-    const int ngS = (nb + spsS - 1) / spsS;
-    hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)(((size_t)rk * rk + 63) / 64)), dim3(256), 0, c->st, Spart, ngS, rk, rk, 32, Ssum);
-    hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)(((size_t)rk * T + 63) / 64)), dim3(256), 0, c->st, Xpart, ngroups, rk, T, 0, Xsum);
+    int cross_used = 0;
+    CHK(split_latent_sums(c, A0, (long long)lw.sM, rpad, D + (size_t)k * Ts + (size_t)r0 * ldd, sD, ldd, rk, kw, T, nb, sps, c->cross_kernel, Spart, Xpart, Ssum, Xsum,
+                          &cross_used));
+    cross_ran = cross_ran || cross_used != 0;
     const double* Fk = c->Flr + (size_t)k * Tp * Tp;
     GemmP z{};                                                                  // Z = F_k S_k   (T x r_k)
     z.A = Fk; z.lda = Tp; z.B = Ssum; z.ldb = rk; z.C = Zb; z.ldc = T;
@@ -325,6 +366,7 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
     xf.B = Xsum; xf.ldb = rk; xf.C = Xfull + (size_t)k * tt; xf.ldc = T; xf.N = T;
     CHK(gemm(c, true, xf));
   }
+  c->info["last_cross_kernel"] = cross_ran ? 1.0 : 0.0;
   // 4. Pacc += eps diag + T1 - Xfull - Xfull^T + sum of the FP16 partial sums
   {
     const int nt64 = (T + PACC_TS - 1) / PACC_TS;
@@ -565,6 +607,7 @@ static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, 
   }
   if (!decided) CHK(decide_split());
   c->info["last_split_cov"] = split ? 1.0 : 0.0;
+  if (!split) for (const char* key : {"last_syrk_tile", "last_split_sps", "last_cross_kernel", "last_mix_form"}) c->info[key] = 0.0;
   if (want_vsmgp && split) {
     CHK(accumulate_split(c, lw, nb, ract, Ts, skip_zero_cols, ctile, fused));
   } else if (want_vsmgp) {
@@ -846,3 +889,105 @@ int pgpfa_set_posterior(pgpfa_ctx* c, int n, const int32_t* idx, const double* p
 }
 
 
+
+// ---- test hooks: steps 2 and 3 of the split covariance sum on caller data, through the launch code above ------------------------------
+namespace {
+constexpr size_t HOOK_BAND = 1024;                      // doubles behind every output buffer of a hook that no kernel may touch
+constexpr double HOOK_BAND_VALUE = -12345.6789;
+
+struct HookBuffers {                                    // device allocations of one hook call, freed when it returns
+  std::vector<void*> ptrs;
+  ~HookBuffers() { for (void* q : ptrs) (void)hipFree(q); }
+  // `count` elements + `slack` zeroed ones behind them (the general GEMM reads whole 64-row tiles: rows past M of the last column of the last slot)
+  template <typename T>
+  int get(T** out, size_t count, size_t slack) {
+    void* q = nullptr;
+    const size_t bytes = (count + slack) * sizeof(T);
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail("out of device memory in a test hook (%zu bytes)", bytes); }
+    ptrs.push_back(q);
+    if (hipMemset(q, 0, bytes) != hipSuccess) return fail("hipMemset failed in a test hook");
+    *out = reinterpret_cast<T*>(q);
+    return 0;
+  }
+};
+
+// output buffer of `count` doubles holding the caller's prefill, with the band behind it
+int hook_output(HookBuffers& hb, double** dev, const double* host, size_t count) {
+  CHK(hb.get(dev, count + HOOK_BAND, 0));
+  HIPC(hipMemcpy(*dev, host, count * sizeof(double), hipMemcpyHostToDevice));
+  const std::vector<double> band(HOOK_BAND, HOOK_BAND_VALUE);
+  HIPC(hipMemcpy(*dev + count, band.data(), HOOK_BAND * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+int hook_collect(const char* what, const double* dev, double* host, size_t count) {
+  std::vector<double> band(HOOK_BAND);
+  HIPC(hipMemcpy(host, dev, count * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(band.data(), dev + count, HOOK_BAND * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < HOOK_BAND; ++i)
+    if (band[i] != HOOK_BAND_VALUE) return fail("%s: a kernel wrote %zu doubles past the end of its output", what, i + 1);
+  return 0;
+}
+}  // namespace
+
+int pgpfa_test_split_syrk(pgpfa_ctx* c, int nslots, int T, int p, int ract, int ldd, int ts, int sps, int tile, const float* D, double* part, int* tile_used,
+                          int* ngroups) {
+  if (!c || !D || !part || !tile_used || !ngroups) return fail("null argument");
+  if (nslots < 1 || T < 1 || p < 1 || ract < 1 || sps < 0) return fail("invalid sizes");
+  if (ts < T) return fail("latent stride ts = %d below T = %d", ts, T);
+  if ((long long)ldd < (long long)p * ts) return fail("column stride ldd = %d below p ts = %lld", ldd, (long long)p * ts);
+  if (tile != 128 && tile != 256) return fail("tile must be 128 or 256");
+  const int ract_alloc = round_up(ract, 32);
+  const size_t slot = (size_t)ract_alloc * ldd;
+  if (slot * sizeof(float) >= ((size_t)1 << 31)) return fail("a slot of D exceeds the 32-bit offsets of the buffer loads");
+  const int sps_eff = sps > 0 ? sps : std::max(1, (nslots + PACC_SPLITS - 1) / PACC_SPLITS);
+  const int ng = (nslots + sps_eff - 1) / sps_eff;
+  const size_t np = (size_t)p * ng * T * T;
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  float* dD = nullptr;
+  double* dpart = nullptr;
+  CHK(hb.get(&dD, slot * nslots, 1024));
+  HIPC(hipMemcpy(dD, D, slot * nslots * sizeof(float), hipMemcpyHostToDevice));
+  CHK(hook_output(hb, &dpart, part, np));
+  int sps_used = 0;
+  CHK(split_syrk_launch(c, dD, (long long)slot, ldd, ts, T, p, ract, nslots, sps, tile, dpart, tile_used, &sps_used, ngroups));
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  return hook_collect("pgpfa_test_split_syrk", dpart, part, np);
+}
+
+int pgpfa_test_split_latent_sums(pgpfa_ctx* c, int nslots, int rk, int kw, int T, int lda, long long sM, int row_off, int ldd, long long sD, int sps, int cross_kernel,
+                                 const double* A, const float* D, double* Ssum, double* Xsum) {
+  if (!c || !A || !D || !Ssum || !Xsum) return fail("null argument");
+  if (nslots < 1 || T < 1 || rk < 1 || kw < 1 || sps < 0 || row_off < 0) return fail("invalid sizes");
+  if (rk % 16 != 0) return fail("rk = %d is no multiple of 16", rk);
+  if (kw % 16 != 0) return fail("kw = %d is no multiple of 16", kw);
+  if (lda < row_off + rk) return fail("lda = %d below row_off + rk = %d", lda, row_off + rk);
+  if (ldd < T) return fail("ldd = %d below T = %d", ldd, T);
+  if (sM < (long long)kw * lda || sD < (long long)kw * ldd) return fail("slot strides below kw columns");
+  if (!c->mfma) return fail("the split form runs on the matrix cores (use_mfma = 1)");
+  const int sps_eff = sps > 0 ? sps : std::max(1, (nslots + PACC_SPLITS - 1) / PACC_SPLITS);
+  const int ng = (nslots + sps_eff - 1) / sps_eff;
+  const int spsS = std::max(1, (nslots + SPLIT_NS - 1) / SPLIT_NS), ngS = (nslots + spsS - 1) / spsS;
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  double *dA = nullptr, *dSp = nullptr, *dXp = nullptr, *dS = nullptr, *dX = nullptr;
+  float* dD = nullptr;
+  CHK(hb.get(&dA, (size_t)sM * nslots, 4096));
+  CHK(hb.get(&dD, (size_t)sD * nslots, 4096));
+  CHK(hb.get(&dSp, (size_t)ngS * rk * rk, 1024));
+  CHK(hb.get(&dXp, (size_t)ng * rk * T, 1024));
+  HIPC(hipMemcpy(dA, A, (size_t)sM * nslots * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dD, D, (size_t)sD * nslots * sizeof(float), hipMemcpyHostToDevice));
+  CHK(hook_output(hb, &dS, Ssum, (size_t)rk * rk));
+  CHK(hook_output(hb, &dX, Xsum, (size_t)rk * T));
+  int cross_used = 0;
+  CHK(split_latent_sums(c, dA + row_off, sM, lda, dD, sD, ldd, rk, kw, T, nslots, sps_eff, cross_kernel != 0, dSp, dXp, dS, dX, &cross_used));
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  if ((cross_kernel != 0) != (cross_used != 0)) return fail("internal: the cross term did not take the requested form");
+  CHK(hook_collect("pgpfa_test_split_latent_sums (S)", dS, Ssum, (size_t)rk * rk));
+  return hook_collect("pgpfa_test_split_latent_sums (X)", dX, Xsum, (size_t)rk * T);
+}

@@ -78,6 +78,10 @@ _SIGNATURES = {
     'pgpfa_test_gemm_nn': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_double, c_double_p, c_double_p, ct.c_double, c_double_p],
     'pgpfa_test_gemm_nt_f32': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_double, c_double_p, c_double_p, ct.c_double, c_double_p],
     'pgpfa_test_gemm_nn_f32': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_double, c_double_p, c_double_p, ct.c_double, c_double_p],
+    'pgpfa_test_split_syrk': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.POINTER(ct.c_float), c_double_p,
+                              ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)],
+    'pgpfa_test_split_latent_sums': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_longlong, ct.c_int, ct.c_int, ct.c_longlong, ct.c_int, ct.c_int,
+                                     c_double_p, ct.POINTER(ct.c_float), c_double_p, c_double_p],
     'pgpfa_bench_syrk': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_double_p, c_double_p],
     'pgpfa_bench_potrf_diag': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, c_double_p],
     'pgpfa_gemm_shape_report': [ct.c_void_p, ct.c_char_p, ct.c_int],
@@ -598,6 +602,36 @@ class Context:
         fn = self.lib.pgpfa_test_gemm_nn_f32 if f32 else self.lib.pgpfa_test_gemm_nn
         check(fn(self.h, M, N, K, float(alpha), dptr(Acm), dptr(Bcm), float(beta), dptr(Ccm)))
         return Ccm.T.copy()
+
+    def test_split_syrk(self, D, T, p, ract, ldd, ts, sps=0, tile=256, fill=0.0, band=0):
+        """The FP16 term of the split covariance sum (pgpfa_test_split_syrk) on D, float32 (nslots, round_up(ract, 32) * ldd).  Returns (part, tile_used,
+        ngroups, tail): part (p, ngroups, T, T) indexed [k, g, j, i] - column-major (i, j) blocks - prefilled with `fill`, so entries no kernel stored
+        keep it; tail: `band` doubles behind the output buffer, prefilled alike."""
+        D = np.ascontiguousarray(D, dtype=np.float32)
+        nslots = D.shape[0]
+        assert D.ndim == 2 and D.shape[1] == (int(ract) + 31) // 32 * 32 * int(ldd)
+        spe = int(sps) if sps > 0 else max(1, (nslots + 63) // 64)
+        ng = (nslots + spe - 1) // spe
+        n = p * ng * T * T
+        buf = np.full(n + int(band), float(fill))
+        tile_used, ngroups = ct.c_int(0), ct.c_int(0)
+        check(self.lib.pgpfa_test_split_syrk(self.h, nslots, int(T), int(p), int(ract), int(ldd), int(ts), int(sps), int(tile),
+                                             D.ctypes.data_as(ct.POINTER(ct.c_float)), dptr(buf), ct.byref(tile_used), ct.byref(ngroups)))
+        assert ngroups.value == ng
+        return buf[:n].reshape(p, ng, T, T), tile_used.value, ngroups.value, buf[n:]
+
+    def test_split_latent_sums(self, A, D, rk, kw, T, lda, row_off, ldd, sps=0, cross_kernel=1, fill=0.0, band=0):
+        """One latent's sums of the split form (pgpfa_test_split_latent_sums): A float64 (nslots, sM), D float32 (nslots, sD).  Returns (S, X, tails):
+        S[j, i] = sum_s (A_s A_s^T)[i, j] (rk, rk), X[t, i] = sum_s (A_s D_s^T)[i, t] (T, rk) - the column-major results - and the `band` doubles behind each."""
+        A = as_f64(A)
+        D = np.ascontiguousarray(D, dtype=np.float32)
+        nslots = A.shape[0]
+        assert A.ndim == 2 and D.ndim == 2 and D.shape[0] == nslots
+        S = np.full(rk * rk + int(band), float(fill))
+        X = np.full(rk * T + int(band), float(fill))
+        check(self.lib.pgpfa_test_split_latent_sums(self.h, nslots, int(rk), int(kw), int(T), int(lda), A.shape[1], int(row_off), int(ldd), D.shape[1], int(sps),
+                                                    int(cross_kernel), dptr(A), D.ctypes.data_as(ct.POINTER(ct.c_float)), dptr(S), dptr(X)))
+        return S[:rk * rk].reshape(rk, rk), X[:rk * T].reshape(T, rk), (S[rk * rk:], X[rk * T:])
 
     def bench_mfma_peak(self, iters=20000):
         tf = ct.c_double(0.0)

@@ -76,6 +76,17 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * Laplace approximation of every processed trial's log evidence, see pgpfa_get_log_evidence - one reduction kernel per chunk behind the covariance
  * phase's factorisation, read back with the pivots, no further host wait; any other value fails.  With "laplace_f32" != 0 pgpfa_estep_laplace fails:
  * the log-determinant is taken from the FP64 factor only),
+ * "dual_masked" (0 - the default: every pgpfa_dual_* entry point refuses while per-trial bin counts or an observation table are set, and launches,
+ * allocations and bits are those of a library without the option; 1: pgpfa_dual_fixed_point, pgpfa_dual_lbfgs, pgpfa_dual_costgrad_batch,
+ * pgpfa_dual_costgrad, pgpfa_dual_finalize, pgpfa_get_dual_lambda, post_cov of a variational trial and the blocks rebuilt on demand for rates and
+ * samples accept both tables; with no table set the code path is the default one, bit for bit; any other value fails.  An entry (n, t) of trial r is
+ * live when t < T_r and the neuron is observed on the trial.  Dual variables keep their padded [q*T] layout: lambda is exactly 0, rho = log lambda
+ * comes back as 0 and gradients are exactly 0 at entries that are not live, and whatever the caller passes there is ignored.  Every result is that
+ * of the reference's functions (inference.py:188-256) on the trial's reduced problem - rows of unobserved neurons deleted, bins cut to T_r - including
+ * the 1e-6 jitter, which for a trial of T_r < T bins is taken from the T_r-bin Gram inverse and put on the bins t < T_r only, and the log-determinant
+ * of the dual cost, corrected by sum_k (log det K_{k,T} - log det K_{k,T_r}); the tables behind both come from one kernel per
+ * set of timescales, launched on the first such call while a length table is set.  pgpfa_dual_post_mean, pgpfa_dual_post_cov, pgpfa_loo_predict and
+ * pgpfa_generate keep refusing),
  * "pcg_fused" (1: inner PCG iterations without host round trips, pcg.h), "pcg_w32" (1: packed FP32 curvature blocks in the PCG
  * Hessian-vector product), "cd_mfma" (1: (C,d) sweep on the matrix cores, mstep.h), "cd_hess_mfma" (1: the Newton pass
  * of the (C,d) M-step - cost, gradient, per-neuron Hessians - on the matrix cores up to 10 latents; 0: the vector kernel), "vsm_mfma" (1: beyond 10 latents the per-bin

@@ -692,6 +692,7 @@ int upload_nosync(pgpfa_ctx* c, void* dev, const void* host, size_t bytes) {
 
 // Kinv (and logdet) of the p Gram slabs currently in Kpad, through the production factor kernels
 int build_kinv(pgpfa_ctx* c) {
+  c->kinv_serial += 1;
   const size_t slab = (size_t)c->Tp * c->Tp;
   CHK(copy_dev(c, c->kws.H, c->Kpad, slab * c->p * sizeof(double)));
   HIPC(hipMemsetAsync(c->kws.info, 0, sizeof(int) * c->p, c->st));
@@ -1013,6 +1014,7 @@ int pgpfa_destroy(pgpfa_ctx* c) {
   if (c->Yhi) hipFree(c->Yhi);
   if (c->trial_len) hipFree(c->trial_len);
   if (c->obs) hipFree(c->obs);
+  if (c->trunc_q) hipFree(c->trunc_q);
   arena_release(c);
   if (c->hbuf) hipHostFree(c->hbuf);
   if (c->dl_stage) hipHostFree(c->dl_stage);
@@ -1095,6 +1097,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "dual_lowrank") c->dual_lowrank = (v != 0.0);
   else if (k == "dual_f32") c->dual_f32 = (int)v;
   else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
+  else if (k == "dual_masked") { if (v != 0.0 && v != 1.0) return fail("dual_masked is 0 or 1"); c->dual_masked = (int)v; }
   else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
   else if (k == "sample_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("sample_chunk_trials is a count of trials, or 0"); c->sample_chunk = (int)v; }
   else if (k == "rates_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("rates_chunk_trials is a count of trials, or 0"); c->rates_chunk = (int)v; }

@@ -775,7 +775,7 @@ static int materialize_impl(pgpfa_ctx* c, const std::vector<int>& need, bool dua
       std::vector<double> sB, sD, vKv;
       CHK(dual_common(c, nb, &sB, &sD, &vKv));
       if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, true, false)); }
-      else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, true, false));
+      else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_blocks(c, nb, scale, true, false)); }
     } else {
       hipLaunchKernelGGL(gather_rows_kernel, dim3((c->n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, c->n, c->Xc, (long long)c->ld,
                          c->trial_of_slot, 0);

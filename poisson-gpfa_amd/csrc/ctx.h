@@ -154,6 +154,16 @@ struct pgpfa_ctx {
   // processes.  The log-determinants are reduced on the device (evidence_logdet_kernel, one entry per slot in evid_ld) right behind the covariance
   // phase's factorisation and come back with the read-back laplace_finish already does.  A trial's value belongs to the posterior of the E-step
   // that wrote it: it is valid while evid_serial equals the trial's mode_serial.
+  // Dual-variational E-step on trials of unequal length and / or with unobserved neurons (option dual_masked).  Off: every
+  // pgpfa_dual_* entry point refuses while a table is set and nothing below exists.  On: the dual variables are exactly zero at entries that are not
+  // live (t >= T_r or obs = 0), and while a length table is set the reference's jitter of a trial comes from the T_r-bin Gram inverse:
+  //   trunc_q[k][L - 1][t] = (K_{k,L}^-1)_tt = sum_{j = t}^{L - 1} M_k[j][t]^2,   M_k = chol(K_k)^-1   (leading blocks of a Cholesky factor nest)
+  //   trunc_ld[k][L]       = log det K_{k,L} = 2 sum_{i < L} log chol(K_k)_ii
+  // built on the first masked dual call after build_kinv has run for the current timescales (ensure_trunc_prior, dual.hip).
+  int dual_masked = 0;
+  double* trunc_q = nullptr;                     // device [p][T][T]
+  std::vector<double> trunc_ld;                  // host [p][T + 1]
+  int kinv_serial = 0, trunc_serial = -1;        // build_kinv calls so far / the one trunc_q and trunc_ld belong to
   int laplace_evidence = 0;
   double* evid_ld = nullptr;                     // device [B] (workspace allocation, made on first use)
   std::vector<double> log_evidence;              // [R]
@@ -480,6 +490,12 @@ int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale);      // step
 int ensure_lambda(pgpfa_ctx* c);
 int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<double>* sD, std::vector<double>* vKv);
 int dual_jitter(pgpfa_ctx* c, int nb);
+// option dual_masked (see pgpfa_ctx::dual_masked)
+int refuse_dual_tables(const pgpfa_ctx* c, const char* entry);       // refuse_trial_lengths + refuse_observed unless the option is on
+bool dual_masking(const pgpfa_ctx* c);                                // the option is on and a table is set: dual variables carry the live mask
+int dual_mask(pgpfa_ctx* c, int nb, double* buf);                     // zero the entries that are not live of a [slot][q][T] array (no-op unless dual_masking)
+int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale);            // the dense engine's jitter: the diagonal scale of assemble, or in the W blocks (length table)
+int ensure_trunc_prior(pgpfa_ctx* c);
 int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want_grad, double* cost, bool tolerate = false);
 int var_offsets(pgpfa_ctx* c, int nb, double* out);
 int check_distinct(const std::vector<int>& v);

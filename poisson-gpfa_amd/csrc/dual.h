@@ -31,6 +31,9 @@ inline __global__ void dual_table_kernel(const double* __restrict__ C, int q, in
 
 // lmy = lambda - y for the slots [0, nslots); partial sums per (slot, 64-bin tile): sum d_n lmy and sum lambda (log lambda - 1).
 // grid = (ceil(T/64), nslots), block = 256 (lanes = bins, the 4 waves take interleaved neurons)
+// MASKED (option dual_masked with a table set): lambda is exactly 0 at entries that are not live and so is the count (checked when the table is
+// set), so lmy and the d term vanish there by themselves; only lambda (log lambda - 1) needs the test.  Without it the kernel is the code it was.
+template <bool MASKED = false>
 inline __global__ __launch_bounds__(256) void dual_pre_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ d, const double* __restrict__ lam,
                                                        double* __restrict__ lmy, double* __restrict__ part, const int* __restrict__ trial_of_slot,
                                                        int q, int T) {
@@ -47,7 +50,7 @@ inline __global__ __launch_bounds__(256) void dual_pre_kernel(const uint8_t* __r
       const double v = l - (double)count_at(Y, Yhi, (trial * q + n) * T + t);
       lmy[e] = v;
       sB += d[n] * v;
-      sD += l * (log(l) - 1.0);
+      if (!MASKED || l > 0.0) sD += l * (log(l) - 1.0);         // (one expression for both instantiations: the same contraction, the same bits)
     }
   }
   for (int off = 32; off > 0; off >>= 1) { sB += __shfl_down(sB, off); sD += __shfl_down(sD, off); }
@@ -176,6 +179,64 @@ inline __global__ void dual_jitter_kernel(double* __restrict__ W, long long sW, 
   const int t = e / p, k = e - t * p;
   double* w = W + (size_t)blockIdx.y * sW + (size_t)t * p * p + k * p + k;
   *w = (1.0 + jit) * (*w) + jit * Kinv[(size_t)k * Tp * Tp + (size_t)t * Tp + t];
+}
+
+// The same for trials of unequal length (option dual_masked with a length table): a trial of L = len[trial] < T bins is the reference's trial of L
+// bins, whose precision is K_L^-1 + scatter(W_t), so its jitter takes (K_{k,L}^-1)_tt = Q[k][L - 1][t] (trunc_prior_kernel) at t < L and the padded
+// bins t >= L get none - marginalising them then returns the reference's jittered posterior of the truncated trial exactly.
+// A trial of all T bins reads the Kinv diagonal with the expression above: the same bits.  grid = (ceil(T*p/256), nslots)
+inline __global__ void dual_jitter_len_kernel(double* __restrict__ W, long long sW, const double* __restrict__ Kinv, int Tp, int T, int p, double jit,
+                                              const int* __restrict__ trial_of_slot, const int* __restrict__ len, const double* __restrict__ Q) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= T * p) return;
+  const int t = e / p, k = e - t * p;
+  const int L = len[trial_of_slot[blockIdx.y]];
+  if (t >= L) return;
+  double* w = W + (size_t)blockIdx.y * sW + (size_t)t * p * p + k * p + k;
+  const double kd = (L == T) ? Kinv[(size_t)k * Tp * Tp + (size_t)t * Tp + t] : Q[((size_t)k * T + (L - 1)) * T + t];
+  // (dual_jitter_kernel's expression compiles to the product jit * (K^-1)_tt rounded once and one fused multiply-add with (1 + jit) W; spelled out here,
+  //  because with the select in front the compiler contracts the other product and a trial of all T bins would lose its bits)
+  *w = fma(1.0 + jit, *w, jit * kd);
+}
+
+// Truncated-prior tables of one latent per blockIdx.y from its Cholesky factor Lf (lower, column-major, ld = Tp) and Mt = Lf^-T (upper, column-major:
+// (Lf^-1)[j][t] sits at Mt[j * Tp + t], j >= t).  The leading L x L block of Lf is the factor of the L-bin Gram matrix and the same holds for the inverse, so
+//   Q[k][L - 1][t] = (K_{k,L}^-1)_tt = sum_{j = t}^{L - 1} Mt[j * Tp + t]^2   for t < L (0 beyond),   ldpre[k][L] = 2 sum_{i < L} log Lf[i][i].
+// Lanes run over t: for a fixed j they read one contiguous run of column j of Mt and write one contiguous run of row j of Q; the sum over j is a
+// running sum in a register.  The last thread of the grid's first block per latent also walks the factor's diagonal.  grid = (ceil(T/256), p), block = 256
+inline __global__ __launch_bounds__(256) void trunc_prior_kernel(const double* __restrict__ Lf, long long sL, const double* __restrict__ Mt, long long sM, int Tp, int T,
+                                                                 double* __restrict__ Q, double* __restrict__ ldpre) {
+  const int k = blockIdx.y;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const double* m = Mt + (size_t)k * sM;
+  double* q = Q + (size_t)k * T * T;
+  if (t < T) {
+    double acc = 0.0;
+    for (int j = 0; j < T; ++j) {
+      if (j >= t) { const double v = m[(size_t)j * Tp + t]; acc += v * v; }
+      q[(size_t)j * T + t] = acc;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 255) {
+    const double* l = Lf + (size_t)k * sL;
+    double* o = ldpre + (size_t)k * (T + 1);
+    double acc = 0.0;
+    o[0] = 0.0;
+    for (int i = 0; i < T; ++i) { acc += 2.0 * log(l[(size_t)i * Tp + i]); o[i + 1] = acc; }
+  }
+}
+
+// buf[slot][n][t] <- 0 at the entries of the slot's trial that are not live: t >= len[trial] or obs[trial][n] == 0 (either table may be NULL).
+// Runs behind every upload or exponential of dual variables and behind the dual gradient and the variance offsets under option dual_masked, so that
+// those are exactly zero there.  grid = (ceil(q*T/256), nslots)
+inline __global__ void dual_live_mask_kernel(double* __restrict__ buf, const int* __restrict__ trial_of_slot, const int* __restrict__ len,
+                                             const uint8_t* __restrict__ obs, int q, int T) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)q * T) return;
+  const size_t trial = trial_of_slot[blockIdx.y];
+  const int n = (int)(e / T), t = (int)(e - (size_t)n * T);
+  const bool live = (!len || t < len[trial]) && (!obs || obs[trial * q + n] != 0);
+  if (!live) buf[(size_t)blockIdx.y * q * T + e] = 0.0;
 }
 
 // grad[slot][n][t] += log(lambda) - d_n.  grid = (ceil(q*T/256), nslots)

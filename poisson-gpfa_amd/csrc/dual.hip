@@ -6,6 +6,73 @@
 using namespace pgpfa;
 
 // ---- dual variational E-step (inference.py:188-432) ----------------------------------------------------
+// Option dual_masked: trials of unequal length and unobserved neurons in the dual path (pgpfa_ctx::dual_masked)
+int refuse_dual_tables(const pgpfa_ctx* c, const char* entry) {
+  if (c && c->dual_masked) return 0;
+  CHK(refuse_trial_lengths(c, entry));
+  return refuse_observed(c, entry);
+}
+
+bool dual_masking(const pgpfa_ctx* c) { return c->dual_masked && (c->trial_len || c->obs); }
+
+static bool dual_live(const pgpfa_ctx* c, int trial, size_t e) {       // entry e = n T + t of a trial's dual variables has a likelihood term
+  if (c->trial_len && (int)(e % c->T) >= c->trial_len_h[trial]) return false;
+  return !c->obs || c->obs_h[(size_t)trial * c->q + e / c->T] != 0;
+}
+
+int dual_mask(pgpfa_ctx* c, int nb, double* buf) {
+  if (!dual_masking(c)) return 0;
+  hipLaunchKernelGGL(dual_live_mask_kernel, dim3((unsigned)(((size_t)c->q * c->T + 255) / 256), nb), dim3(256), 0, c->st, buf, c->trial_of_slot, c->trial_len, c->obs,
+                     c->q, c->T);
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+// trunc_q / trunc_ld of the Gram slabs in Kpad.  build_kinv's factor workspace also serves the timescale M-step, which overwrites it, so the factor
+// and its inverse are taken again here (p factorisations of T bins, once per set of timescales and only while a length table is set under the option)
+int ensure_trunc_prior(pgpfa_ctx* c) {
+  if (c->trunc_q && c->trunc_serial == c->kinv_serial) return 0;
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");   // it shares kws with this one
+  const int p = c->p, T = c->T, Tp = c->Tp;
+  const size_t slab = (size_t)Tp * Tp, nq = (size_t)p * T * T;
+  if (!c->trunc_q) {
+    if (hipMalloc((void**)&c->trunc_q, nq * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); c->trunc_q = nullptr; return fail("hipMalloc(%zu bytes) for the truncated-prior table failed", nq * sizeof(double)); }
+    c->bytes += nq * sizeof(double);
+  }
+  double* ldpre = nullptr;
+  if (hipMalloc((void**)&ldpre, (size_t)p * (T + 1) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail("hipMalloc failed"); }
+  struct Free { double* q2; ~Free() { hipFree(q2); } } freer{ldpre};
+  CHK(copy_dev(c, c->kws.H, c->Kpad, slab * p * sizeof(double)));
+  HIPC(hipMemsetAsync(c->kws.info, 0, sizeof(int) * p, c->st));
+  CHK(factor(c, c->kws, nullptr, p));
+  CHK(inverse_t(c, c->kws, nullptr, p));
+  hipLaunchKernelGGL(trunc_prior_kernel, dim3((unsigned)((T + 255) / 256), p), dim3(256), 0, c->st, c->kws.H, (long long)c->kws.sH, c->kws.Mt, (long long)c->kws.sM, Tp, T,
+                     c->trunc_q, ldpre);
+  HIPC(hipGetLastError());
+  c->trunc_ld.assign((size_t)p * (T + 1), 0.0);
+  CHK(download(c, c->trunc_ld.data(), ldpre, c->trunc_ld.size()));
+  c->trunc_serial = c->kinv_serial;
+  return 0;
+}
+
+// log det(P_a + J_a) of the reference's truncated trial minus the log det of the padded jittered precision the engines factor:
+// sum_k (log det K_{k,T} - log det K_{k,T_r})   (0 without a length table, and exactly 0 for a trial of all T bins)
+static double trunc_logdet_correction(const pgpfa_ctx* c, int trial) {
+  if (!c->dual_masked || !c->trial_len) return 0.0;
+  const int T = c->T, L = c->trial_len_h[trial];
+  double s = 0.0;
+  for (int k = 0; k < c->p; ++k) s += c->trunc_ld[(size_t)k * (T + 1) + T] - c->trunc_ld[(size_t)k * (T + 1) + L];
+  return s;
+}
+
+// The dense engine scales the assembled diagonal by 1 + 1e-6 (inference.py:190).  While a length table is set under the option the jitter depends on the
+// trial and goes into the W blocks of the slots [0, nb) instead (dual_jitter), and the assembly runs with scale 1.
+int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale) {
+  *scale = 1.0 + 1e-6;
+  if (c->dual_masked && c->trial_len) { CHK(dual_jitter(c, nb)); *scale = 1.0; }
+  return 0;
+}
+
 int ensure_lambda(pgpfa_ctx* c) {
   if (c->lamd) return 0;
   // (slack: the GEMM form reads Lambda^T as a T x qpad operand and whole 128-row tiles)
@@ -27,7 +94,8 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
   if (c->dual_gemm && c->mfma) {
     const long long sW = (long long)T * p * p;
     const int np = p * (p + 1) / 2;
-    hipLaunchKernelGGL(dual_pre_kernel, dim3(ntile, nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->lamd, c->dgrad, c->dpart, c->trial_of_slot, q, T);
+    if (dual_masking(c)) hipLaunchKernelGGL((dual_pre_kernel<true>), dim3(ntile, nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->lamd, c->dgrad, c->dpart, c->trial_of_slot, q, T);
+    else hipLaunchKernelGGL((dual_pre_kernel<false>), dim3(ntile, nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->lamd, c->dgrad, c->dpart, c->trial_of_slot, q, T);
     GemmP w{};                                               // Wp (T x pairs) = Lambda^T . TBL[:, pairs]
     w.A = c->lamd; w.sA = (long long)q * T; w.lda = T;
     w.B = c->dual_tbl; w.sB = 0; w.ldb = c->dual_ncol;
@@ -41,8 +109,10 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
     hipLaunchKernelGGL(dual_unpack_w_kernel, dim3((unsigned)((T + nbu - 1) / nbu), nb), dim3(256), (size_t)np * (nbu + 1) * sizeof(double), c->st, c->dual_scr, c->dual_sscr,
                        c->W, sW, T, p, nbu);
   } else {
-    hipLaunchKernelGGL(dual_prep_kernel, dim3(ntile, nb), dim3(64), 0, c->st, c->Y, c->Yhi, c->C, c->d, c->lamd, (long long)q * T, c->Xt, ld, c->W,
-                       (long long)T * p * p, c->dpart, ntile, c->ident, c->trial_of_slot, q, p, T);
+    if (dual_masking(c)) hipLaunchKernelGGL((dual_prep_kernel<true>), dim3(ntile, nb), dim3(64), 0, c->st, c->Y, c->Yhi, c->C, c->d, c->lamd, (long long)q * T, c->Xt, ld, c->W,
+                                            (long long)T * p * p, c->dpart, ntile, c->ident, c->trial_of_slot, q, p, T);
+    else hipLaunchKernelGGL((dual_prep_kernel<false>), dim3(ntile, nb), dim3(64), 0, c->st, c->Y, c->Yhi, c->C, c->d, c->lamd, (long long)q * T, c->Xt, ld, c->W,
+                            (long long)T * p * p, c->dpart, ntile, c->ident, c->trial_of_slot, q, p, T);
   }
   CHK(prior_mv(c, c->ident, nb, c->Xt, c->KD, c->Kpad));            // K v
   hipLaunchKernelGGL(dots3_kernel, dim3(nb), dim3(256), 0, c->st, c->Xt, ld, c->KD, ld, (const double*)nullptr, 0LL, (const double*)nullptr, 0LL,
@@ -63,9 +133,9 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
 }
 
 int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost, double* grad) {
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_costgrad"));
-  CHK(refuse_observed(c, "pgpfa_dual_costgrad"));
-  if (c && c->have_counts && c->have_params && c->dual_lowrank && want_lowrank(c)) {
+  CHK(refuse_dual_tables(c, "pgpfa_dual_costgrad"));
+  // (the low-rank engine, and any evaluation under a table, is the batched evaluation with one trial)
+  if (c && c->have_counts && c->have_params && ((c->dual_lowrank && want_lowrank(c)) || dual_masking(c))) {
     // the low-rank engine is the batched evaluation with one trial
     const int32_t t = trial;
     return pgpfa_dual_costgrad_batch(c, 1, &t, lam, cost, grad);
@@ -138,7 +208,9 @@ static int dual_post_cov_dev(pgpfa_ctx* c, double* cov, double* prec) {
   }
   HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int), c->st));
   CHK(ensure_mt_clean(c));
-  CHK(assemble(c, c->ident, 1, 1.0 + 1e-6));
+  double scale = 1.0;
+  CHK(dual_dense_scale(c, 1, &scale));
+  CHK(assemble(c, c->ident, 1, scale));
   CHK(factor(c, c->ws, c->ident, 1));
   CHK(inverse_t(c, c->ws, c->ident, 1));
   GemmP g{};
@@ -186,6 +258,13 @@ int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out) {
 
 // the reference's 1e-6 relative jitter on the diagonal of the posterior precision, applied to the W blocks of the slots [0, nb) in place
 int dual_jitter(pgpfa_ctx* c, int nb) {
+  if (c->dual_masked && c->trial_len) {
+    CHK(ensure_trunc_prior(c));
+    hipLaunchKernelGGL(dual_jitter_len_kernel, dim3((unsigned)((c->T * c->p + 255) / 256), nb), dim3(256), 0, c->st, c->W, (long long)c->T * c->p * c->p,
+                       c->Kinv, c->Tp, c->T, c->p, 1e-6, c->trial_of_slot, c->trial_len, c->trunc_q);
+    HIPC(hipGetLastError());
+    return 0;
+  }
   hipLaunchKernelGGL(dual_jitter_kernel, dim3((unsigned)((c->T * c->p + 255) / 256), nb), dim3(256), 0, c->st, c->W, (long long)c->T * c->p * c->p,
                      c->Kinv, c->Tp, c->T, c->p, 1e-6);
   HIPC(hipGetLastError());
@@ -229,6 +308,7 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
   const int p = c->p, T = c->T;
   std::vector<double> sB, sD, vKv, logdet(nb);
   std::vector<int> info(nb);
+  const bool masked = dual_masking(c);
   CHK(dual_common(c, nb, &sB, &sD, &vKv));
   if (c->plan_lowrank) {
     // low-rank engine: log det through the r x r system, Sigma_t blocks from the per-bin pass over Yt.  The reference's jitter
@@ -240,6 +320,7 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
     CHK(dl_flush(c));
     for (int s2 = 0; s2 < nb; ++s2) {
       cost[s2] = 0.5 * vKv[s2] - sB[s2] - 0.5 * logdet[s2] + sD[s2];
+      if (masked) cost[s2] -= 0.5 * trunc_logdet_correction(c, tos[s2]);
       if (info[s2] != 0 || !std::isfinite(cost[s2])) {
         if (!tolerate) return fail("dual problem: posterior precision of trial %d not positive definite (pivot %d)", tos[s2], info[s2]);
         cost[s2] = std::numeric_limits<double>::infinity();
@@ -247,12 +328,15 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
     }
     if (want_grad) {
       CHK(dual_gradient(c, nb));
+      CHK(dual_mask(c, nb, c->dgrad));
     }
     return 0;
   }
   HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
   CHK(ensure_mt_clean(c));
-  CHK(assemble(c, c->ident, nb, 1.0 + 1e-6));                           // inference.py:190
+  double scale = 1.0;
+  CHK(dual_dense_scale(c, nb, &scale));
+  CHK(assemble(c, c->ident, nb, scale));                                // inference.py:190
   CHK(factor(c, c->ws, c->ident, nb));
   hipLaunchKernelGGL(logdet_batch_kernel, dim3(nb), dim3(256), 0, c->st, c->ws.H, (long long)c->ws.sH, c->ld, c->npad, c->sc_f);
   CHK(download(c, logdet.data(), c->sc_f, nb));
@@ -261,6 +345,7 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
   for (int s2 = 0; s2 < nb; ++s2) {
     // A + B + C + D of inference.py:203-213 ; C = 0.5*logdet(Sigma) = -0.5*logdet(precision + jitter)
     cost[s2] = 0.5 * vKv[s2] - sB[s2] - 0.5 * logdet[s2] + sD[s2];
+    if (masked) cost[s2] -= 0.5 * trunc_logdet_correction(c, tos[s2]);
     if (info[s2] != 0 || !std::isfinite(cost[s2])) {
       if (!tolerate) return fail("dual problem: posterior precision of trial %d not positive definite (pivot %d)", tos[s2], info[s2]);
       cost[s2] = std::numeric_limits<double>::infinity();
@@ -270,6 +355,7 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
     CHK(inverse_t(c, c->ws, c->ident, nb));
     CHK(post_vsm_from_mt(c, nb));
     CHK(dual_gradient(c, nb));
+    CHK(dual_mask(c, nb, c->dgrad));
   }
   return 0;
 }
@@ -295,7 +381,8 @@ int var_offsets(pgpfa_ctx* c, int nb, double* out) {
     hipLaunchKernelGGL(var_quad_kernel, dim3((T + 63) / 64, q, nb), dim3(64), 0, c->st, c->C, c->vsm, c->trial_of_slot, out, q, p, T);
   }
   HIPC(hipGetLastError());
-  return 0;
+  // (option dual_masked: no offset where there is no rate - the fixed point's stop test, the max-norm of the change, then runs over live entries only)
+  return dual_mask(c, nb, out);
 }
 
 // The optimum of the dual problem (inference.py:196-219) of a list of trials by a fixed point instead of a quasi-Newton run in lambda.
@@ -313,8 +400,7 @@ int var_offsets(pgpfa_ctx* c, int nb, double* out) {
 int pgpfa_dual_fixed_point(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int start, int max_outer, double tol, double* fopt, int32_t* outer,
                            int32_t* vstatus, double* lam_out) {
   if (!c) return fail("null context");
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_fixed_point"));
-  CHK(refuse_observed(c, "pgpfa_dual_fixed_point"));
+  CHK(refuse_dual_tables(c, "pgpfa_dual_fixed_point"));
   if (!fopt || !vstatus) return fail("null argument");
   if (max_outer < 1 || !(tol > 0.0)) return fail("max_outer and tol must be positive");
   if (start < 0 || start > 3) return fail("start must be 0 (cold), 1 (rho is the start), 2 (rho is a previous optimum) or 3 (the resident optimum)");
@@ -353,8 +439,7 @@ int check_distinct(const std::vector<int>& v) {
 int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const double* lam, double* cost, double* grad) {
   PhaseRange range_phase("pgpfa.dual_costgrad_batch");
   if (!c) return fail("null context");
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_costgrad_batch"));
-  CHK(refuse_observed(c, "pgpfa_dual_costgrad_batch"));
+  CHK(refuse_dual_tables(c, "pgpfa_dual_costgrad_batch"));
   if (!lam || !cost) return fail("null argument");
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
@@ -363,14 +448,16 @@ int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const dou
   CHK(ready_estep(c, c->dual_lowrank));
   CHK(ensure_lambda(c));
   const size_t m = (size_t)c->q * c->T;
+  const bool masked = dual_masking(c);                              // (entries that are not live are ignored on input and zeroed on the device)
   for (size_t i = 0; i < (size_t)N * m; ++i)
-    if (!(lam[i] > 0.0)) return fail("lambda must be positive (trial %d, entry %zu = %g)", tr.v[i / m], i % m, lam[i]);
+    if (!(lam[i] > 0.0) && !(masked && !dual_live(c, tr.v[i / m], i % m))) return fail("lambda must be positive (trial %d, entry %zu = %g)", tr.v[i / m], i % m, lam[i]);
   CHK(check_distinct(tr.v));
   for (int c0 = 0; c0 < N; c0 += c->B) {
     const int nb = std::min(c->B, N - c0);
     std::vector<int> tos(tr.v.begin() + c0, tr.v.begin() + c0 + nb);
     CHK(upload_list(c, c->trial_of_slot, tos));
     CHK(upload(c, c->lamd, lam + (size_t)c0 * m, (size_t)nb * m));
+    CHK(dual_mask(c, nb, c->lamd));
     CHK(dual_eval_slots(c, nb, tos, grad != nullptr, cost + c0));
     if (grad) CHK(download(c, grad + (size_t)c0 * m, c->dgrad, (size_t)nb * m));
   }
@@ -386,8 +473,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
                      int32_t* iters) {
   PhaseRange range_phase("pgpfa.dual_lbfgs");
   if (!c) return fail("null context");
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_lbfgs"));
-  CHK(refuse_observed(c, "pgpfa_dual_lbfgs"));
+  CHK(refuse_dual_tables(c, "pgpfa_dual_lbfgs"));
   if (!rho || !fopt) return fail("null argument");
   if (max_iter < 1) return fail("max_iter must be positive");
   Trials tr;
@@ -436,6 +522,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
     auto evaluate = [&](const double* Xin, double* Gout, std::vector<double>& f) -> int {
       n_eval += 1.0;
       hipLaunchKernelGGL(exp_kernel, dim3((unsigned)((nb * m + 255) / 256)), dim3(256), 0, c->st, Xin, c->lamd, nb * m);
+      CHK(dual_mask(c, nb, c->lamd));                                  // (entries that are not live: lambda = 0, gradient 0 - rho never moves there)
       CHK(dual_eval_slots(c, nb, tos, true, f.data(), /*tolerate=*/true));
       hipLaunchKernelGGL(chain_kernel, dim3((unsigned)((nb * m + 255) / 256)), dim3(256), 0, c->st, c->dgrad, c->lamd, Gout, nb * m);
       HIPC(hipGetLastError());
@@ -603,8 +690,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
 // the dual variables resident for the listed trials (the optimum of the last pgpfa_dual_fixed_point, or what pgpfa_dual_finalize was given)
 int pgpfa_get_dual_lambda(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {
   if (!c || !out) return fail("null argument");
-  CHK(refuse_trial_lengths(c, "pgpfa_get_dual_lambda"));
-  CHK(refuse_observed(c, "pgpfa_get_dual_lambda"));
+  CHK(refuse_dual_tables(c, "pgpfa_get_dual_lambda"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   HIPC(hipSetDevice(c->device));
@@ -621,8 +707,7 @@ int pgpfa_get_dual_lambda(pgpfa_ctx* c, int n, const int32_t* idx, double* out) 
 int pgpfa_dual_finalize(pgpfa_ctx* c, int n, const int32_t* idx, const double* lam, double* nlp_sum) {
   PhaseRange range_phase("pgpfa.dual_finalize");
   if (!c) return fail("null context");
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_finalize"));
-  CHK(refuse_observed(c, "pgpfa_dual_finalize"));
+  CHK(refuse_dual_tables(c, "pgpfa_dual_finalize"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
   const int N = (int)tr.v.size();
@@ -656,7 +741,7 @@ int pgpfa_dual_finalize(pgpfa_ctx* c, int n, const int32_t* idx, const double* l
     const int nb = std::min(c->B, N - c0);
     std::vector<int> tos(tr.v.begin() + c0, tr.v.begin() + c0 + nb);
     CHK(upload_list(c, c->trial_of_slot, tos));
-    if (lam) CHK(upload(c, c->lamd, lam + (size_t)c0 * q * c->T, (size_t)nb * q * c->T));
+    if (lam) { CHK(upload(c, c->lamd, lam + (size_t)c0 * q * c->T, (size_t)nb * q * c->T)); CHK(dual_mask(c, nb, c->lamd)); }
     for (int s = 0; s < nb; ++s) {
       const size_t mq = (size_t)q * c->T;
       if (lam) { CHK(copy_dev(c, c->lam_keep + (size_t)tos[s] * mq, c->lamd + (size_t)s * mq, mq * sizeof(double))); c->lam_resident[tos[s]] = 0; c->lam_valid[tos[s]] = 1; }
@@ -669,7 +754,7 @@ int pgpfa_dual_finalize(pgpfa_ctx* c, int n, const int32_t* idx, const double* l
     // posterior mean -K C_big (lambda - y) (inference.py:194) and covariance blocks (inference.py:188-191)
     hipLaunchKernelGGL(negate_rows_kernel, dim3((c->n + 255) / 256, nb), dim3(256), 0, c->st, c->KD, ld, c->Xc, ld, c->n, c->ident);
     if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, true, sum_only)); }
-    else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, true));
+    else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_blocks(c, nb, scale, true)); }
     for (int t : tos) c->vsmgp_ok[t] = sum_only ? 0 : 1;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3((c->n + 255) / 256, nb), dim3(256), 0, c->st, c->Xc, ld, c->n, c->Xmode, c->trial_of_slot);
     for (int t_ : tos) c->mode_serial[t_] = -10;

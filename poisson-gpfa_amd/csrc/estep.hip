@@ -564,6 +564,7 @@ static int start_variational(pgpfa_ctx* c, Chunk& ch, const VarJob* var, const V
     for (int s = 0; s < nb; ++s) CHK(copy_dev(c, c->lamd + (size_t)s * mlam, c->lam_keep + (size_t)ch.tos[s] * mlam, mlam * sizeof(double)));
   } else if (var->start != 0) {
     CHK(upload(c, c->lamd, var->rho + (size_t)ch.c0 * mlam, (size_t)nb * mlam));
+    CHK(dual_mask(c, nb, c->lamd));                                  // (option dual_masked: rho is ignored at entries that are not live)
   }
   int* bad_dev = reinterpret_cast<int*>(c->pcg_ratio);              // (scratch word: no inner solve is running)
   HIPC(hipMemsetAsync(bad_dev, 0, sizeof(int), c->st));
@@ -572,13 +573,14 @@ static int start_variational(pgpfa_ctx* c, Chunk& ch, const VarJob* var, const V
   CHK(dl_enqueue(c, &bad, bad_dev, sizeof(int)));
   CHK(dl_flush(c));
   if (bad) return fail("rho must be finite with a positive finite exp (trials %d..%d)", ch.tos.front(), ch.tos.back());
+  CHK(dual_mask(c, nb, c->lamd));                                    // (option dual_masked: lambda is exactly 0 where there is no likelihood term)
   std::vector<double> sB_, sD_, vKv_;
   CHK(dual_common(c, nb, &sB_, &sD_, &vKv_));
   // (only when lambda is a previous optimum: from a cold lambda that mean is far out - hundreds in the log rate - and zero is the safe start)
   if (var->start >= 2) hipLaunchKernelGGL(negate_rows_kernel, dim3((nvec + 255) / 256, nb), dim3(256), 0, c->st, c->KD, ld, c->Xc, ld, nvec, c->ident);
   else HIPC(hipMemsetAsync(c->Xc, 0, (size_t)ld * nb * sizeof(double), c->st));
   if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }
-  else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
+  else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_blocks(c, nb, scale, false)); }
   CHK(var_offsets(c, nb, c->voff));
   c->var_active = true;
   return 0;
@@ -1238,8 +1240,9 @@ static int var_pass(pgpfa_ctx* c, Chunk& ch, const VarJob* var, VarState& vs, in
   c->lam_out_active = true;
   CHK(poisson(c, c->ident, nb, c->Xc, c->Glt, c->Wt, c->sc_f, 0));        // lambda = exp(C m + d + offset) -> c->lamd
   c->lam_out_active = false;
+  CHK(dual_mask(c, nb, c->lamd));
   if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, false, false)); }   // (c->W: curvature at the modes = C^T diag(lambda) C)
-  else CHK(posterior_blocks(c, nb, 1.0 + 1e-6, false));
+  else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_blocks(c, nb, scale, false)); }
   CHK(dl_enqueue(c, ch.info.data(), c->ws.info, sizeof(int) * nb));
   CHK(dl_flush(c));
   for (int s = 0; s < nb; ++s)
@@ -1302,6 +1305,7 @@ static int var_finish(pgpfa_ctx* c, Chunk& ch, const VarJob* var, const VarState
   if (var->lam_out) CHK(download(c, var->lam_out + (size_t)c0 * mlam, c->lamd, (size_t)nb * mlam));
   if (var->rho) {
     hipLaunchKernelGGL(var_log_kernel, dim3(2048), dim3(256), 0, c->st, (const double*)c->lamd, c->dgrad, (size_t)nb * mlam);
+    CHK(dual_mask(c, nb, c->dgrad));                                 // (option dual_masked: rho comes back as 0 where lambda is 0)
     CHK(download(c, var->rho + (size_t)c0 * mlam, c->dgrad, (size_t)nb * mlam));
   }
   for (int s = 0; s < nb; ++s) {

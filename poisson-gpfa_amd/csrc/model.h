@@ -1626,7 +1626,10 @@ inline __global__ __launch_bounds__(256) void reduce_parts_kernel(const double* 
 //   W[t] = C^T diag(lambda[:,t]) C                                   (posterior precision blocks)
 //   partial sums  sB = sum d_n lmy[n][t] ,  sD = sum lambda (log lambda - 1)
 // grid = (ceil(T/64), nslots), block = 64 threads (one bin each).
+// MASKED (option dual_masked with a table set): lambda and the counts are exactly 0 at entries that are not live - every sum skips them by itself
+// except lambda (log lambda - 1), which is tested.  Without it the kernel is the code it was.
 // --------------------------------------------------------------------------------------------------
+template <bool MASKED = false>
 inline __global__ void dual_prep_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C, const double* __restrict__ d,
                                  const double* __restrict__ lam, long long sLam, double* __restrict__ V, long long sV,
                                  double* __restrict__ W, long long sW, double* __restrict__ part, int ntile,
@@ -1654,7 +1657,7 @@ inline __global__ void dual_prep_kernel(const uint8_t* __restrict__ Y, const uin
     for (int n = 0; n < q; ++n) {
       const double l = L[(size_t)n * T + t];
       sB += d[n] * (l - (double)count_at(Yr, Yh, (size_t)n * T + t));
-      sD += l * (log(l) - 1.0);
+      if (!MASKED || l > 0.0) sD += l * (log(l) - 1.0);         // (one expression for both instantiations: the same contraction, the same bits)
     }
   }
   for (int off = 32; off > 0; off >>= 1) { sB += __shfl_down(sB, off); sD += __shfl_down(sD, off); }

@@ -90,7 +90,7 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
       std::vector<double> sB, sD, vKv;
       CHK(dual_common(c, nb, &sB, &sD, &vKv));
       if (lr) { CHK(dual_jitter(c, nb)); CHK(posterior_factor_only(c, nb, 1.0)); }
-      else CHK(posterior_factor_only(c, nb, 1.0 + 1e-6));
+      else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_factor_only(c, nb, scale)); }
     } else {
       hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, n, c->Xc, (long long)c->ld, c->trial_of_slot, 0);
       CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));

@@ -316,6 +316,15 @@ class DeviceOptimRes(LazyTrialList):
         return True
 
 
+def log_live(lam):
+    """log of dual variables in their padded layout: entries that are not live hold lambda = 0 (inference.DUAL_MASKED) and come back as rho = 0."""
+    lam = np.asarray(lam, dtype=np.float64)
+    if np.all(lam > 0.0):
+        return np.log(lam)
+    live = lam > 0.0
+    return np.where(live, np.log(np.where(live, lam, 1.0)), 0.0)
+
+
 class DeviceDualOptimRes(LazyTrialList):
     """varOptimRes of inference.dualVariational (inference.py:326 / 398: the optimal lambda, or rho = log lambda, per trial) left on the
     device: an entry is downloaded when it is read, and handed back as prevOptimRes of the next call on the same trials it is a warm start that
@@ -326,7 +335,7 @@ class DeviceDualOptimRes(LazyTrialList):
     def __init__(self, session, trial_idx, log):
         tid = np.asarray(trial_idx, dtype=np.int32)
         ctx = session.ctx
-        super().__init__(len(tid), lambda i: self._fresh(i) and (np.log(ctx.dual_lambda(tid[i:i + 1])[0]) if log else ctx.dual_lambda(tid[i:i + 1])[0]))
+        super().__init__(len(tid), lambda i: self._fresh(i) and (log_live(ctx.dual_lambda(tid[i:i + 1])[0]) if log else ctx.dual_lambda(tid[i:i + 1])[0]))
         self.session = session
         self.trial_idx = tid
         self.log = bool(log)
@@ -352,7 +361,7 @@ class DeviceDualOptimRes(LazyTrialList):
             part = missing[c0:c0 + step]
             lam = self.session.ctx.dual_lambda(self.trial_idx[part])
             for j, i in enumerate(part):
-                self._cache[i] = np.log(lam[j]) if self.log else lam[j].copy()
+                self._cache[i] = log_live(lam[j]) if self.log else lam[j].copy()
         return self
 
 
@@ -442,6 +451,19 @@ class Session:
             else:
                 raise ValueError('prevOptimRes entry %d has %d values; trial %d has %d bins (xdim*T_r = %d)' % (j, x.size, int(t), L, self.p * L))
         return X.reshape(len(rows), -1)
+
+    def live_mask(self, trials):
+        """Boolean (n, q*T) array over the padded dual variables of the listed trials: True where entry (neuron, bin) has a likelihood term - the bin
+        lies inside the trial's own T_r bins and the neuron was recorded on the trial.  None when no table is set (every entry is live)."""
+        if self.lengths is None and getattr(self, 'observed', None) is None:
+            return None
+        trials = np.asarray(trials, dtype=np.int64)
+        live = np.ones((len(trials), self.q, self.T), dtype=bool)
+        if self.lengths is not None:
+            live &= (np.arange(self.T)[None, :] < self.lengths[trials][:, None])[:, None, :]
+        if self.observed is not None:
+            live &= self.observed[trials][:, :, None]
+        return live.reshape(len(trials), -1)
 
     def refuse_unequal(self, what):
         """Entry points that do not know per-trial lengths must not run on padded data as if the padding were observed."""

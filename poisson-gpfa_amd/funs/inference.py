@@ -12,7 +12,7 @@ K_bigInv, xdim, ydim) but are also offered in the structured form the device eva
 import numpy as np
 
 from . import _hip
-from ._session import DeviceDualOptimRes, DeviceInfRes, DeviceOptimRes, session_for
+from ._session import DeviceDualOptimRes, DeviceInfRes, DeviceOptimRes, log_live, session_for
 
 # covariance engine of every context this module creates: None = the library's choice (low-rank when it pays), 1 = dense, 2 = low-rank
 # (tests pin one or the other; results agree to the low-rank tolerance)
@@ -409,6 +409,13 @@ LAPLACE_F32 = False
 # both are None and the E-step is the default one, bit for bit.  Not available together with LAPLACE_F32 (the call fails).  laplace() sends it
 # on every call; engine.PPGPFAfit(trackEvidence=True) and util.crossValidation(score='evidence') switch it on around their own E-steps.
 LAPLACE_EVIDENCE = False
+# dualVariational on trials of unequal length (experiment.data[r]['Y'] of shape (ydim, T_r)) and / or with neurons unobserved on some trials
+# (experiment.data[r]['observed']) - C-ABI option dual_masked, sent on every call.  False: such experiments are refused, as every pgpfa_dual_*
+# entry point refuses them.  True: every trial's optimum, cost, posterior mean and covariance are those of the reference's functions on the trial's
+# reduced problem (unobserved rows of Y, C, d deleted, bins cut to T_r), jitter included; varOptimRes entries keep their
+# padded (ydim*T,) layout with zeros at entries without a likelihood term, and are accepted back as prevOptimRes.  Without a table the flag
+# changes nothing, bit for bit.
+DUAL_MASKED = False
 
 
 class _ConcurrentProblems:
@@ -494,17 +501,25 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     the GPU in structured form: W_t = C^T diag(lambda_t) C, one Cholesky of the (xdim*T)^2 precision for the
     log-determinant, its inverse's per-bin blocks for c_n^T Sigma_t c_n - C_big and diag(lambda) are never formed.
     Returns (infRes, -mean negLogPosterior at the VI means, mean dual optimum[, varOptimRes]).
+    With DUAL_MASKED set, trials may differ in length and neurons may be unobserved on some trials, as in laplace(): infRes entries of trial r have
+    T_r bins, and varOptimRes[r] stays a padded (ydim*T,) array (T: the longest trial) with zeros at entries without a likelihood term.
     """
     import scipy.optimize as op
     sess, trial_idx = _prepare(experiment, params)
-    sess.refuse_unequal('dualVariational')
-    sess.refuse_unobserved('dualVariational')
+    masked = bool(DUAL_MASKED)
+    if not masked:
+        sess.refuse_unequal('dualVariational')
+        sess.refuse_unobserved('dualVariational')
+    sess.ctx.set_option('dual_masked', int(masked))
     n_all = len(trial_idx)
     local_shard = bool(getattr(experiment, '_pgpfa_local_shard', False))
     lo, hi = (0, n_all) if local_shard else sess.local_slice(n_all)
     mine = trial_idx[lo:hi]
     m = sess.q * sess.T
     ctx = sess.ctx
+    # DUAL_MASKED with a table set: which entries of the padded dual variables have a likelihood term (None: all).  The device ignores whatever
+    # the others hold on input and keeps lambda = 0 there; on the host they are 0 in lambda and in rho
+    live = sess.live_mask(mine) if masked else None
     # DUAL_LOWRANK: the dual is evaluated through the low-rank covariance engine when that pays (large xdim*T), with the
     # reference's 1e-6 diagonal jitter (inference.py:190) carried by the per-bin blocks; otherwise the dense engine
     ctx.set_option('dual_lowrank', 1 if DUAL_LOWRANK else 0)
@@ -515,6 +530,8 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
         def prev_rho():
             prev = np.stack([np.asarray(prevOptimRes[j] if len(prevOptimRes) == len(mine) else prevOptimRes[lo + j], dtype=np.float64)
                              for j in range(len(mine))])
+            if live is not None:
+                return np.where(live, prev if optimizeLogLambda else np.log(np.maximum(prev, 1e-300)), 0.0)
             return prev if optimizeLogLambda else np.log(np.maximum(prev, 1e-300))
         lam_all = None
         if DUAL_SOLVER == 'fixedpoint':
@@ -530,12 +547,13 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
             res = ctx.dual_fixed_point(mine, None if (prevOptimRes is None or resident) else prev_rho(), max_outer=DUAL_FP_MAX_PASSES, tol=DUAL_FP_TOL,
                                        warm=prevOptimRes is not None, resident=resident, want_rho=False)
             fopt, iters, vstat = res[1:4]
+            fp_status = np.array(vstat, copy=True)           # (before the handed-back trials are finished below)
             bad = np.nonzero(vstat != 0)[0]
             if len(bad):
                 # (rare: bring the whole optimum to the host, finish the handed-back trials there, finalize from the host copy)
                 lam_all = ctx.dual_lambda(mine)
-                rho_b, fopt_b, it_b = ctx.dual_lbfgs(mine[bad], np.log(lam_all[bad]))
-                lam_all[bad], fopt[bad] = np.exp(rho_b), fopt_b
+                rho_b, fopt_b, it_b = ctx.dual_lbfgs(mine[bad], log_live(lam_all[bad]))
+                lam_all[bad], fopt[bad] = (np.exp(rho_b) if live is None else np.where(live[bad], np.exp(rho_b), 0.0)), fopt_b
                 iters[bad] += it_b
             nlp = ctx.dual_finalize(mine, lam_all)           # (None: the optimum the fixed point left on the device)
             sess.mark_written(mine)
@@ -544,6 +562,8 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
             tot = sess.allreduce(np.array([nlp, float(np.sum(fopt)), float(len(mine))]))
             infRes = DeviceInfRes(sess, mine, (lo, hi))
             infRes.dual_iterations = iters
+            # status of the fixed point per trial: 0 converged, 1 pass cap, 2 not contracting (1 and 2 were finished by L-BFGS above)
+            infRes.dual_status = fp_status
             if returnOptimRes:
                 return infRes, -tot[0] / tot[2], tot[1] / tot[2], optim
             return infRes, -tot[0] / tot[2], tot[1] / tot[2]
@@ -552,8 +572,10 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
                 rho0 = np.zeros((len(mine), m)) if optimizeLogLambda else np.full((len(mine), m), np.log(0.5))
             else:
                 rho0 = prev_rho()
+            if live is not None:
+                rho0 = np.where(live, rho0, 0.0)                # (the lockstep L-BFGS never moves them: zero gradient)
             rho, fopt, iters = ctx.dual_lbfgs(mine, rho0)
-            lam_all = np.exp(rho)
+            lam_all = np.exp(rho) if live is None else np.where(live, np.exp(rho), 0.0)
             optim = list(rho) if optimizeLogLambda else list(lam_all)
             nlp = ctx.dual_finalize(mine, lam_all)
         sess.mark_written(mine)
@@ -601,8 +623,14 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
                                 bounds=[(1e-10, None)] * m, factr=1e7, disp=False)
 
     outs = _ConcurrentProblems(len(mine), evaluate_batch).run(solve_one) if len(mine) else []
-    optim = [out[0] for out in outs]
-    lams = [np.exp(out[0]) if optimizeLogLambda else out[0] for out in outs]
+    if live is not None:
+        # entries without a likelihood term kept their start value through the run (the device ignores them and returns a zero gradient there);
+        # the returned varOptimRes holds 0 there, in lambda and in rho
+        optim = [np.where(live[j], out[0], 0.0) for j, out in enumerate(outs)]
+        lams = [np.where(live[j], np.exp(out[0]) if optimizeLogLambda else out[0], 0.0) for j, out in enumerate(outs)]
+    else:
+        optim = [out[0] for out in outs]
+        lams = [np.exp(out[0]) if optimizeLogLambda else out[0] for out in outs]
     vlb = float(sum(out[1] for out in outs))
     nlp = ctx.dual_finalize(mine, np.stack(lams)) if len(mine) else 0.0
     sess.mark_written(mine)

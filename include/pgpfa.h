@@ -201,6 +201,7 @@ int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
  * "last_fallback_outer_cap" (slots the shared-preconditioner Newton phase gave up on, by reason); of the context: "plans" and "plan_ms_total"
  * (workspace plans made and their time), "arena_grow_ms_total" (of it: mapping memory), "set_params_calls"; "trial_lengths_set" (1 while
  * pgpfa_set_trial_lengths has given the trials bin counts of their own, 0 when every trial has T bins); "observed_set" (1 while pgpfa_set_observed has marked (trial, neuron) pairs as not recorded, else 0);
+ * "observed_bins_set" (1 while pgpfa_set_observed_bins has given the context a per-bin table, else 0);
  * "last_cd_unobserved_neurons" (neurons without an observed trial in the list of the last (C,d) M-step pass). */
 int pgpfa_get_info(pgpfa_ctx* ctx, const char* key, double* value);
 
@@ -230,6 +231,17 @@ int pgpfa_set_trial_lengths(pgpfa_ctx* ctx, const int32_t* len /* [R], NULL: all
  * step (only a prior moves it).  With no table every kernel takes the branch it took before.  The dual-variational entry points, pgpfa_loo_predict and
  * pgpfa_generate do not know the table and fail while it is set (info key "observed_set"). */
 int pgpfa_set_observed(pgpfa_ctx* ctx, const uint8_t* obs /* [R][q], non-zero = observed; NULL: all observed, drops the table */);
+/* Single entries not recorded (a channel that drops out for part of a trial, a blanked artifact, speckled hold-out): live[R][q][T], non-zero = entry
+ * (r, n, t) was recorded; NULL drops the table.  Called after the counts are uploaded.  The table composes with pgpfa_set_trial_lengths and
+ * pgpfa_set_observed by AND, in any order of the three calls: an entry is live when t < T_r, obs[r][n] is set and live[r][n][t] is.  Trial r's
+ * likelihood is the sum over its live entries of exp(h_nt) - y_nt h_nt; the prior is unchanged, so posterior, objective and evidence are those of the
+ * model marginalised over the dead entries, and the (C,d) M-step sums run over live entries.  The call (and a later call of the other two setters
+ * while a table is set) fails, naming the first offender, when a trial is left without a live entry, a neuron has no live entry on any trial, or a
+ * count at a dead entry is non-zero; counts uploaded while a table is set are checked again.  Setting or dropping the table supersedes resident
+ * posteriors.  A table that marks every entry live computes what no table computes, through other kernel instantiations.  The dual-variational
+ * entry points (also under the option dual_masked), pgpfa_loo_predict and pgpfa_generate do not know the table and fail while it is set (info key
+ * "observed_bins_set"). */
+int pgpfa_set_observed_bins(pgpfa_ctx* ctx, const uint8_t* live /* [R][q][T], non-zero = recorded; NULL drops the table */);
 /* resident counts of the listed trials (idx NULL: all) as uint16 [n][q][T] */
 int pgpfa_get_counts_u16(pgpfa_ctx* ctx, int n, const int32_t* idx, uint16_t* out);
 /* params = {'C': [q][p], 'd': [q], 'tau': [p] seconds} (engine.py:40-44).  Builds the p Gram

@@ -983,6 +983,7 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   c->info["counts_two_bytes"] = 0.0;
   c->info["trial_lengths_set"] = 0.0;
   c->info["observed_set"] = 0.0;
+  c->info["observed_bins_set"] = 0.0;
   c->info["last_cd_unobserved_neurons"] = 0.0;
   c->info["arena_bytes"] = 0.0;
   c->info["last_eps_wt_norm"] = 0.0;
@@ -1014,6 +1015,8 @@ int pgpfa_destroy(pgpfa_ctx* c) {
   if (c->Yhi) hipFree(c->Yhi);
   if (c->trial_len) hipFree(c->trial_len);
   if (c->obs) hipFree(c->obs);
+  if (c->binw) hipFree(c->binw);
+  if (c->nlive) hipFree(c->nlive);
   if (c->trunc_q) hipFree(c->trunc_q);
   arena_release(c);
   if (c->hbuf) hipHostFree(c->hbuf);
@@ -1233,6 +1236,142 @@ int ensure_high_plane(pgpfa_ctx* c) {
   return 0;
 }
 
+// ---- single entries not recorded (per-bin table) ----------------------------------------------------------------------------------
+static void drop_observed_bins(pgpfa_ctx* c) {
+  if (c->binw) {
+    hipStreamSynchronize(c->st);
+    hipFree(c->binw);
+    hipFree(c->nlive);
+    const size_t nw = (size_t)(c->T + 63) / 64;
+    c->bytes -= (size_t)c->R * (c->q + 1) * nw * sizeof(unsigned long long) + (size_t)c->R * c->q * sizeof(int);
+    c->binw = nullptr;
+    c->nlive = nullptr;
+  }
+  c->nlive_h.clear();
+  c->bins_h.clear();
+  c->info["observed_bins_set"] = 0.0;
+}
+
+int refuse_observed_bins(const pgpfa_ctx* c, const char* entry) {
+  if (c && c->binw)
+    return fail("%s does not support a per-bin observation table yet: one is set (pgpfa_set_observed_bins) and the entries it marks as not "
+                "recorded would be treated as zero counts", entry);
+  return 0;
+}
+
+// One word of 64 bins per workgroup (a single wave): bit t & 63 of words[r][n][t >> 6] = entry (r, n, t) is live - marked in raw (may be NULL: all),
+// inside the trial's length (len may be NULL) and the neuron recorded on the trial (obs may be NULL).  Row q of a trial collects the OR over its
+// neurons, nlive[r][n] the popcounts, bad[r] the non-zero counts at entries that are not live (either byte plane).  words, nlive and bad come in
+// zeroed.  With raw, len and obs all NULL and `check` set it only counts against the finished words (counts uploaded under a table).
+// grid = R q ceil(T/64), block = 64
+static __global__ __launch_bounds__(64) void pack_bins_kernel(const uint8_t* __restrict__ raw, const int* __restrict__ len, const uint8_t* __restrict__ obs,
+                                                              const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, int q, int T, int nw,
+                                                              unsigned long long* __restrict__ words, int* __restrict__ nlive, int* __restrict__ bad, int check) {
+  const int lane = threadIdx.x;
+  const int w = blockIdx.x % nw, n = (blockIdx.x / nw) % q;
+  const size_t r = blockIdx.x / ((unsigned)nw * q);
+  const int t = w * 64 + lane;
+  const bool in = t < T;
+  const size_t e = (r * q + n) * T + (in ? t : 0);
+  const size_t wi = (r * (q + 1) + n) * nw + w;
+  bool live;
+  if (check) live = (words[wi] >> lane) & 1ull;
+  else live = in && (!raw || raw[e] != 0) && (!len || t < len[r]) && (!obs || obs[r * q + n] != 0);
+  const bool nz = in && !live && (Y[e] != 0 || (Yhi && Yhi[e] != 0));
+  const unsigned long long m = __ballot(live), b = __ballot(nz);
+  if (lane == 0) {
+    if (!check) {
+      words[wi] = m;
+      if (m) {
+        atomicAdd(&nlive[r * q + n], __popcll(m));
+        atomicOr(&words[(r * (q + 1) + q) * nw + w], m);
+      }
+    }
+    if (b) atomicAdd(&bad[r], __popcll(b));
+  }
+}
+
+// The device image of the per-bin table from the host copy c->bins_h and the given length and observation tables (device pointers, either may be
+// NULL): built, validated - every trial and every neuron keeps a live entry, counts at dead entries are zero - and only then put in place of the
+// one before.  On failure the context keeps what it had.
+static int rebuild_observed_bins(pgpfa_ctx* c, const int* dlen, const uint8_t* dobs) {
+  const int R = c->R, q = c->q, T = c->T, nw = (T + 63) / 64;
+  const size_t nraw = (size_t)R * q * T, nwords = (size_t)R * (q + 1) * nw, nblocks = (size_t)R * q * nw;
+  if (nblocks > 0x7fffffffull) return fail("pgpfa_set_observed_bins: R q ceil(T/64) = %zu exceeds the grid limit", nblocks);
+  uint8_t* draw = nullptr;
+  unsigned long long* dw = nullptr;
+  int *dnl = nullptr, *dbad = nullptr;
+  auto release = [&]() { if (draw) hipFree(draw); if (dw) hipFree(dw); if (dnl) hipFree(dnl); if (dbad) hipFree(dbad); };
+  if (hipMalloc((void**)&draw, nraw) != hipSuccess || hipMalloc((void**)&dw, nwords * sizeof(unsigned long long)) != hipSuccess ||
+      hipMalloc((void**)&dnl, (size_t)R * q * sizeof(int)) != hipSuccess || hipMalloc((void**)&dbad, (size_t)R * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    release();
+    return fail("hipMalloc for the per-bin observation table failed");
+  }
+  std::vector<int> nl((size_t)R * q, 0), bad(R, 0);
+  hipMemcpyAsync(draw, c->bins_h.data(), nraw, hipMemcpyHostToDevice, c->st);
+  hipMemsetAsync(dw, 0, nwords * sizeof(unsigned long long), c->st);
+  hipMemsetAsync(dnl, 0, (size_t)R * q * sizeof(int), c->st);
+  hipMemsetAsync(dbad, 0, (size_t)R * sizeof(int), c->st);
+  hipLaunchKernelGGL(pack_bins_kernel, dim3((unsigned)nblocks), dim3(64), 0, c->st, draw, dlen, dobs, c->Y, c->Yhi, q, T, nw, dw, dnl, dbad, 0);
+  hipMemcpyAsync(nl.data(), dnl, (size_t)R * q * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  hipMemcpyAsync(bad.data(), dbad, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  hipError_t e = hipStreamSynchronize(c->st);            // (the host vectors and the device temporaries outlive every copy and the kernel)
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(draw); draw = nullptr;
+  hipFree(dbad); dbad = nullptr;
+  if (e != hipSuccess) { release(); return fail("pgpfa_set_observed_bins: %s", hipGetErrorString(e)); }
+  for (int r = 0; r < R; ++r) {
+    long long seen = 0;
+    for (int n = 0; n < q; ++n) seen += nl[(size_t)r * q + n];
+    if (!seen) { release(); return fail("trial %d has no live entry under the per-bin table (with lengths and the observation table folded in)", r); }
+  }
+  for (int n = 0; n < q; ++n) {
+    long long seen = 0;
+    for (int r = 0; r < R; ++r) seen += nl[(size_t)r * q + n];
+    if (!seen) { release(); return fail("neuron %d has no live entry on any trial under the per-bin table", n); }
+  }
+  for (int r = 0; r < R; ++r)
+    if (bad[r]) {
+      release();
+      return fail("trial %d: %d non-zero counts at entries the per-bin table marks as not recorded: the count tensor must be zero there", r, bad[r]);
+    }
+  if (c->binw) {
+    hipFree(c->binw);
+    hipFree(c->nlive);
+  } else {
+    c->bytes += nwords * sizeof(unsigned long long) + (size_t)R * q * sizeof(int);
+  }
+  c->binw = dw;
+  c->nlive = dnl;
+  c->nlive_h.swap(nl);
+  c->info["observed_bins_set"] = 1.0;
+  return 0;
+}
+
+// counts uploaded while a per-bin table is set must be zero at its dead entries; on failure the context has no counts (the caller uploads again)
+static int recheck_observed_bins(pgpfa_ctx* c) {
+  if (!c->binw) return 0;
+  const int R = c->R, nw = (c->T + 63) / 64;
+  int* dbad = nullptr;
+  if (hipMalloc((void**)&dbad, (size_t)R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail("hipMalloc failed"); }
+  std::vector<int> bad(R, 0);
+  hipMemsetAsync(dbad, 0, (size_t)R * sizeof(int), c->st);
+  hipLaunchKernelGGL(pack_bins_kernel, dim3((unsigned)((size_t)R * c->q * nw)), dim3(64), 0, c->st, (const uint8_t*)nullptr, (const int*)nullptr,
+                     (const uint8_t*)nullptr, c->Y, c->Yhi, c->q, c->T, nw, c->binw, c->nlive, dbad, 1);
+  hipMemcpyAsync(bad.data(), dbad, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  hipError_t e = hipStreamSynchronize(c->st);
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(dbad);
+  if (e != hipSuccess) { c->have_counts = false; return fail("pgpfa_upload_counts: %s", hipGetErrorString(e)); }
+  for (int r = 0; r < R; ++r)
+    if (bad[r]) {
+      c->have_counts = false;
+      return fail("trial %d: %d non-zero counts at entries the per-bin table marks as not recorded: the count tensor must be zero there", r, bad[r]);
+    }
+  return 0;
+}
+
 // ---- trials of unequal length --------------------------------------------------------------------------------------------------
 static void drop_trial_lengths(pgpfa_ctx* c) {
   if (c->trial_len) {
@@ -1275,7 +1414,11 @@ int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
   if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
   HIPC(hipSetDevice(c->device));
   if (!len) {                                               // back to R trials of T bins; what was computed under the table is stale
-    if (c->trial_len) { drop_trial_lengths(c); counts_changed(c, nullptr); }
+    if (c->trial_len) {
+      if (c->binw) CHK(rebuild_observed_bins(c, nullptr, c->obs));     // (the per-bin words carry the lengths: built anew without them)
+      drop_trial_lengths(c);
+      counts_changed(c, nullptr);
+    }
     return 0;
   }
   for (int r = 0; r < c->R; ++r)
@@ -1296,6 +1439,7 @@ int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
       hipFree(dlen);
       return fail("trial %d: %d non-zero counts at padded bins (t >= %d): the count tensor must be zero-padded behind a trial's length", r, bad[r], lv[r]);
     }
+  if (c->binw && rebuild_observed_bins(c, dlen, c->obs)) { hipFree(dlen); return 1; }   // (the per-bin words carry the lengths; a trial these leave without a live entry fails here)
   drop_trial_lengths(c);
   c->trial_len = dlen;
   c->bytes += (size_t)c->R * sizeof(int);
@@ -1363,7 +1507,11 @@ int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
   if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
   HIPC(hipSetDevice(c->device));
   if (!obs) {                                               // back to fully observed trials; what was computed under the table is stale
-    if (c->obs) { drop_observed(c); counts_changed(c, nullptr); }
+    if (c->obs) {
+      if (c->binw) CHK(rebuild_observed_bins(c, c->trial_len, nullptr));   // (the per-bin words carry the table: built anew without it)
+      drop_observed(c);
+      counts_changed(c, nullptr);
+    }
     return 0;
   }
   const size_t nq = (size_t)c->R * c->q;
@@ -1383,6 +1531,7 @@ int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
   HIPC(hipMalloc((void**)&dobs, nq));
   hipMemcpyAsync(dobs, ov.data(), nq, hipMemcpyHostToDevice, c->st);
   if (check_unobserved_counts(c, dobs)) { hipFree(dobs); return 1; }
+  if (c->binw && rebuild_observed_bins(c, c->trial_len, dobs)) { hipFree(dobs); return 1; }   // (the per-bin words carry the table)
   drop_observed(c);
   c->obs = dobs;
   c->bytes += nq;
@@ -1392,11 +1541,33 @@ int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
   return 0;
 }
 
+int pgpfa_set_observed_bins(pgpfa_ctx* c, const uint8_t* live) {
+  if (!c) return fail("null context");
+  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_observed_bins checks them");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  if (!live) {                                              // back to the length and observation tables alone; what was computed under the table is stale
+    if (c->binw) { drop_observed_bins(c); counts_changed(c, nullptr); }
+    return 0;
+  }
+  const size_t n = (size_t)c->R * c->q * c->T;
+  std::vector<uint8_t> bv(n);
+  for (size_t i = 0; i < n; ++i) bv[i] = live[i] ? 1 : 0;
+  c->bins_h.swap(bv);                                       // (rebuild reads the host copy; the one before comes back if the new table is refused)
+  if (rebuild_observed_bins(c, c->trial_len, c->obs)) { c->bins_h.swap(bv); return 1; }
+  counts_changed(c, nullptr);                               // sums and posteriors computed under another table are stale
+  return 0;
+}
+
 // counts uploaded while a table is set must be zero at its unobserved rows; on failure the context has no counts (the caller uploads again)
 static int recheck_observed(pgpfa_ctx* c) {
   if (!c->obs) return 0;
   if (check_unobserved_counts(c, c->obs)) { c->have_counts = false; return 1; }
   return 0;
+}
+static int recheck_tables(pgpfa_ctx* c) {
+  CHK(recheck_observed(c));
+  return recheck_observed_bins(c);
 }
 
 int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
@@ -1409,7 +1580,7 @@ int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = 0.0;
-  return recheck_observed(c);
+  return recheck_tables(c);
 }
 
 // counts from a host array of TS (double or uint16): validated and split into byte planes on the device, staged in pieces
@@ -1457,7 +1628,7 @@ static int upload_counts_wide(pgpfa_ctx* c, const TS* Y) {
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = c->Yhi ? 1.0 : 0.0;
-  return recheck_observed(c);
+  return recheck_tables(c);
 }
 
 int pgpfa_upload_counts_f64(pgpfa_ctx* c, const double* Y) {

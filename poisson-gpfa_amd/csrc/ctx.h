@@ -103,6 +103,13 @@ struct pgpfa_ctx {
   // (checked), no rate in the Poisson pass, the cold objective and the (C,d) passes.  NULL: every neuron is observed on every trial.
   uint8_t* obs = nullptr;                        // device [R][q]
   std::vector<uint8_t> obs_h;                    // host copy (neurons without an observed trial in an M-step list); empty while obs is NULL
+  // Single entries not recorded (pgpfa_set_observed_bins).  The caller's table stays on the host (bins_h, one byte per entry); the device holds it as
+  // bit words of 64 bins with lengths and obs folded in, [R][q + 1][ceil(T/64)] (row q of a trial: OR over its neurons - bin_words, model.h), rebuilt
+  // whenever one of the three tables changes, and the live entries per (trial, neuron).  NULL: no per-bin table.
+  unsigned long long* binw = nullptr;            // device [R][q + 1][ceil(T/64)]
+  int* nlive = nullptr;                          // device [R][q]
+  std::vector<int> nlive_h;                      // host copy (cold objective aside: neurons without a live entry in an M-step list)
+  std::vector<uint8_t> bins_h;                   // the caller's table [R][q][T], 0 / 1; empty while binw is NULL
   double *C = nullptr, *d = nullptr, *tau = nullptr;
   double *Kpad = nullptr, *Kinv = nullptr;      // [p][Tp][Tp]
   double* Xmode = nullptr;                       // [R][p][T]   post_mean / warm start
@@ -453,6 +460,7 @@ int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
 int resolve_trials(pgpfa_ctx* c, int n, const int32_t* idx, Trials* out, bool distinct = false);
 void counts_changed(pgpfa_ctx* c, const std::vector<int>* trials);
+int refuse_observed_bins(const pgpfa_ctx* c, const char* entry);      // fails while a per-bin table is set: entry points that do not know it
 int refuse_observed(const pgpfa_ctx* c, const char* entry);           // fails while an observation table is set: entry points that do not know it
 int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry);      // fails while per-trial bin counts are set: entry points that do not know them
 int ensure_high_plane(pgpfa_ctx* c);

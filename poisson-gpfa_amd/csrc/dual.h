@@ -66,12 +66,16 @@ inline __global__ __launch_bounds__(256) void dual_pre_kernel(const uint8_t* __r
 //   h = C x + d [+ off],  lam = exp(h),  lmy = lam - y,  partial objective sum_n,t lam - y h per (slot, 64-bin tile)
 // - the q x p x T product as a vector kernel (2 % of the flops of the pass: W_t = C^T diag(lam_t) C and C^T (lam - y) follow as the GEMMs of the dual
 // evaluation against the pair / loading table).  len (may be NULL): per-trial bin counts, bins behind them get lam = lmy = 0; obs (may be NULL): [R][q] bytes,
-// rows of neurons not recorded on the trial get lam = lmy = 0 likewise.  grid = (ceil(T/64), nslots), block = 256 (lanes = bins, the 4 waves take interleaved neurons).
-inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C,
-                                                         const double* __restrict__ d, const double* __restrict__ X, long long sX,
-                                                         const double* __restrict__ off, double* __restrict__ lam, double* __restrict__ lmy,
-                                                         double* __restrict__ fpart, const int* __restrict__ slots,
-                                                         const int* __restrict__ trial_of_slot, const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int p, int T) {
+// rows of neurons not recorded on the trial get lam = lmy = 0 likewise; bins (may be NULL): the per-bin table of pgpfa_set_observed_bins as words of 64
+// bins, [R][q + 1][ceil(T/64)] (bin_words, model.h) - entries whose bit is clear get lam = lmy = 0.  grid = (ceil(T/64), nslots), block = 256 (lanes = bins, the 4 waves take interleaved neurons).
+// BINS: the per-bin table is a kernel of its own (rates_wide_bins_kernel) around the same body, so that the kernel launched without one is the code it was.
+template <bool BINS>
+__device__ __forceinline__ void rates_wide_body(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C,
+                                                const double* __restrict__ d, const double* __restrict__ X, long long sX,
+                                                const double* __restrict__ off, double* __restrict__ lam, double* __restrict__ lmy,
+                                                double* __restrict__ fpart, const int* __restrict__ slots,
+                                                const int* __restrict__ trial_of_slot, const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int p, int T,
+                                                const unsigned long long* __restrict__ bins) {
   extern __shared__ double rw_x[];                 // [p][64]
   __shared__ double red[4];
   const size_t slot = slots[blockIdx.y];
@@ -81,6 +85,7 @@ inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* _
   const bool valid = t < T;
   const int Tl = len ? len[trial] : T;             // bins of this trial with a likelihood term (no table: all T)
   const uint8_t* ob = obs ? obs + trial * q : nullptr;   // (uniform over the workgroup; no table: every neuron observed)
+  const unsigned long long* bw = BINS ? bins + trial * (size_t)(q + 1) * gridDim.x + blockIdx.x : nullptr;   // (this block's word of each neuron row)
   for (int e = threadIdx.x; e < p * 64; e += 256) {
     const int l = e >> 6, tt = t0 + (e & 63);
     rw_x[e] = tt < T ? X[slot * sX + (size_t)l * T + tt] : 0.0;
@@ -90,7 +95,7 @@ inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* _
   if (valid) {
     for (int n = wave; n < q; n += 4) {
       const size_t e = slot * (size_t)q * T + (size_t)n * T + t;
-      if (t >= Tl || (ob && ob[n] == 0)) {          // a padded bin or an unobserved neuron: no rate and no count - zero rows of the products that follow
+      if (t >= Tl || (ob && ob[n] == 0) || (BINS && !((bw[(size_t)n * gridDim.x] >> lane) & 1ull))) {   // a padded bin, an unobserved neuron or a dead entry: no rate and no count - zero rows of the products that follow
         lam[e] = 0.0;
         lmy[e] = 0.0;
         continue;
@@ -113,6 +118,20 @@ inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* _
   if (lane == 0) red[wave] = facc;
   __syncthreads();
   if (threadIdx.x == 0) fpart[slot * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+inline __global__ __launch_bounds__(256) void rates_wide_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C,
+                                                         const double* __restrict__ d, const double* __restrict__ X, long long sX,
+                                                         const double* __restrict__ off, double* __restrict__ lam, double* __restrict__ lmy,
+                                                         double* __restrict__ fpart, const int* __restrict__ slots,
+                                                         const int* __restrict__ trial_of_slot, const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int p, int T) {
+  rates_wide_body<false>(Y, Yhi, C, d, X, sX, off, lam, lmy, fpart, slots, trial_of_slot, len, obs, q, p, T, nullptr);
+}
+inline __global__ __launch_bounds__(256) void rates_wide_bins_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ C,
+                                                              const double* __restrict__ d, const double* __restrict__ X, long long sX,
+                                                              const double* __restrict__ off, double* __restrict__ lam, double* __restrict__ lmy,
+                                                              double* __restrict__ fpart, const int* __restrict__ slots,
+                                                              const int* __restrict__ trial_of_slot, const unsigned long long* __restrict__ bins, int q, int p, int T) {
+  rates_wide_body<true>(Y, Yhi, C, d, X, sX, off, lam, lmy, fpart, slots, trial_of_slot, nullptr, nullptr, q, p, T, bins);
 }
 
 // W[slot][t][a][b] = W[slot][t][b][a] = Wp[slot][pair(a,b)][t]: a transpose between the pair-major image of the GEMMs and the per-bin blocks.

@@ -8,6 +8,7 @@ using namespace pgpfa;
 // ---- dual variational E-step (inference.py:188-432) ----------------------------------------------------
 // Option dual_masked: trials of unequal length and unobserved neurons in the dual path (pgpfa_ctx::dual_masked)
 int refuse_dual_tables(const pgpfa_ctx* c, const char* entry) {
+  CHK(refuse_observed_bins(c, entry));                      // (a per-bin table is outside the option too)
   if (c && c->dual_masked) return 0;
   CHK(refuse_trial_lengths(c, entry));
   return refuse_observed(c, entry);
@@ -180,6 +181,7 @@ int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost
 int pgpfa_dual_post_mean(pgpfa_ctx* c, int trial, const double* lam, double* mean) {
   CHK(refuse_trial_lengths(c, "pgpfa_dual_post_mean"));
   CHK(refuse_observed(c, "pgpfa_dual_post_mean"));
+  CHK(refuse_observed_bins(c, "pgpfa_dual_post_mean"));
   CHK(ready(c));
   if (!lam || !mean) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
@@ -232,6 +234,7 @@ static int dual_post_cov_dev(pgpfa_ctx* c, double* cov, double* prec) {
 int pgpfa_dual_post_cov(pgpfa_ctx* c, int trial, const double* lam, double* cov, double* prec) {
   CHK(refuse_trial_lengths(c, "pgpfa_dual_post_cov"));
   CHK(refuse_observed(c, "pgpfa_dual_post_cov"));
+  CHK(refuse_observed_bins(c, "pgpfa_dual_post_cov"));
   CHK(ready(c));
   if (!lam || !cov) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);

@@ -20,6 +20,10 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   // unobserved rows are zero (checked when the table is set), so the count terms (cd_ym_*, count_moments_kernel) and everything behind this pass - the
   // PCG, both covariance engines, the evidence, the single-precision covariance phase, rates and samples - see G, W and the objective of the reduced model.
   a.obs = c->obs;
+  // A per-bin table (pgpfa_set_observed_bins) rides in the same field as words of 64 bins with lengths and the byte table folded in; the kernels
+  // that read it are the instantiations of template state 2 (bin_words, model.h).
+  const bool bins = c->binw != nullptr;
+  if (bins) a.obs = reinterpret_cast<const uint8_t*>(c->binw);
   a.off = c->var_active ? c->voff : nullptr; a.sOff = (long long)c->q * c->T;
   a.lam_out = c->lam_out_active ? c->lamd : nullptr; a.sLam = (long long)c->q * c->T;
   a.q = c->q; a.p = c->p; a.T = c->T; a.ntile = (c->T + 63) / 64; a.full = full;
@@ -34,8 +38,12 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   if (gemm_form) {
     CHK(ensure_lambda(c));
     prof_begin(c, TAG_POISSON, fl);
-    hipLaunchKernelGGL(rates_wide_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
-                       a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->obs, c->q, c->p, c->T);
+    if (bins)                                                     // (lengths and the byte table are folded into the words)
+      hipLaunchKernelGGL(rates_wide_bins_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
+                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, (const unsigned long long*)c->binw, c->q, c->p, c->T);
+    else
+      hipLaunchKernelGGL(rates_wide_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
+                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->obs, c->q, c->p, c->T);
     prof_end(c);
     if (full) {
       const int np = c->p * (c->p + 1) / 2;
@@ -65,19 +73,24 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
     dispatch_pw(c->p, [&](auto pm) {
       constexpr int PW = decltype(pm)::value;
       if constexpr (PW <= 10) {
-        if (a.obs) {                                              // (the instantiations that read the observation table)
+        if (bins) {                                               // (the instantiations that read the per-bin table)
+          if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+          else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        } else if (a.obs) {                                       // (the instantiations that read the observation table)
           if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
           else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
         } else if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
         else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
       } else if constexpr (PW <= 16) {
-        if (a.obs) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        if (bins) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+        else if (a.obs) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
         else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
       }
     });
   } else {
     dispatch_pw(c->p, [&](auto pm) {
-      if (a.obs) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, true>), grid, block, 0, c->st, a);
+      if (bins) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, 2>), grid, block, 0, c->st, a);
+      else if (a.obs) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, true>), grid, block, 0, c->st, a);
       else hipLaunchKernelGGL(poisson_pass_kernel<decltype(pm)::value>, grid, block, 0, c->st, a);
     });
   }
@@ -388,10 +401,12 @@ static int shared_factor(pgpfa_ctx* c, int nb) {
 // the cold start - what a warm start has to beat (estep_impl: a start point that does worse is replaced by zero).  One pass over the slot's count
 // rows (q T bytes).  grid = (slots), block = 256 (a wave per neuron row); mask (may be null): the neuron a leave-one-out item leaves out;
 // len (may be null): per-trial bin counts - a trial of T_r bins has f0 = sum_n (T_r exp(d_n) - d_n sum_t y_nt);
-// obs (may be null): [R][q] bytes - the sum runs over the neurons recorded on the trial.
+// obs (may be null): [R][q] bytes - the sum runs over the neurons recorded on the trial;
+// nlive (may be null): [R][q] live entries per (trial, neuron) under a per-bin table - f0 = sum_n (nlive exp(d_n) - d_n sum_t y_nt).
 static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const double* __restrict__ d,
                                                                     const int* __restrict__ trial_of_slot, const int* __restrict__ mask,
-                                                                    const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int T, double* __restrict__ f0) {
+                                                                    const int* __restrict__ len, const uint8_t* __restrict__ obs, int q, int T, double* __restrict__ f0,
+                                                                    const int* __restrict__ nlive = nullptr) {
   __shared__ double red[4];
   const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t base = (size_t)trial_of_slot[s] * q * T;
@@ -409,7 +424,8 @@ static __global__ __launch_bounds__(256) void cold_objective_kernel(const uint8_
       for (int t = lane; t < T; t += 64) cnt += (unsigned)rh[t] << 8;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-    if (lane == 0) acc += (double)Tl * exp(d[n]) - d[n] * (double)cnt;
+    const int Tn = nlive ? nlive[(size_t)trial_of_slot[s] * q + n] : Tl;   // (a neuron without a live entry: zero counts, no term)
+    if (lane == 0) acc += (double)Tn * exp(d[n]) - d[n] * (double)cnt;
   }
   if (lane == 0) red[wave] = acc;
   __syncthreads();
@@ -631,7 +647,7 @@ static int eval_start_guarded(pgpfa_ctx* c, Chunk& ch, bool guard, EstepStats& s
   if (guard) {
     // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
     hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
-                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->obs, c->q, c->T, c->sc_alpha);
+                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->obs, c->q, c->T, c->sc_alpha, (const int*)c->nlive);
     CHK(dl_enqueue(c, ch.ftry.data(), c->sc_alpha, nb * sizeof(double)));
   }
   CHK(eval_start(c, ch));
@@ -1529,6 +1545,7 @@ int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, d
   if (!c || !y_pred || !err_sum) return fail("null argument");
   CHK(refuse_trial_lengths(c, "pgpfa_loo_predict"));
   CHK(refuse_observed(c, "pgpfa_loo_predict"));
+  CHK(refuse_observed_bins(c, "pgpfa_loo_predict"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   const int q = c->q, T = c->T;

@@ -64,6 +64,7 @@ int pgpfa_generate(pgpfa_ctx* c, unsigned long long seed, int n, const int32_t* 
   if (!c->have_params) return fail("set_params has not been called");
   CHK(refuse_trial_lengths(c, "pgpfa_generate"));
   CHK(refuse_observed(c, "pgpfa_generate"));
+  CHK(refuse_observed_bins(c, "pgpfa_generate"));
   if (c->T > 65536 || c->q > 65535) return fail("generator supports up to 65535 neurons and 65536 bins");
   HIPC(hipSetDevice(c->device));
   Trials tr;

@@ -190,11 +190,18 @@ struct PoissonArgs {
   const uint8_t* obs;
 };
 
+// Per-bin table (pgpfa_set_observed_bins), template state OBS == 2: `obs` carries bit words of 64 bins instead of bytes, [R][q + 1][ceil(T/64)] -
+// bit t & 63 of word t >> 6 in row n of trial r is set when entry (r, n, t) is live (lengths and the byte table are folded in when the words are
+// built); row q of a trial is the OR over its neurons (a 64-bin block or 16-bin tile without a live entry skips its neuron loop).  The argument
+// structs are the ones they were, so the instantiations launched without a bin table are too.
+__device__ __forceinline__ const unsigned long long* bin_words(const uint8_t* obs) { return reinterpret_cast<const unsigned long long*>(obs); }
+
 constexpr int PNC = 32;
 
 // OBS: the instantiation launched while an observation table is set (pgpfa_set_observed); without one the kernel is the code it was (the narrow widths
 // sit at the scalar-register class of their occupancy, which a run-time test of one more pointer costs them)
-template <int PMAX, bool OBS = false>
+// OBS == 2: a per-bin table (bin_words): a wave holds one neuron and the workgroup 64 bins, so one scalar word covers a wave's entries
+template <int PMAX, int OBS = 0>
 __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(PoissonArgs a) {
   constexpr int NK = (PMAX > 16) ? 2 : 1;
   __shared__ double E[PNC][64];
@@ -228,14 +235,22 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
   double facc = 0.0;
 
   // (a workgroup wholly past the trial's length skips the neuron loop: its bins keep G = 0 and W = 0, which the solvers still read)
-  for (int n0 = 0; n0 < q && blockIdx.x * 64 < Tl; n0 += PNC) {
+  // (per-bin table: the trial's rows of words for this workgroup's 64 bins; a block no neuron of the trial has a live entry in skips the loop too)
+  const unsigned long long* bw = nullptr;
+  bool some = true;
+  if constexpr (OBS == 2) {
+    bw = bin_words(a.obs) + (size_t)trial * (q + 1) * a.ntile + blockIdx.x;
+    some = bw[(size_t)q * a.ntile] != 0ull;
+  }
+  for (int n0 = 0; n0 < q && blockIdx.x * 64 < Tl && some; n0 += PNC) {
     for (int nn = ty; nn < PNC; nn += KY) {
       const int n = n0 + nn;
       double e = 0.0, r = 0.0;
       // a neuron not recorded on the trial has no rate and no count: e = r = 0 and no objective term (a wave holds one neuron - blockDim.x = 64 - so the
       // table's byte is a scalar and the test a uniform branch)
       bool seen = true;
-      if (OBS && n < q) seen = __builtin_amdgcn_readfirstlane((int)a.obs[(size_t)trial * q + __builtin_amdgcn_readfirstlane(n)]) != 0;
+      if (OBS == 1 && n < q) seen = __builtin_amdgcn_readfirstlane((int)a.obs[(size_t)trial * q + __builtin_amdgcn_readfirstlane(n)]) != 0;
+      if (OBS == 2 && n < q) seen = (bw[(size_t)__builtin_amdgcn_readfirstlane(n) * a.ntile] >> tx) & 1ull;   // (a scalar word, this lane's bit)
       if (n < q && lik && n != held_out && seen) {
         double h = a.d[n];
         if (a.off) h += a.off[(size_t)slot * a.sOff + (size_t)n * T + t];
@@ -290,7 +305,12 @@ __global__ __launch_bounds__(PMAX == 20 ? 640 : 1024) void poisson_pass_kernel(P
     }
   }
   // the rate plane of an unobserved row is 0 (written here, behind the accumulators' last use, so that the neuron loop keeps its registers)
-  if (OBS && a.lam_out && lik)
+  if (OBS == 2 && a.lam_out && valid) {
+    const unsigned long long* bz = bin_words(a.obs) + (size_t)trial * (q + 1) * a.ntile + blockIdx.x;
+    for (int n = ty; n < q; n += KY)
+      if (!((bz[(size_t)n * a.ntile] >> tx) & 1ull)) a.lam_out[(size_t)slot * a.sLam + (size_t)n * T + t] = 0.0;
+  }
+  if (OBS == 1 && a.lam_out && lik)
     for (int n = ty; n < q; n += KY)
       if (a.obs[(size_t)trial * q + n] == 0) a.lam_out[(size_t)slot * a.sLam + (size_t)n * T + t] = 0.0;
   // deterministic block reduction of the objective partial: lanes, then waves in order
@@ -334,7 +354,8 @@ inline __global__ void poisson_tables_kernel(const double* __restrict__ C, int q
 // tile, every fragment read conflict-free - ran 0.60 ms: at two tiles per wave the fragments are no longer what bounds the pass.  Dropped.)
 // grid = (ceil(T / (64 NBT)), nslots); fpart holds gridDim.x partial sums per slot.
 // OBS: the instantiation launched while an observation table is set (pgpfa_set_observed); without one the kernel is the code it was, register for register
-template <int PW, int NBT, bool OBS = false>
+// OBS == 2: a per-bin table (bin_words): one bit per (lane's neuron, lane's bin) of a 16 x 16 tile, 4 NBT bits per lane and neuron tile
+template <int PW, int NBT, int OBS = 0>
 __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, const double* __restrict__ CCu, const double* __restrict__ C16, int qpad) {
   constexpr int NP = PW * (PW + 1) / 2, NT = (NP + 15) / 16, NC = NT * 16, KS = (PW + 3) / 4;
   __shared__ double Wl[4][16 * PW * PW];
@@ -350,7 +371,8 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
   const double* X = a.X + (size_t)slot * a.sX;
   const uint8_t* Y = a.Y + (size_t)trial * q * T;
   const uint8_t* Yh = a.Yhi ? a.Yhi + (size_t)trial * q * T : nullptr;
-  const uint8_t* ob = OBS ? a.obs + (size_t)trial * q : nullptr;    // the trial's row of the observation table
+  const uint8_t* ob = OBS == 1 ? a.obs + (size_t)trial * q : nullptr;    // the trial's row of the observation table
+  const unsigned long long* bw = OBS == 2 ? bin_words(a.obs) + (size_t)trial * (q + 1) * ((T + 63) >> 6) : nullptr;   // the trial's rows of the per-bin table
 
   double xb[NBT][KS];
   int tcl[NBT];
@@ -385,6 +407,16 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
     for (int tl = 0; tl < NT; ++tl) accW[bt][tl] = mdouble4{0.0, 0.0, 0.0, 0.0};
   }
   double facc = 0.0;
+  // (per-bin table: the 16 bits of each of the wave's tiles in the OR over the trial's neurons; a tile without a live entry is skipped like one past the length)
+  unsigned anyt[NBT];
+#pragma unroll
+  for (int bt = 0; bt < NBT; ++bt) {
+    anyt[bt] = 1u;
+    if constexpr (OBS == 2) {
+      const int tb = sbase0 + 16 * bt;
+      anyt[bt] = tb < T ? (unsigned)((bw[(size_t)q * ((T + 63) >> 6) + (tb >> 6)] >> (tb & 63)) & 0xffffull) : 0u;
+    }
+  }
 
   if (sbase0 < Tl) {
     // every global load of a neuron tile (offsets, counts, table fragments) is issued up front with clamped,
@@ -400,9 +432,11 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
         const int n = nb0 + l4 + 4 * r;
         const int nc = n < q ? n : q - 1;
         dn[r] = a.d[nc];
-        if constexpr (OBS) seen &= ~((unsigned)(ob[nc] == 0) << r);   // (the byte rides with the tile's other clamped loads: once per neuron tile and lane)
+        if constexpr (OBS == 1) seen &= ~((unsigned)(ob[nc] == 0) << r);   // (the byte rides with the tile's other clamped loads: once per neuron tile and lane)
+        if constexpr (OBS == 2) seen = r == 0 ? 0u : seen;               // (per-bin table: bit r + 4 bt, this lane's neuron of register r at its bin of tile bt)
 #pragma unroll
         for (int bt = 0; bt < NBT; ++bt) {
+          if constexpr (OBS == 2) seen |= (unsigned)((bw[(size_t)nc * ((T + 63) >> 6) + (tcl[bt] >> 6)] >> (tcl[bt] & 63)) & 1ull) << (r + 4 * bt);
           dv[bt][r] = dn[r];
           if (a.off) dv[bt][r] += a.off[(size_t)slot * a.sOff + (size_t)nc * T + tcl[bt]];
           yv[bt][r] = count_at(Y, Yh, (size_t)nc * T + tcl[bt]);
@@ -423,6 +457,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
 #pragma unroll
       for (int bt = 0; bt < NBT; ++bt) {
         if (sbase0 + 16 * bt >= Tl) continue;                   // (uniform over the wave; a tile past the trial's length leaves zeros)
+        if (OBS == 2 && anyt[bt] == 0u) continue;               // (uniform too: no neuron of the trial has a live entry in this tile)
         mdouble4 h;
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = (nb0 + l4 + 4 * r < q) ? dv[bt][r] : 0.0;
@@ -432,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void poisson_mfma_kernel(PoissonArgs a, con
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = nb0 + l4 + 4 * r;
-          const bool ok = (n < q) && (sbase0 + 16 * bt + l15 < Tl) && (n != held_out) && (!OBS || ((seen >> r) & 1u));
+          const bool ok = (n < q) && (sbase0 + 16 * bt + l15 < Tl) && (n != held_out) && (!OBS || ((seen >> (OBS == 2 ? r + 4 * bt : r)) & 1u));
           const double y = ok ? (double)yv[bt][r] : 0.0;
           const double ev = ok ? exp(h[r]) : 0.0;
           e[r] = ev;
@@ -1076,17 +1111,24 @@ struct CdArgs {
 // `live` of a lane's neuron for one (trial, tile) item.  OBS - the instantiations launched while an observation table is set (pgpfa_set_observed): the
 // neuron must also be recorded on the item's trial, one byte per item behind a wave-uniform row base.  Without a table the kernels are the code they
 // were, register for register: most of them sit at the 102-SGPR ceiling, where the two scalars of a run-time test of the pointer spill into vector registers.
-template <bool OBS>
+template <int OBS>
 __device__ __forceinline__ bool cd_item_live(const CdArgs& a, size_t r, int n, bool live) {
-  if constexpr (!OBS) return live;
+  if constexpr (OBS != 1) return live;
   else return live && (a.obs + (size_t)__builtin_amdgcn_readfirstlane((int)r) * a.q)[n] != 0;
+}
+// Per-bin table (OBS == 2, bin_words): the word of the lane's neuron for the item's tile, shifted so that bit t is bin t0 + t.  Tiles of 64, 32, 16 or
+// 8 bins start at multiples of their width and never straddle a word.  (A lane past q reads row 0: it is not live.)
+template <int OBS>
+__device__ __forceinline__ unsigned long long cd_item_bits(const CdArgs& a, size_t r, int n, int t0) {
+  if constexpr (OBS != 2) return ~0ull;
+  else return bin_words(a.obs)[(r * (size_t)(a.q + 1) + (n < a.q ? n : 0)) * (size_t)((a.T + 63) >> 6) + (t0 >> 6)] >> (t0 & 63);
 }
 constexpr int CD_KY = 8;
 // waves per workgroup of mstep_cd_kernel: 8 up to 16 latents (128-register budget), 4 beyond (c, acc, u of 20+ doubles each need the 256 budget)
 template <int PW> struct CdKy { static constexpr int v = (PW <= 16) ? 8 : 4; };
 template <int PW> struct CdTile { static constexpr int TT = (PW <= 10) ? 64 : (PW <= 16) ? 32 : (PW <= 20) ? 16 : 8; };
 
-template <int PW, bool OBS = false>
+template <int PW, int OBS = 0>
 __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
   constexpr int KYW = CdKy<PW>::v;
   constexpr int TT = CdTile<PW>::TT;
@@ -1117,6 +1159,9 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
     const int t0 = (item % ntt) * TT;
     const int Tl = a.len ? a.len[r] : T;
     if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    if constexpr (OBS == 2) {                      // (every wave holds the block's 64 neurons: uniform over the workgroup too)
+      if (!__any(live && (cd_item_bits<OBS>(a, r, n, t0) & (TT == 64 ? ~0ull : ((1ull << TT) - 1ull))) != 0ull)) continue;
+    }
     const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
@@ -1138,6 +1183,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
     }
     __syncthreads();
     const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
+    const unsigned long long lw = cd_item_bits<OBS>(a, r, n, t0);   // (per-bin table: this lane's bits of the tile)
     for (int t = ty; t < tn; t += KYW) {
       // u = V_t c from the lower triangle only (V_t is symmetric): p(p+1)/2 LDS reads instead of p^2
       double u[PW];
@@ -1162,7 +1208,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
       const double rs = y - yh;
-      if (on) {
+      if (OBS == 2 ? (on && ((lw >> t) & 1ull)) : on) {   // (per-bin table: this bin of this neuron is live)
         cost += y * hh - yh;
         dd += rs;
 #pragma unroll
@@ -1199,7 +1245,7 @@ __global__ __launch_bounds__(64 * CdKy<PW>::v) void mstep_cd_kernel(CdArgs a) {
 // part layout per block: [NH][q], NH = 1 + (p+1) + (p+1)(p+2)/2 : cost | grad (c.., d) | packed lower Hessian
 // --------------------------------------------------------------------------------------------------
 constexpr int CDH_KY = 4;      // 4 waves per block: the whole 512-register file per lane for the (p+1)(p+2)/2 Hessian accumulators
-template <int PW, bool OBS = false>
+template <int PW, int OBS = 0>
 __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
   constexpr int TT = CdTile<PW>::TT;
   constexpr int YS = TT + 4;
@@ -1232,6 +1278,9 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
     const int t0 = (item % ntt) * TT;
     const int Tl = a.len ? a.len[r] : T;
     if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    if constexpr (OBS == 2) {                      // (every wave holds the block's 64 neurons: uniform over the workgroup too)
+      if (!__any(live && (cd_item_bits<OBS>(a, r, n, t0) & (TT == 64 ? ~0ull : ((1ull << TT) - 1ull))) != 0ull)) continue;
+    }
     const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
@@ -1253,6 +1302,7 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
     }
     __syncthreads();
     const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
+    const unsigned long long lw = cd_item_bits<OBS>(a, r, n, t0);   // (per-bin table: this lane's bits of the tile)
     for (int t = ty; t < tn; t += CDH_KY) {
       double w[D];
       double hh = dn, rho = 0.0;
@@ -1279,7 +1329,7 @@ __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_kernel(CdArgs a) {
       w[PW] = 1.0;
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
-      if (on) {
+      if (OBS == 2 ? (on && ((lw >> t) & 1ull)) : on) {   // (per-bin table: this bin of this neuron is live)
         cost += y * hh - yh;
 #pragma unroll
         for (int k = 0; k < PW; ++k) gacc[k] -= y * Mt[k][t] - yh * w[k];
@@ -1349,7 +1399,7 @@ constexpr int cd_group_entries(int D, int NG, int G) {
   return n;
 }
 
-template <int PW, int NG, int G, bool OBS>
+template <int PW, int NG, int G, int OBS>
 __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[PW * PW], double (*Mt)[CdTile<PW>::TT], uint16_t* Yt,
                                                   double (*red)[64]) {
   constexpr int TT = CdTile<PW>::TT;
@@ -1380,6 +1430,9 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
     const int t0 = (item % ntt) * TT;
     const int Tl = a.len ? a.len[r] : T;
     if (t0 >= Tl) continue;                        // (uniform over the workgroup)
+    if constexpr (OBS == 2) {                      // (every wave holds the block's 64 neurons: uniform over the workgroup too)
+      if (!__any(live && (cd_item_bits<OBS>(a, r, n, t0) & (TT == 64 ? ~0ull : ((1ull << TT) - 1ull))) != 0ull)) continue;
+    }
     const int tn = (Tl - t0 < TT) ? Tl - t0 : TT;
     const double* mean = a.mean + r * p * T;
     const double* vsm = a.vsm + (r * T + t0) * p * p;
@@ -1401,6 +1454,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
     }
     __syncthreads();
     const bool on = cd_item_live<OBS>(a, r, n, live);   // this lane's neuron was recorded on the item's trial (no table: live)
+    const unsigned long long lw = cd_item_bits<OBS>(a, r, n, t0);   // (per-bin table: this lane's bits of the tile)
     for (int t = ty; t < tn; t += CDH_KY) {
       double w[D];
       double hh = dn, rho = 0.0;
@@ -1426,7 +1480,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
       w[PW] = 1.0;
       const double yh = exp(hh + 0.5 * rho);
       const double y = (double)Yt[lane * YS + t];
-      if (on) {
+      if (OBS == 2 ? (on && ((lw >> t) & 1ull)) : on) {   // (per-bin table: this bin of this neuron is live)
         if (G == 0) {
           cost += y * hh - yh;
 #pragma unroll
@@ -1488,7 +1542,7 @@ __device__ __forceinline__ void cd_hess_rows_body(const CdArgs& a, double (*Vt)[
   }
 }
 
-template <int PW, int NG, bool OBS = false>
+template <int PW, int NG, int OBS = 0>
 __global__ __launch_bounds__(64 * CDH_KY) void mstep_cd_hess_rows_kernel(CdArgs a) {
   constexpr int TT = CdTile<PW>::TT;
   __shared__ __attribute__((aligned(16))) double Vt[TT][PW * PW];

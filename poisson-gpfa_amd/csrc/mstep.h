@@ -228,7 +228,7 @@ struct CdK {
 };
 
 // OBS: the instantiation launched while an observation table is set (cd_item_live, model.h)
-template <int PW, bool OBS = false>
+template <int PW, int OBS = 0>
 __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_per_group) {
   using M = CdM<PW>;
   using K = CdK<PW>;
@@ -355,7 +355,11 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
     if (more && !(a.dbg & 8)) prefetch(c_tr, c_ti);     // global loads in flight while this stage is multiplied
     const double* st = lds + cur * M::LDS_DOUBLES;
     const bool seen = cd_item_live<OBS>(a, (size_t)tr_item, nc, live);   // this lane's neuron was recorded on the item's trial (no table: live)
-    if (active_wave) {
+    // (per-bin table: the bits of this lane's neuron over the item's tile; a wave whose 16 neurons have no live entry in it skips the products)
+    const unsigned long long lw = cd_item_bits<OBS>(a, (size_t)tr_item, nc, t0);
+    bool some = true;
+    if constexpr (OBS == 2) some = t0 < T && __any(live && (lw & (BT == 64 ? ~0ull : ((1ull << BT) - 1ull))) != 0ull);
+    if (active_wave && some) {
 #pragma unroll
       for (int sub = 0; sub < BT / 16; ++sub) {
         if (sub * 16 >= tn) break;
@@ -376,7 +380,7 @@ __global__ __launch_bounds__(512) void mstep_cd_mfma_kernel(CdArgs a, int tiles_
           double hv = h[r] + h2[r];
 #pragma unroll
           for (int i = 0; i < KV; ++i) hv += bin[4 * KSM + i] * thv[i];
-          const double e = (seen && sub * 16 + 4 * r + l4 < tn) ? ((a.dbg & 1) ? 1.0 + 1e-3 * hv : exp(hv)) : 0.0;
+          const double e = (seen && sub * 16 + 4 * r + l4 < tn && (OBS != 2 || ((lw >> (sub * 16 + 4 * r + l4)) & 1ull))) ? ((a.dbg & 1) ? 1.0 + 1e-3 * hv : exp(hv)) : 0.0;
           yh[r] = e;
 #pragma unroll
           for (int i = 0; i < NV; ++i) accv[i] += bin[16 * NTM + i] * e;
@@ -504,7 +508,7 @@ __device__ __forceinline__ void cdh_swap32(double& a, double& b) {
   a = __hiloint2double((int)r1[0], (int)r0[0]); b = __hiloint2double((int)r1[1], (int)r0[1]);
 }
 
-template <int PW, bool OBS = false>
+template <int PW, int OBS = 0>
 __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs a, int tiles_per_group) {
   using M = CdM<PW>;
   using H = CdH<PW>;
@@ -620,12 +624,16 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
     const int Tl = a.len ? a.len[a.trials[c_tr]] : T;
     const int tn = (Tl - t0 < BT) ? Tl - t0 : BT;      // bins of this item inside the trial's length (<= 0: the item does nothing)
     const bool seen = cd_item_live<OBS>(a, (size_t)(OBS ? a.trials[c_tr] : 0), nc, live);   // this lane's neuron was recorded on the item's trial (no table: live)
+    // (per-bin table: the bits of this lane's neuron over the item's tile; a wave whose 16 neurons have no live entry in it skips the products)
+    const unsigned long long lw = cd_item_bits<OBS>(a, (size_t)(OBS ? a.trials[c_tr] : 0), nc, t0);
+    bool some = true;
+    if constexpr (OBS == 2) some = t0 < T && __any(live && (lw & (BT == 64 ? ~0ull : ((1ull << BT) - 1ull))) != 0ull);
     const bool more = item + (int)gridDim.x < nitems;
     c_tr += step_tr; c_ti += step_ti;
     if (c_ti >= ntt) { c_ti -= ntt; c_tr += 1; }
     if (more) prefetch(c_tr, c_ti);
     const double* st = lds + cur * H::LDS_DOUBLES;
-    if (active_wave) {
+    if (active_wave && some) {
       for (int tb0 = 0; tb0 < tn; tb0 += 4) {
         // stage 1: h[b][r] = (V_t c_n)_{4 r + l4} for the bins b = tb0 .. tb0 + 3 (rows past tn are zero-filled stage rows: yhat is masked below)
         mdouble4 h[4];
@@ -654,7 +662,7 @@ __global__ __launch_bounds__(64 * CDH_NW) void mstep_cd_hess_mfma_kernel(CdArgs 
         cdh_swap16(sb[2], sb[3]);
         double t01 = sb[0] + sb[1], t23 = sb[2] + sb[3];
         cdh_swap32(t01, t23);
-        const bool on = seen && tb0 + l4 < tn;
+        const bool on = seen && tb0 + l4 < tn && (OBS != 2 || ((lw >> (tb0 + l4)) & 1ull));
         const double yh = exp(on ? dn + (t01 + t23) : -1000.0);      // (exp(-1000) = 0: masked bins and neurons drop out of every sum)
         const double sq = sqrt(yh);
         double sqb[4];

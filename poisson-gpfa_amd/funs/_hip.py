@@ -30,6 +30,7 @@ _SIGNATURES = {
     'pgpfa_upload_counts_u16': [ct.c_void_p, ct.POINTER(ct.c_uint16)],
     'pgpfa_set_trial_lengths': [ct.c_void_p, c_int32_p],
     'pgpfa_set_observed': [ct.c_void_p, c_uint8_p],
+    'pgpfa_set_observed_bins': [ct.c_void_p, c_uint8_p],
     'pgpfa_get_counts_u16': [ct.c_void_p, ct.c_int, c_int32_p, ct.POINTER(ct.c_uint16)],
     'pgpfa_set_params': [ct.c_void_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_get_gram': [ct.c_void_p, c_double_p],
@@ -226,6 +227,17 @@ class Context:
         if ob.shape != (self.R, self.q):
             raise ValueError('observation table must have shape (R,q)=%s, got %s' % ((self.R, self.q), ob.shape))
         check(self.lib.pgpfa_set_observed(self.h, ob.ctypes.data_as(c_uint8_p)))
+
+    def set_observed_bins(self, live):
+        """Per-bin table (R, q, T): non-zero = entry (trial, neuron, bin) was recorded; None drops the table.  Composes with the trial lengths and the
+        observation table by AND; entries that are not live carry no likelihood term (pgpfa_set_observed_bins); their resident counts must be zero."""
+        if live is None:
+            check(self.lib.pgpfa_set_observed_bins(self.h, None))
+            return
+        lv = np.ascontiguousarray(np.asarray(live) != 0, dtype=np.uint8)
+        if lv.shape != (self.R, self.q, self.T):
+            raise ValueError('per-bin table must have shape (R,q,T)=%s, got %s' % ((self.R, self.q, self.T), lv.shape))
+        check(self.lib.pgpfa_set_observed_bins(self.h, lv.ctypes.data_as(c_uint8_p)))
 
     def set_params(self, C, d, tau):
         C, d, tau = as_f64(C), as_f64(d).reshape(-1), as_f64(tau).reshape(-1)

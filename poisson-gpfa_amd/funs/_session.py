@@ -380,6 +380,7 @@ class Session:
         self.observed = None
         if observed is not None and not np.all(observed):
             self.observed = check_observed(observed, R, q)
+        self.observed_bins = None                            # per-bin table (R, q, T) of booleans: set_observed_bins
         self.ctx = _hip.Context(q, p, T, R, bin_ms, device=WORLD.device())
         self.ctx.upload_counts(Y)
         if self.lengths is not None:
@@ -415,6 +416,26 @@ class Session:
 
     def set_params(self, params):
         self.ctx.set_params(params['C'], params['d'], params['tau'])
+
+    def set_observed_bins(self, table):
+        """Give the session a per-bin table (R, q, T) of booleans, True = recorded, on top of its lengths and observation table (None drops it).  A
+        table that marks every entry inside those two as recorded is dropped here: no table is set and the path is that of the other two alone.
+        Resident posteriors are superseded, as by any change of the data.  ValueError for a wrong shape or a trial / neuron left without a live
+        entry, before anything reaches the device."""
+        if table is not None:
+            table = compose_observed_bins(table, self.lengths, self.observed, self.R, self.q, self.T)
+        self._install_observed_bins(table)
+
+    def _install_observed_bins(self, table):
+        """set_observed_bins for a table that compose_observed_bins has returned already (session_for checks it before anything is uploaded)."""
+        if table is None and self.observed_bins is None:
+            return
+        if table is not None and self.comm_ready:
+            # (the moments all-reduce s and S over the ranks, the live and co-live counts would have to follow)
+            raise NotImplementedError('a per-bin observation table is not supported on a sharded session yet')
+        self.ctx.set_observed_bins(table)
+        self.observed_bins = table
+        self.mark_written(np.arange(self.R))
 
     def cut(self, key, trial, arr):
         """The padded device entry `arr` of `trial` restricted to the trial's own T_r bins: post_mean (p, T_r), post_vsm (T_r, p, p),
@@ -455,7 +476,7 @@ class Session:
     def live_mask(self, trials):
         """Boolean (n, q*T) array over the padded dual variables of the listed trials: True where entry (neuron, bin) has a likelihood term - the bin
         lies inside the trial's own T_r bins and the neuron was recorded on the trial.  None when no table is set (every entry is live)."""
-        if self.lengths is None and getattr(self, 'observed', None) is None:
+        if self.lengths is None and getattr(self, 'observed', None) is None and getattr(self, 'observed_bins', None) is None:
             return None
         trials = np.asarray(trials, dtype=np.int64)
         live = np.ones((len(trials), self.q, self.T), dtype=bool)
@@ -463,7 +484,14 @@ class Session:
             live &= (np.arange(self.T)[None, :] < self.lengths[trials][:, None])[:, None, :]
         if self.observed is not None:
             live &= self.observed[trials][:, :, None]
+        if getattr(self, 'observed_bins', None) is not None:
+            live &= self.observed_bins[trials]
         return live.reshape(len(trials), -1)
+
+    def live_entries(self):
+        """Boolean (R, q, T) array of the entries that carry a likelihood term: lengths, observation table and per-bin table by AND."""
+        live = self.live_mask(np.arange(self.R))
+        return np.ones((self.R, self.q, self.T), dtype=bool) if live is None else live.reshape(self.R, self.q, self.T)
 
     def refuse_unequal(self, what):
         """Entry points that do not know per-trial lengths must not run on padded data as if the padding were observed."""
@@ -476,6 +504,12 @@ class Session:
         if getattr(self, 'observed', None) is not None:
             raise NotImplementedError('%s does not support unobserved neurons yet (this experiment has %d unobserved (trial, neuron) pairs); '
                                       'only the Laplace EM path does' % (what, int((~self.observed).sum())))
+
+    def refuse_masked_bins(self, what):
+        """Entry points that do not know the per-bin table must not treat the zero-filled entries it marks as not recorded as counts of zero."""
+        if getattr(self, 'observed_bins', None) is not None:
+            raise NotImplementedError('%s does not support a per-bin observation table yet (this experiment has %d entries marked as not recorded by '
+                                      "'observedBins'); only the Laplace EM path does" % (what, int((~self.observed_bins).sum())))
 
     def mark_dual_written(self, trial_idx):
         """A variational E-step has just overwritten the resident dual variables of these trials."""
@@ -514,6 +548,53 @@ def check_observed(observed, R, q):
     return np.ascontiguousarray(ob)
 
 
+def compose_observed_bins(table, lengths, observed, R, q, T):
+    """The per-bin table as a contiguous boolean (R, q, T) array, or None when it marks every entry inside the lengths (may be None) and the
+    observation table (may be None) as recorded.  ValueError for a wrong shape, and for a trial or a neuron that the three tables together leave
+    without a live entry (nothing has been uploaded yet when this runs)."""
+    ob = np.asarray(table)
+    if ob.shape != (R, q, T):
+        raise ValueError('per-bin table must have shape (trials, ydim, T) = (%d, %d, %d), got %s' % (R, q, T, ob.shape))
+    ob = ob != 0
+    base = np.ones((R, q, T), dtype=bool)
+    if lengths is not None:
+        base &= (np.arange(T)[None, :] < np.asarray(lengths).reshape(-1)[:, None])[:, None, :]
+    if observed is not None:
+        base &= np.asarray(observed, dtype=bool)[:, :, None]
+    if np.all(ob[base]):
+        return None
+    live = ob & base
+    empty = np.flatnonzero(~live.any(axis=(1, 2)))
+    if empty.size:
+        raise ValueError('trial %d has no live entry: every (neuron, bin) of it is marked as not recorded' % int(empty[0]))
+    never = np.flatnonzero(~live.any(axis=(0, 2)))
+    if never.size:
+        raise ValueError('neuron %d has no live entry on any trial' % int(never[0]))
+    return np.ascontiguousarray(ob)
+
+
+def _stack_observed_bins(experiment):
+    """Per-bin table (R, ydim, T) of experiment.data, booleans, T the longest trial: trial r holds data[r]['observedBins'] (ydim, T_r), all True for
+    a trial without the key and False behind a shorter trial's own bins; None when no trial carries the key.  ValueError for a wrong shape."""
+    rows = [tr.get('observedBins') if hasattr(tr, 'get') else None for tr in experiment.data]
+    if all(o is None for o in rows):
+        return None
+    shapes = [np.asarray(tr['Y']).shape for tr in experiment.data]
+    q, T = shapes[0][0], max(sh[1] for sh in shapes if len(sh) == 2)
+    table = np.zeros((len(rows), q, T), dtype=bool)
+    for r, o in enumerate(rows):
+        if len(shapes[r]) != 2:
+            continue                                     # (reported by _stack_counts)
+        if o is None:
+            table[r, :, :shapes[r][1]] = True
+            continue
+        o = np.asarray(o)
+        if o.shape != tuple(shapes[r]):
+            raise ValueError("trial %d: 'observedBins' must have the shape of 'Y', (ydim, T) = %s, got %s" % (r, tuple(shapes[r]), o.shape))
+        table[r, :, :shapes[r][1]] = o != 0
+    return table
+
+
 def _stack_observed(experiment):
     """Observation table (R, ydim) of experiment.data, booleans: row r is data[r]['observed'] (all True for a trial without the key), or None
     when no trial carries the key.  Raises ValueError for a wrong shape, a trial without an observed neuron or a neuron never observed."""
@@ -533,7 +614,14 @@ def _stack_observed(experiment):
 
 
 def _observed_filled(tr, y):
-    """y with the rows that data[r]['observed'] marks as not recorded set to zero (a copy; NaN is accepted in those rows only)."""
+    """y with the rows that data[r]['observed'] marks as not recorded, and the entries that data[r]['observedBins'] marks so, set to zero (a copy; NaN
+    is accepted there only)."""
+    b = tr.get('observedBins') if hasattr(tr, 'get') else None
+    if b is not None:
+        b = np.asarray(b)
+        if b.shape == y.shape and not np.all(b != 0):    # (a wrong shape is reported by _stack_observed_bins)
+            y = np.array(y, copy=True)
+            y[b == 0] = 0
     o = tr.get('observed') if hasattr(tr, 'get') else None
     if o is None:
         return y
@@ -591,8 +679,12 @@ def session_for(experiment, p):
     sess = per_exp.get(p)
     if sess is None or sess.R != n_trials:
         observed = _stack_observed(experiment)            # (before anything is uploaded: a bad table raises ValueError here)
+        bins = _stack_observed_bins(experiment)
         Y, lengths = _stack_counts(experiment)
+        if bins is not None:                              # (still before anything is uploaded)
+            bins = compose_observed_bins(bins, lengths if np.any(lengths != Y.shape[2]) else None, observed, Y.shape[0], Y.shape[1], Y.shape[2])
         sess = Session(Y, p, float(experiment.binSize), lengths, observed)
+        sess._install_observed_bins(bins)
         per_exp[p] = sess
     return sess, np.arange(n_trials, dtype=np.int32)
 

@@ -93,9 +93,11 @@ def laplace(experiment, params, prevOptimRes=None, returnOptimRes=True, verbose=
     xdim*T_r values, and bins past T_r carry no likelihood term on the device.
     Neurons may be unobserved on some trials (experiment.data[r]['observed'], an optional boolean (ydim,)): trial r's posterior is then that of
     the model with only its observed rows of C, d and Y; the values of 'Y' in unobserved rows are ignored (NaN is accepted there).
+    Single entries may be missing (experiment.data[r]['observedBins'], an optional boolean (ydim, T_r), True = recorded; ANDed with the other
+    two): an entry that is not recorded carries no likelihood term, its value in 'Y' is ignored (NaN is accepted there).
     """
     sess, trial_idx = _prepare(experiment, params)
-    sess.ctx.set_option('laplace_f32', int(LAPLACE_F32))       # (True is 1; LAPLACE_F32 is defined next to DUAL_F32 below)
+    sess.ctx.set_option('laplace_f32', int(LAPLACE_F32))      # (True is 1; LAPLACE_F32 is defined next to DUAL_F32 below)
     evidence = bool(LAPLACE_EVIDENCE)
     sess.ctx.set_option('laplace_evidence', int(evidence))
     n_all = len(trial_idx)
@@ -507,6 +509,7 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     import scipy.optimize as op
     sess, trial_idx = _prepare(experiment, params)
     masked = bool(DUAL_MASKED)
+    sess.refuse_masked_bins('dualVariational')              # (a per-bin table is outside DUAL_MASKED too)
     if not masked:
         sess.refuse_unequal('dualVariational')
         sess.refuse_unobserved('dualVariational')

@@ -19,6 +19,7 @@ def PosteriorMCMC(experiment, params, maxSampleIter, trial):
     sess, trial_idx = inference._prepare(experiment, params)
     sess.refuse_unequal('PosteriorMCMC')
     sess.refuse_unobserved('PosteriorMCMC')
+    sess.refuse_masked_bins('PosteriorMCMC')
     tr = trial_idx[np.asarray([trial])]
     # chol(K_big) is block diagonal: one T x T Cholesky factor per latent (mcmc.py:29)
     K = sess.ctx.gram()
@@ -82,6 +83,7 @@ def PosteriorMCMC_batch(experiment, params, maxSampleIter, trials, seeds):
     sess, trial_idx = inference._prepare(experiment, params)
     sess.refuse_unequal('PosteriorMCMC_batch')
     sess.refuse_unobserved('PosteriorMCMC_batch')
+    sess.refuse_masked_bins('PosteriorMCMC_batch')
     dev = trial_idx[trials]
     K = sess.ctx.gram()
     chol = [np.linalg.cholesky(K[k]) for k in range(xdim)]

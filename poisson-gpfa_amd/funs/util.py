@@ -97,6 +97,7 @@ def leaveOneOutPrediction(params, experiment):
     sess, trial_idx = _session.session_for(experiment, xdim)
     sess.refuse_unequal('leaveOneOutPrediction')
     sess.refuse_unobserved('leaveOneOutPrediction')
+    sess.refuse_masked_bins('leaveOneOutPrediction')
     lo, hi = (0, len(trial_idx)) if getattr(experiment, '_pgpfa_local_shard', False) else sess.local_slice(len(trial_idx))
     sess.set_params(params)
     y_loc, err_loc = sess.ctx.loo_predict(trial_idx[lo:hi])
@@ -169,7 +170,9 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     length each is cut to its T_r bins - a list of (ydim, T_r) arrays - unless forecast=True, which keeps all T bins: behind T_r the
     posterior is the GP's prediction from the trial's own bins.  With `conditions` the dict also holds 'condition_mean' [G][ydim][T] in
     spikes per second (the mean over the condition's trials that have the bin; NaN where none has), 'condition_count' [G][T] and
-    'condition_labels' [G]; with want=() only these come back and no per-trial plane leaves the device."""
+    'condition_labels' [G]; with want=() only these come back and no per-trial plane leaves the device.
+    Under a per-bin table (experiment.data[r]['observedBins']) the planes and the condition averages cover every entry - an entry that was not
+    recorded gets the model's prediction - and 'ell' raises ValueError: the resident counts at such entries are placeholders."""
     from . import _session, inference
     want = tuple(want)
     unknown = [k for k in want if k not in _RATE_KEYS]
@@ -178,6 +181,9 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     z = _band_z(level)
     xdim = np.shape(params['C'])[1]
     sess, trial_idx = _session.session_for(experiment, xdim)
+    if 'ell' in want and getattr(sess, 'observed_bins', None) is not None:
+        raise ValueError("want: 'ell' is not available under a per-bin table ('observedBins'): the resident counts at entries that were not "
+                         'recorded are placeholders')
     if sess.comm_ready:
         raise NotImplementedError('posteriorRates does not support sharded sessions yet: every rank holds the posterior of its own trials only')
     pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
@@ -310,11 +316,17 @@ def coSmoothing(params, experiment, heldOut, trials=None):
     if pos.size == 0:
         raise ValueError('empty trial list')
     table = _session._stack_observed(experiment)
+    own_bins = _session._stack_observed_bins(experiment)    # (per-bin table of the experiment, or None: ANDed with the mask of the held-out neurons)
     Y, lengths = _session._stack_counts(experiment)
     if Y.shape[1] != ydim:
         raise ValueError("params['C'] has %d rows but the experiment has %d neurons" % (ydim, Y.shape[1]))
     own = np.ones((n_all, ydim), dtype=bool) if table is None else table
     n = pos.size
+    bins_t = None
+    if own_bins is not None:
+        bins_t = np.ones((n + 1,) + own_bins.shape[1:], dtype=bool)
+        bins_t[:n] = own_bins[pos]
+        bins_t[:n, held] = True                          # (whole rows are masked by the observation table below; their bits do not matter)
     masked = np.ones((n + 1, ydim), dtype=bool)
     masked[:n] = own[pos]
     masked[:n, held] = False
@@ -325,8 +337,11 @@ def coSmoothing(params, experiment, heldOut, trials=None):
     Yt[:n] = Y[pos]
     Yt[:n, held] = 0
     len_t = np.concatenate([np.asarray(lengths, dtype=np.int32)[pos], [Y.shape[2]]]).astype(np.int32)
+    if bins_t is not None:                               # (checked before the context exists; None: every entry inside the other two tables is live)
+        bins_t = _session.compose_observed_bins(bins_t, len_t, masked, n + 1, ydim, Y.shape[2])
     sess = _session.Session(Yt, xdim, float(experiment.binSize), len_t, masked)
     try:
+        sess._install_observed_bins(bins_t)
         sess.set_params({'C': C, 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
         idx = np.arange(n, dtype=np.int32)
         _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
@@ -338,33 +353,154 @@ def coSmoothing(params, experiment, heldOut, trials=None):
         sess.ctx.close()
     per_s = 1000.0 / float(experiment.binSize)
     rates = [lam[i, :, :int(len_t[i])] * per_s for i in range(n)]
-    # the score, on the host: the caller's true counts at the pairs the experiment observed
-    ll = np.zeros(held.size)
-    spikes = np.zeros(held.size)
-    tot_y = np.zeros(held.size)
-    tot_bins = np.zeros(held.size)
-    truth = []
-    for i, r in enumerate(pos):
-        y = np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64)[held]
-        scored = own[int(r)][held]
-        truth.append((y, scored))
-        tot_y += np.where(scored, np.where(scored[:, None], y, 0.0).sum(axis=1), 0.0)
-        tot_bins += scored * y.shape[1]
+    # the score, on the host: the caller's true counts at the entries the experiment itself recorded
+    lam = [lam[i, :, :int(len_t[i])] for i in range(n)]
+    scored = [np.broadcast_to(own[int(r)][held][:, None], lm.shape) if own_bins is None else own[int(r)][held][:, None] & own_bins[int(r)][held][:, :lm.shape[1]]
+              for r, lm in zip(pos, lam)]
+    truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64)[held] for r in pos]
+    total, per_neuron, _ = _score_entries(truth, lam, scored)
+    return {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+
+
+def _score_entries(truth, lam, scored):
+    """Bits per spike over single entries: truth, lam (predicted counts per bin) and scored (booleans) are lists of (rows, T_r) arrays, one per
+    trial.  Per row n: sum over its scored entries of [y log lam - lam] - [y log lbar_n - lbar_n], lbar_n the mean count of row n over its scored
+    entries - the null model of coSmoothing, per entry.  Returns (total, per row (NaN for a row without a scored spike), entries scored)."""
+    rows = truth[0].shape[0]
+    tot_y, tot_n = np.zeros(rows), np.zeros(rows)
+    for y, sc in zip(truth, scored):
+        tot_y += np.where(sc, y, 0.0).sum(axis=1)
+        tot_n += sc.sum(axis=1)
     with np.errstate(invalid='ignore', divide='ignore'):
-        lbar = np.where(tot_bins > 0, tot_y / tot_bins, 0.0)
-    for i, (y, scored) in enumerate(truth):
-        L = y.shape[1]
-        y = np.where(scored[:, None], y, 0.0)
-        lm = lam[i, :, :L]
+        lbar = np.where(tot_n > 0, tot_y / tot_n, 0.0)
+    ll, spikes = np.zeros(rows), np.zeros(rows)
+    for y, lm, sc in zip(truth, lam, scored):
+        y = np.where(sc, y, 0.0)                         # (NaN in the caller's counts is accepted where nothing is scored)
         with np.errstate(invalid='ignore', divide='ignore'):
             null = np.where(y > 0, y * np.log(lbar)[:, None], 0.0) - lbar[:, None]
         model = y * np.log(lm) - lm
-        ll += np.where(scored, (model - null).sum(axis=1), 0.0)
+        ll += np.where(sc, model - null, 0.0).sum(axis=1)
         spikes += y.sum(axis=1)
     with np.errstate(invalid='ignore', divide='ignore'):
-        per_neuron = np.where(spikes > 0, ll / (np.log(2.0) * spikes), np.nan)
+        per_row = np.where(spikes > 0, ll / (np.log(2.0) * spikes), np.nan)
         total = float(ll.sum() / (np.log(2.0) * spikes.sum())) if spikes.sum() > 0 else float('nan')
-    return {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+    return total, per_row, int(tot_n.sum())
+
+
+def binHoldout(params, experiment, heldOut, trials=None):
+    """Predict single (neuron, bin) entries of the listed trials from everything else and score the prediction: the per-entry sibling of
+    coSmoothing ("speckled" hold-out).  heldOut: one boolean (ydim, T_r) array per listed trial, True = hide and score.  The hidden entries are
+    marked as not recorded (on top of the experiment's own lengths, 'observed' and 'observedBins'), ONE Laplace E-step gives the posterior of
+    the latents without them, and an entry's predicted rate is the posterior mean rate exp(eta + var / 2) that posteriorRates documents.
+
+    Runs on a context of its own that holds the listed trials and one silent, fully observed trial that no E-step touches (coSmoothing), so the
+    experiment, its session, the session's tables and its resident posterior stay as they were.
+
+    trials: positions in experiment.data (None: all).  Returns a dict: 'rate' - one (ydim, T_r) array per listed trial, spikes per second,
+    every entry; 'bitsPerSpike' and 'bitsPerSpikePerNeuron' [ydim] as coSmoothing defines them, over the entries that are held out AND were
+    live in the experiment (the null model is each neuron's mean count over its scored entries); 'nScored' - how many those are."""
+    from . import _session
+    C = np.asarray(params['C'], dtype=np.float64)
+    ydim, xdim = C.shape
+    if WORLD_sharded():
+        raise NotImplementedError('binHoldout does not support sharded sessions yet')
+    n_all = len(experiment.data)
+    pos = np.arange(n_all) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    if pos.size == 0:
+        raise ValueError('empty trial list')
+    if len(heldOut) != pos.size:
+        raise ValueError('heldOut: one boolean (ydim, T_r) array per listed trial expected (%d trials, %d arrays)' % (pos.size, len(heldOut)))
+    table = _session._stack_observed(experiment)
+    own_bins = _session._stack_observed_bins(experiment)
+    Y, lengths = _session._stack_counts(experiment)
+    if Y.shape[1] != ydim:
+        raise ValueError("params['C'] has %d rows but the experiment has %d neurons" % (ydim, Y.shape[1]))
+    T = Y.shape[2]
+    lengths = np.asarray(lengths, dtype=np.int32)
+    n = pos.size
+    # the entries the experiment itself has a likelihood term for
+    own_live = (np.arange(T)[None, None, :] < lengths[pos][:, None, None]) & np.ones((n, ydim, T), dtype=bool)
+    if table is not None:
+        own_live &= table[pos][:, :, None]
+    if own_bins is not None:
+        own_live &= own_bins[pos]
+    hide = np.zeros((n, ydim, T), dtype=bool)
+    for i, h in enumerate(heldOut):
+        h = np.asarray(h)
+        L = int(lengths[pos[i]])
+        if h.shape != (ydim, L):
+            raise ValueError('heldOut[%d] must have shape (ydim, T_r) = (%d, %d), got %s' % (i, ydim, L, h.shape))
+        hide[i, :, :L] = h != 0
+    bins_t = np.ones((n + 1, ydim, T), dtype=bool)
+    bins_t[:n] = own_live & ~hide
+    empty = np.flatnonzero(~bins_t[:n].any(axis=(1, 2)))
+    if empty.size:
+        raise ValueError('trial %d has no live entry left once the held-out ones are hidden' % int(pos[empty[0]]))
+    masked = np.ones((n + 1, ydim), dtype=bool)
+    if table is not None:
+        masked[:n] = table[pos]
+    Yt = np.zeros((n + 1,) + Y.shape[1:], dtype=Y.dtype)
+    Yt[:n] = np.where(bins_t[:n], Y[pos], 0)
+    len_t = np.concatenate([lengths[pos], [T]]).astype(np.int32)
+    live_t = _session.compose_observed_bins(bins_t, len_t, masked, n + 1, ydim, T)      # (checked before the context exists; None: nothing is hidden)
+    sess = _session.Session(Yt, xdim, float(experiment.binSize), len_t, masked)
+    try:
+        sess._install_observed_bins(live_t)
+        sess.set_params({'C': C, 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+        idx = np.arange(n, dtype=np.int32)
+        _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
+        if np.any(status > 1):
+            raise _hip.HipBackendError('binHoldout: the Laplace mode search failed for %d trial(s)' % int(np.sum(status > 1)))
+        dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
+        lam = np.exp(dev['eta'] + 0.5 * dev['var'])                             # predicted counts per bin [n][ydim][T]
+    finally:
+        sess.ctx.close()
+    per_s = 1000.0 / float(experiment.binSize)
+    lam = [lam[i, :, :int(len_t[i])] for i in range(n)]
+    scored = [(hide[i] & own_live[i])[:, :int(len_t[i])] for i in range(n)]
+    truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64) for r in pos]
+    total, per_neuron, n_scored = _score_entries(truth, lam, scored)
+    return {'rate': [lm * per_s for lm in lam], 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'nScored': n_scored}
+
+
+def speckledHoldout(experiment, holdoutFraction=0.1, seed=0):
+    """A seeded random subset of the experiment's live entries: one boolean (ydim, T_r) array per trial, True = held out.  Every entry is drawn
+    with probability holdoutFraction from numpy.random.default_rng(seed), trial after trial; entries the experiment did not record are never
+    chosen.  The subset depends on the experiment and the seed only - not on a latent width."""
+    from . import _session
+    if not 0.0 < float(holdoutFraction) < 1.0:
+        raise ValueError('holdoutFraction must lie strictly between 0 and 1')
+    rng = np.random.default_rng(seed)
+    table = _session._stack_observed(experiment)
+    own_bins = _session._stack_observed_bins(experiment)
+    out = []
+    for r, tr in enumerate(experiment.data):
+        shape = np.asarray(tr['Y']).shape
+        live = np.ones(shape, dtype=bool)
+        if table is not None:
+            live &= table[r][:, None]
+        if own_bins is not None:
+            live &= own_bins[r][:, :shape[1]]
+        out.append((rng.random(shape) < float(holdoutFraction)) & live)
+    return out
+
+
+def _with_hidden_entries(experiment, heldOut):
+    """A shallow copy of the experiment whose trials carry 'observedBins' = their own table AND NOT heldOut (a data set of its own on the device)."""
+    from . import _session
+    own_bins = _session._stack_observed_bins(experiment)
+    hidden = copy.copy(experiment)
+    hidden.__dict__.pop('_pgpfa_parent', None)
+    hidden.__dict__.pop('batchTrIdx', None)
+    hidden.data = []
+    for r, (tr, h) in enumerate(zip(experiment.data, heldOut)):
+        tr = dict(tr)
+        keep = ~np.asarray(h, dtype=bool)
+        if own_bins is not None:
+            keep &= own_bins[r][:, :keep.shape[1]]
+        tr['observedBins'] = keep
+        hidden.data.append(tr)
+    return hidden
 
 
 def WORLD_sharded():
@@ -407,18 +543,27 @@ class crossValidation:
     prediction error on the test split; optimXdim is the arg-min.  learningMethod: 'batch', 'diag', 'hess' or 'grad'.
     score='evidence' (an addition; Laplace only) scores a fit by ONE Laplace E-step of its parameters on the test split instead of the
     numTestTrials * ydim held-out mode searches: errs[i] = - sum_r log Z_r / sum_r T_r, the negative Laplace log evidence per bin (lower is
-    better, so optimXdim stays the arg-min).  It also takes test trials of unequal length, which the leave-one-out score refuses."""
+    better, so optimXdim stays the arg-min).  It also takes test trials of unequal length, which the leave-one-out score refuses.
+    score='speckled' (an addition; Laplace only) hides a seeded random subset of the TRAINING trials' live entries (speckledHoldout: each with
+    probability holdoutFraction, numpy.random.default_rng(seed), the same subset for every width), fits on the rest and scores the fit by
+    binHoldout at the hidden entries: errs[i] = - bitsPerSpike (lower is better); the test split is not used."""
 
     def __init__(self, experiment, numTrainingTrials=10, numTestTrials=2, maxXdim=6, maxEMiter=3, batchSize=5,
-                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo'):
+                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo', holdoutFraction=0.1, seed=0):
         from . import engine
         if learningMethod not in ('batch', 'diag', 'hess', 'grad'):
             raise ValueError("learningMethod must be 'batch', 'diag', 'hess' or 'grad'")
-        if score not in ('loo', 'evidence'):
-            raise ValueError("score must be 'loo' or 'evidence'")
+        if score not in ('loo', 'evidence', 'speckled'):
+            raise ValueError("score must be 'loo' or 'evidence', or 'speckled' (hold-out of single entries of the training trials)")
         if score == 'evidence' and inferenceMethod != 'laplace':
             raise ValueError("score='evidence' is the Laplace log evidence: it needs inferenceMethod='laplace'")
+        if score == 'speckled' and inferenceMethod != 'laplace':
+            raise ValueError("score='speckled' fits and scores under a per-bin table: it needs inferenceMethod='laplace'")
         trainingSet, testSet = splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials)
+        if score == 'speckled':
+            scoredSet = trainingSet                       # (the hidden entries are scored against the training trials' true counts)
+            self.heldOut = speckledHoldout(scoredSet, holdoutFraction, seed)
+            trainingSet = _with_hidden_entries(scoredSet, self.heldOut)
         self.errs, self.fits = [], []
         for xdimFit in range(1, maxXdim + 1):
             initParams = initializeParams(xdimFit, trainingSet.ydim, trainingSet)
@@ -429,7 +574,9 @@ class crossValidation:
                 fit = engine.PPGPFAfit(experiment=trainingSet, initParams=initParams, inferenceMethod=inferenceMethod,
                                        EMmode='Online', onlineParamUpdateMethod=learningMethod, maxEMiter=maxEMiter,
                                        batchSize=batchSize, quiet=quiet)
-            if score == 'evidence':
+            if score == 'speckled':
+                predErr = -binHoldout(fit.optimParams, scoredSet, self.heldOut)['bitsPerSpike']
+            elif score == 'evidence':
                 predErr = negLogEvidencePerBin(fit.optimParams, testSet)
             else:
                 _, predErr = leaveOneOutPrediction(fit.optimParams, testSet)
@@ -564,6 +711,9 @@ def countMoments(experiment, xdim):
     if sess.comm_ready:
         red = sess.allreduce(np.concatenate([s, S.reshape(-1), [ns]]))
         s, S, ns = red[:s.size], red[s.size:-1].reshape(S.shape), float(red[-1])
+    if getattr(sess, 'observed_bins', None) is not None:   # (per-bin table: live and co-live entries, counted on the host from the boolean table)
+        mean, cov = _live_moments(s, S, sess.live_entries()[np.asarray(trial_idx, dtype=np.int64)])
+        return mean, cov, s, int(ns)
     observed = getattr(sess, 'observed', None)
     if observed is not None:
         mean, cov = _observed_moments(s, S, observed, sess.lengths, sess.T, trial_idx)
@@ -574,13 +724,30 @@ def countMoments(experiment, xdim):
 
 
 def observedTrialCounts(experiment, xdim):
-    """Per neuron, the number of the experiment's trials that observed it (experiment.data[r]['observed']); the trial count where no table is set."""
+    """Per neuron, the number of the experiment's trials that observed it (experiment.data[r]['observed']); the trial count where no table is set.
+    Under a per-bin table ('observedBins') a trial counts by the fraction of its T_r bins that are live for the neuron: sum_r n_live[r][i] / T_r."""
     from . import _session
     sess, trial_idx = _session.session_for(experiment, xdim)
+    if getattr(sess, 'observed_bins', None) is not None:
+        idx = np.asarray(trial_idx, dtype=np.int64)
+        Tr = np.full(len(idx), float(sess.T)) if sess.lengths is None else np.asarray(sess.lengths, dtype=np.float64)[idx]
+        return (sess.live_entries()[idx].sum(axis=2) / Tr[:, None]).sum(axis=0)
     observed = getattr(sess, 'observed', None)
     if observed is None:
         return float(len(trial_idx))
     return observed[np.asarray(trial_idx, dtype=np.int64)].sum(axis=0).astype(np.float64)
+
+
+def _live_moments(s, S, live):
+    """Count moments under a per-bin table: the formulas of _observed_moments with n_i = live entries of neuron i and n_ij = entries at which both
+    neurons of a pair are live, over the boolean table live[n][q][T] of the listed trials (lengths and the observation table folded in)."""
+    L = np.asarray(live, dtype=np.float64)
+    n_i = L.sum(axis=(0, 2))
+    n_ij = np.einsum('rit,rjt->ij', L, L)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = np.where(n_i > 0, s / n_i, 0.0)
+        cov = (S - np.outer(s, s) * n_ij / np.outer(n_i, n_i)) / (n_ij - 1.0)
+    return mean, np.where(n_ij >= 2, cov, 0.0)
 
 
 def _observed_moments(s, S, observed, lengths, T, trial_idx):

@@ -423,8 +423,8 @@ int ensure_workspace(pgpfa_ctx* c, bool plan_lr) {
   static_assert(sizeof(PcgCtl) <= 64, "the control block is the first 16 words of the solve's upload block");
   CHK(dmalloc(c, &c->pcg_blk, 16 + 4 * nB, true));
   if (c->pcg_blk) {
-    c->pcgctl = reinterpret_cast<PcgCtl*>(c->pcg_blk); c->list_a = c->pcg_blk + 16; c->live = c->list_a + nB;
-    c->pcg_eta = reinterpret_cast<float*>(c->live + nB); c->live1 = c->live + 2 * nB;
+    c->pcgctl = reinterpret_cast<PcgCtl*>(c->pcg_blk); c->list_a = c->pcg_blk + 16; c->live0 = c->list_a + nB;
+    c->pcg_eta = reinterpret_cast<float*>(c->live0 + nB); c->live1 = c->live0 + 2 * nB;
   }
   CHK(dmalloc(c, &c->pcg_ratio, nB, true));
   CHK(dmalloc(c, &c->GbT, (size_t)c->T * (c->p * (c->p + 1) / 2) + 64)); CHK(dmalloc(c, &c->WbT, (size_t)c->T * (c->p * (c->p + 1) / 2) + 64));
@@ -898,6 +898,7 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   HIPC(hipSetDevice(device));
   pgpfa_ctx* c = new pgpfa_ctx();
   c->device = device; c->q = q; c->p = p; c->T = T; c->R = R; c->bin = bin_ms;
+  c->live.q = q; c->live.T = T;
   c->n = p * T;
   c->npad = round_up(c->n, NB);
   c->ld = c->npad;
@@ -1002,6 +1003,8 @@ int pgpfa_create(pgpfa_ctx** out, int device, int q, int p, int T, int R, double
   return 0;
 }
 
+static void free_tables(LiveTables& L);                    // (the missing-data tables, below)
+
 int pgpfa_destroy(pgpfa_ctx* c) {
   if (!c) return 0;
   hipSetDevice(c->device);
@@ -1013,10 +1016,7 @@ int pgpfa_destroy(pgpfa_ctx* c) {
   if (c->lam_keep) hipFree(c->lam_keep);
   if (c->split_buf) hipFree(c->split_buf);
   if (c->Yhi) hipFree(c->Yhi);
-  if (c->trial_len) hipFree(c->trial_len);
-  if (c->obs) hipFree(c->obs);
-  if (c->binw) hipFree(c->binw);
-  if (c->nlive) hipFree(c->nlive);
+  free_tables(c->live);
   if (c->trunc_q) hipFree(c->trunc_q);
   arena_release(c);
   if (c->hbuf) hipHostFree(c->hbuf);
@@ -1236,249 +1236,52 @@ int ensure_high_plane(pgpfa_ctx* c) {
   return 0;
 }
 
-// ---- single entries not recorded (per-bin table) ----------------------------------------------------------------------------------
-static void drop_observed_bins(pgpfa_ctx* c) {
-  if (c->binw) {
-    hipStreamSynchronize(c->st);
-    hipFree(c->binw);
-    hipFree(c->nlive);
-    const size_t nw = (size_t)(c->T + 63) / 64;
-    c->bytes -= (size_t)c->R * (c->q + 1) * nw * sizeof(unsigned long long) + (size_t)c->R * c->q * sizeof(int);
-    c->binw = nullptr;
-    c->nlive = nullptr;
-  }
-  c->nlive_h.clear();
-  c->bins_h.clear();
-  c->info["observed_bins_set"] = 0.0;
+// ---- the missing-data tables (LiveTables, live.h): lengths, observation table, per-bin table ---------------------------------------------
+static_assert(OBS_NONE == 0 && OBS_ROWS == 1 && OBS_BINS == 2, "dispatch_obs (ctx.h) switches on these values");
+int LiveTables::state() const { return binw ? OBS_BINS : (obs ? OBS_ROWS : OBS_NONE); }
+
+static void free_tables(LiveTables& L) {
+  if (L.trial_len) hipFree(L.trial_len);
+  if (L.obs) hipFree(L.obs);
+  if (L.binw) hipFree(L.binw);
+  if (L.nlive) hipFree(L.nlive);
 }
 
-int refuse_observed_bins(const pgpfa_ctx* c, const char* entry) {
-  if (c && c->binw)
+int refuse_tables(const pgpfa_ctx* c, const char* entry, int allowed, int with_dual_masked) {
+  if (!c) return 0;
+  const LiveTables& L = c->live;
+  const int set = (L.trial_len ? TBL_LEN : 0) | (L.obs ? TBL_ROWS : 0) | (L.binw ? TBL_BINS : 0);
+  int bad = set & ~(allowed | with_dual_masked);
+  if (!bad && !c->dual_masked) bad = set & ~allowed;
+  if (bad & TBL_LEN)
+    return fail("%s does not support trials of unequal length yet: per-trial bin counts are set (pgpfa_set_trial_lengths) and the padded bins "
+                "would be treated as data", entry);
+  if (bad & TBL_ROWS)
+    return fail("%s does not support unobserved neurons yet: an observation table is set (pgpfa_set_observed) and the unobserved rows "
+                "would be treated as silent neurons", entry);
+  if (bad & TBL_BINS)
     return fail("%s does not support a per-bin observation table yet: one is set (pgpfa_set_observed_bins) and the entries it marks as not "
                 "recorded would be treated as zero counts", entry);
   return 0;
 }
 
-// One word of 64 bins per workgroup (a single wave): bit t & 63 of words[r][n][t >> 6] = entry (r, n, t) is live - marked in raw (may be NULL: all),
-// inside the trial's length (len may be NULL) and the neuron recorded on the trial (obs may be NULL).  Row q of a trial collects the OR over its
-// neurons, nlive[r][n] the popcounts, bad[r] the non-zero counts at entries that are not live (either byte plane).  words, nlive and bad come in
-// zeroed.  With raw, len and obs all NULL and `check` set it only counts against the finished words (counts uploaded under a table).
-// grid = R q ceil(T/64), block = 64
-static __global__ __launch_bounds__(64) void pack_bins_kernel(const uint8_t* __restrict__ raw, const int* __restrict__ len, const uint8_t* __restrict__ obs,
-                                                              const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, int q, int T, int nw,
-                                                              unsigned long long* __restrict__ words, int* __restrict__ nlive, int* __restrict__ bad, int check) {
-  const int lane = threadIdx.x;
-  const int w = blockIdx.x % nw, n = (blockIdx.x / nw) % q;
-  const size_t r = blockIdx.x / ((unsigned)nw * q);
-  const int t = w * 64 + lane;
-  const bool in = t < T;
-  const size_t e = (r * q + n) * T + (in ? t : 0);
-  const size_t wi = (r * (q + 1) + n) * nw + w;
-  bool live;
-  if (check) live = (words[wi] >> lane) & 1ull;
-  else live = in && (!raw || raw[e] != 0) && (!len || t < len[r]) && (!obs || obs[r * q + n] != 0);
-  const bool nz = in && !live && (Y[e] != 0 || (Yhi && Yhi[e] != 0));
-  const unsigned long long m = __ballot(live), b = __ballot(nz);
-  if (lane == 0) {
-    if (!check) {
-      words[wi] = m;
-      if (m) {
-        atomicAdd(&nlive[r * q + n], __popcll(m));
-        atomicOr(&words[(r * (q + 1) + q) * nw + w], m);
-      }
-    }
-    if (b) atomicAdd(&bad[r], __popcll(b));
-  }
-}
-
-// The device image of the per-bin table from the host copy c->bins_h and the given length and observation tables (device pointers, either may be
-// NULL): built, validated - every trial and every neuron keeps a live entry, counts at dead entries are zero - and only then put in place of the
-// one before.  On failure the context keeps what it had.
-static int rebuild_observed_bins(pgpfa_ctx* c, const int* dlen, const uint8_t* dobs) {
-  const int R = c->R, q = c->q, T = c->T, nw = (T + 63) / 64;
-  const size_t nraw = (size_t)R * q * T, nwords = (size_t)R * (q + 1) * nw, nblocks = (size_t)R * q * nw;
-  if (nblocks > 0x7fffffffull) return fail("pgpfa_set_observed_bins: R q ceil(T/64) = %zu exceeds the grid limit", nblocks);
-  uint8_t* draw = nullptr;
-  unsigned long long* dw = nullptr;
-  int *dnl = nullptr, *dbad = nullptr;
-  auto release = [&]() { if (draw) hipFree(draw); if (dw) hipFree(dw); if (dnl) hipFree(dnl); if (dbad) hipFree(dbad); };
-  if (hipMalloc((void**)&draw, nraw) != hipSuccess || hipMalloc((void**)&dw, nwords * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void**)&dnl, (size_t)R * q * sizeof(int)) != hipSuccess || hipMalloc((void**)&dbad, (size_t)R * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    release();
-    return fail("hipMalloc for the per-bin observation table failed");
-  }
-  std::vector<int> nl((size_t)R * q, 0), bad(R, 0);
-  hipMemcpyAsync(draw, c->bins_h.data(), nraw, hipMemcpyHostToDevice, c->st);
-  hipMemsetAsync(dw, 0, nwords * sizeof(unsigned long long), c->st);
-  hipMemsetAsync(dnl, 0, (size_t)R * q * sizeof(int), c->st);
-  hipMemsetAsync(dbad, 0, (size_t)R * sizeof(int), c->st);
-  hipLaunchKernelGGL(pack_bins_kernel, dim3((unsigned)nblocks), dim3(64), 0, c->st, draw, dlen, dobs, c->Y, c->Yhi, q, T, nw, dw, dnl, dbad, 0);
-  hipMemcpyAsync(nl.data(), dnl, (size_t)R * q * sizeof(int), hipMemcpyDeviceToHost, c->st);
-  hipMemcpyAsync(bad.data(), dbad, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->st);
-  hipError_t e = hipStreamSynchronize(c->st);            // (the host vectors and the device temporaries outlive every copy and the kernel)
-  if (e == hipSuccess) e = hipGetLastError();
-  hipFree(draw); draw = nullptr;
-  hipFree(dbad); dbad = nullptr;
-  if (e != hipSuccess) { release(); return fail("pgpfa_set_observed_bins: %s", hipGetErrorString(e)); }
-  for (int r = 0; r < R; ++r) {
-    long long seen = 0;
-    for (int n = 0; n < q; ++n) seen += nl[(size_t)r * q + n];
-    if (!seen) { release(); return fail("trial %d has no live entry under the per-bin table (with lengths and the observation table folded in)", r); }
-  }
-  for (int n = 0; n < q; ++n) {
-    long long seen = 0;
-    for (int r = 0; r < R; ++r) seen += nl[(size_t)r * q + n];
-    if (!seen) { release(); return fail("neuron %d has no live entry on any trial under the per-bin table", n); }
-  }
-  for (int r = 0; r < R; ++r)
-    if (bad[r]) {
-      release();
-      return fail("trial %d: %d non-zero counts at entries the per-bin table marks as not recorded: the count tensor must be zero there", r, bad[r]);
-    }
-  if (c->binw) {
-    hipFree(c->binw);
-    hipFree(c->nlive);
-  } else {
-    c->bytes += nwords * sizeof(unsigned long long) + (size_t)R * q * sizeof(int);
-  }
-  c->binw = dw;
-  c->nlive = dnl;
-  c->nlive_h.swap(nl);
-  c->info["observed_bins_set"] = 1.0;
-  return 0;
-}
-
-// counts uploaded while a per-bin table is set must be zero at its dead entries; on failure the context has no counts (the caller uploads again)
-static int recheck_observed_bins(pgpfa_ctx* c) {
-  if (!c->binw) return 0;
-  const int R = c->R, nw = (c->T + 63) / 64;
-  int* dbad = nullptr;
-  if (hipMalloc((void**)&dbad, (size_t)R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail("hipMalloc failed"); }
-  std::vector<int> bad(R, 0);
-  hipMemsetAsync(dbad, 0, (size_t)R * sizeof(int), c->st);
-  hipLaunchKernelGGL(pack_bins_kernel, dim3((unsigned)((size_t)R * c->q * nw)), dim3(64), 0, c->st, (const uint8_t*)nullptr, (const int*)nullptr,
-                     (const uint8_t*)nullptr, c->Y, c->Yhi, c->q, c->T, nw, c->binw, c->nlive, dbad, 1);
-  hipMemcpyAsync(bad.data(), dbad, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->st);
-  hipError_t e = hipStreamSynchronize(c->st);
-  if (e == hipSuccess) e = hipGetLastError();
-  hipFree(dbad);
-  if (e != hipSuccess) { c->have_counts = false; return fail("pgpfa_upload_counts: %s", hipGetErrorString(e)); }
-  for (int r = 0; r < R; ++r)
-    if (bad[r]) {
-      c->have_counts = false;
-      return fail("trial %d: %d non-zero counts at entries the per-bin table marks as not recorded: the count tensor must be zero there", r, bad[r]);
-    }
-  return 0;
-}
-
-// ---- trials of unequal length --------------------------------------------------------------------------------------------------
-static void drop_trial_lengths(pgpfa_ctx* c) {
-  if (c->trial_len) {
-    hipStreamSynchronize(c->st);
-    hipFree(c->trial_len);
-    c->bytes -= (size_t)c->R * sizeof(int);
-    c->trial_len = nullptr;
-  }
-  c->trial_len_h.clear();
-  c->info["trial_lengths_set"] = 0.0;
-}
-
-int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry) {
-  if (c && c->trial_len)
-    return fail("%s does not support trials of unequal length yet: per-trial bin counts are set (pgpfa_set_trial_lengths) and the padded bins "
-                "would be treated as data", entry);
-  return 0;
-}
-
-// cnt[r] = number of non-zero counts of trial r at bins t >= len[r] (either byte plane).  grid = R, block = 256
-static __global__ __launch_bounds__(256) void padded_counts_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const int* __restrict__ len,
-                                                                   int q, int T, int* __restrict__ cnt) {
-  __shared__ int red[4];
-  const size_t r = blockIdx.x;
-  const int L = len[r], w = T - L;
-  int bad = 0;
-  for (long long e = threadIdx.x; e < (long long)q * w; e += 256) {
-    const size_t i = (r * q + (size_t)(e / w)) * T + L + (size_t)(e % w);
-    bad += (Y[i] != 0) || (Yhi && Yhi[i] != 0);
-  }
-  for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bad;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[r] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
-  if (!c) return fail("null context");
-  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_trial_lengths checks them");
-  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
-  HIPC(hipSetDevice(c->device));
-  if (!len) {                                               // back to R trials of T bins; what was computed under the table is stale
-    if (c->trial_len) {
-      if (c->binw) CHK(rebuild_observed_bins(c, nullptr, c->obs));     // (the per-bin words carry the lengths: built anew without them)
-      drop_trial_lengths(c);
-      counts_changed(c, nullptr);
-    }
-    return 0;
-  }
-  for (int r = 0; r < c->R; ++r)
-    if (len[r] < 1 || len[r] > c->T) return fail("trial %d: length %d is outside 1..T = %d", r, (int)len[r], c->T);
-  int* dlen = nullptr;
-  int* dcnt = nullptr;
-  HIPC(hipMalloc((void**)&dlen, (size_t)c->R * sizeof(int)));
-  if (hipMalloc((void**)&dcnt, (size_t)c->R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); hipFree(dlen); return fail("hipMalloc failed"); }
-  std::vector<int> lv(len, len + c->R), bad(c->R, 0);
-  hipMemcpyAsync(dlen, lv.data(), (size_t)c->R * sizeof(int), hipMemcpyHostToDevice, c->st);
-  hipLaunchKernelGGL(padded_counts_kernel, dim3(c->R), dim3(256), 0, c->st, c->Y, c->Yhi, dlen, c->q, c->T, dcnt);
-  hipMemcpyAsync(bad.data(), dcnt, (size_t)c->R * sizeof(int), hipMemcpyDeviceToHost, c->st);
-  const hipError_t e = hipStreamSynchronize(c->st);
-  hipFree(dcnt);
-  if (e != hipSuccess || hipGetLastError() != hipSuccess) { hipFree(dlen); return fail("pgpfa_set_trial_lengths: %s", hipGetErrorString(e)); }
-  for (int r = 0; r < c->R; ++r)
-    if (bad[r]) {
-      hipFree(dlen);
-      return fail("trial %d: %d non-zero counts at padded bins (t >= %d): the count tensor must be zero-padded behind a trial's length", r, bad[r], lv[r]);
-    }
-  if (c->binw && rebuild_observed_bins(c, dlen, c->obs)) { hipFree(dlen); return 1; }   // (the per-bin words carry the lengths; a trial these leave without a live entry fails here)
-  drop_trial_lengths(c);
-  c->trial_len = dlen;
-  c->bytes += (size_t)c->R * sizeof(int);
-  c->trial_len_h.swap(lv);
-  c->info["trial_lengths_set"] = 1.0;
-  counts_changed(c, nullptr);                               // sums and posteriors computed under other lengths are stale
-  return 0;
-}
-
-// ---- neurons unobserved on some trials -------------------------------------------------------------------------------------------
-static void drop_observed(pgpfa_ctx* c) {
-  if (c->obs) {
-    hipStreamSynchronize(c->st);
-    hipFree(c->obs);
-    c->bytes -= (size_t)c->R * c->q;
-    c->obs = nullptr;
-  }
-  c->obs_h.clear();
-  c->info["observed_set"] = 0.0;
-}
-
-int refuse_observed(const pgpfa_ctx* c, const char* entry) {
-  if (c && c->obs)
-    return fail("%s does not support unobserved neurons yet: an observation table is set (pgpfa_set_observed) and the unobserved rows "
-                "would be treated as silent neurons", entry);
-  return 0;
-}
-
-// cnt[r] = number of non-zero counts of trial r at rows n with obs[r][n] == 0 (either byte plane).  grid = R, block = 256 (a wave per neuron row)
-static __global__ __launch_bounds__(256) void unobserved_counts_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const uint8_t* __restrict__ obs,
-                                                                       int q, int T, int* __restrict__ cnt) {
+// cnt[r] = number of non-zero counts of trial r (either byte plane) at entries that are not live under the tables given (each may be NULL): bins
+// t >= len[r], rows n with obs[r][n] == 0, clear bits of the words [R][q + 1][nw].  grid = R, block = 256 (a wave per neuron row)
+static __global__ __launch_bounds__(256) void dead_counts_kernel(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ Yhi, const int* __restrict__ len,
+                                                                 const uint8_t* __restrict__ obs, const unsigned long long* __restrict__ words, int q, int T, int nw,
+                                                                 int* __restrict__ cnt) {
   __shared__ int red[4];
   const size_t r = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int L = len ? len[r] : T;
   int bad = 0;
   for (int n = wave; n < q; n += 4) {
-    if (obs[r * q + n]) continue;                           // (uniform over the wave)
+    const bool row = !obs || obs[r * q + n] != 0;            // (uniform over the wave)
     const size_t base = (r * q + n) * T;
-    for (int t = lane; t < T; t += 64) bad += (Y[base + t] != 0) || (Yhi && Yhi[base + t] != 0);
+    for (int t = lane; t < T; t += 64) {
+      const bool live = row && t < L && (!words || ((words[(r * (q + 1) + n) * nw + (t >> 6)] >> (t & 63)) & 1ull));
+      bad += !live && (Y[base + t] != 0 || (Yhi && Yhi[base + t] != 0));
+    }
   }
   for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
   if (lane == 0) red[wave] = bad;
@@ -1486,101 +1289,218 @@ static __global__ __launch_bounds__(256) void unobserved_counts_kernel(const uin
   if (threadIdx.x == 0) cnt[r] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// the resident counts against a device table: fails, naming the first trial, on a non-zero count at an unobserved row
-static int check_unobserved_counts(pgpfa_ctx* c, const uint8_t* dobs) {
+// The resident counts against ONE device table (the other two pointers NULL; len_h: host copy of len): fails, naming the first trial, on a non-zero
+// count at an entry the table marks dead.
+static int check_dead_counts(pgpfa_ctx* c, const char* entry, const int* len, const std::vector<int>* len_h, const uint8_t* obs, const unsigned long long* words) {
   int* dcnt = nullptr;
   if (hipMalloc((void**)&dcnt, (size_t)c->R * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail("hipMalloc failed"); }
   std::vector<int> bad(c->R, 0);
-  hipLaunchKernelGGL(unobserved_counts_kernel, dim3(c->R), dim3(256), 0, c->st, c->Y, c->Yhi, dobs, c->q, c->T, dcnt);
+  hipLaunchKernelGGL(dead_counts_kernel, dim3(c->R), dim3(256), 0, c->st, c->Y, c->Yhi, len, obs, words, c->q, c->T, (c->T + 63) / 64, dcnt);
   hipMemcpyAsync(bad.data(), dcnt, (size_t)c->R * sizeof(int), hipMemcpyDeviceToHost, c->st);
   const hipError_t e = hipStreamSynchronize(c->st);
   hipFree(dcnt);
-  if (e != hipSuccess || hipGetLastError() != hipSuccess) return fail("pgpfa_set_observed: %s", hipGetErrorString(e));
-  for (int r = 0; r < c->R; ++r)
-    if (bad[r]) return fail("trial %d: %d non-zero counts at unobserved neurons: the count tensor must be zero at the rows the table marks as not recorded", r, bad[r]);
+  if (e != hipSuccess || hipGetLastError() != hipSuccess) return fail("%s: %s", entry, hipGetErrorString(e));
+  for (int r = 0; r < c->R; ++r) {
+    if (!bad[r]) continue;
+    if (len) return fail("trial %d: %d non-zero counts at padded bins (t >= %d): the count tensor must be zero-padded behind a trial's length", r, bad[r], (*len_h)[r]);
+    if (obs) return fail("trial %d: %d non-zero counts at unobserved neurons: the count tensor must be zero at the rows the table marks as not recorded", r, bad[r]);
+    return fail("trial %d: %d non-zero counts at entries the per-bin table marks as not recorded: the count tensor must be zero there", r, bad[r]);
+  }
   return 0;
 }
 
-int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
+// One word of 64 bins per workgroup (a single wave): bit t & 63 of words[r][n][t >> 6] = entry (r, n, t) is live - marked in raw, inside the trial's
+// length (len may be NULL) and the neuron recorded on the trial (obs may be NULL).  Row q of a trial collects the OR over its neurons, nlive[r][n]
+// the popcounts.  words and nlive come in zeroed.  grid = R q ceil(T/64), block = 64
+static __global__ __launch_bounds__(64) void pack_bins_kernel(const uint8_t* __restrict__ raw, const int* __restrict__ len, const uint8_t* __restrict__ obs,
+                                                              int q, int T, int nw, unsigned long long* __restrict__ words, int* __restrict__ nlive) {
+  const int lane = threadIdx.x;
+  const int w = blockIdx.x % nw, n = (blockIdx.x / nw) % q;
+  const size_t r = blockIdx.x / ((unsigned)nw * q);
+  const int t = w * 64 + lane;
+  const bool live = t < T && raw[(r * q + n) * T + t] != 0 && (!len || t < len[r]) && (!obs || obs[r * q + n] != 0);
+  const unsigned long long m = __ballot(live);
+  if (lane == 0) {
+    words[(r * (q + 1) + n) * nw + w] = m;
+    if (m) {
+      atomicAdd(&nlive[r * q + n], __popcll(m));
+      atomicOr(&words[(r * (q + 1) + q) * nw + w], m);
+    }
+  }
+}
+
+// The device image of a per-bin table from the caller's bytes `raw` and the given length and observation tables (device pointers, either may be
+// NULL): built and validated - every trial and every neuron keeps a live entry, counts at dead entries are zero.  The caller owns *dw and *dnl.
+static int build_bin_words(pgpfa_ctx* c, const char* entry, const std::vector<uint8_t>& raw, const int* dlen, const uint8_t* dobs, unsigned long long** dw, int** dnl,
+                           std::vector<int>* nl) {
+  const int R = c->R, q = c->q, T = c->T, nw = (T + 63) / 64;
+  const size_t nwords = (size_t)R * (q + 1) * nw, nblocks = (size_t)R * q * nw;
+  if (nblocks > 0x7fffffffull) return fail("pgpfa_set_observed_bins: R q ceil(T/64) = %zu exceeds the grid limit", nblocks);
+  uint8_t* draw = nullptr;
+  *dw = nullptr; *dnl = nullptr;
+  auto release = [&]() { if (draw) hipFree(draw); if (*dw) hipFree(*dw); if (*dnl) hipFree(*dnl); draw = nullptr; *dw = nullptr; *dnl = nullptr; };
+  if (hipMalloc((void**)&draw, raw.size()) != hipSuccess || hipMalloc((void**)dw, nwords * sizeof(unsigned long long)) != hipSuccess ||
+      hipMalloc((void**)dnl, (size_t)R * q * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    release();
+    return fail("hipMalloc for the per-bin observation table failed");
+  }
+  nl->assign((size_t)R * q, 0);
+  hipMemcpyAsync(draw, raw.data(), raw.size(), hipMemcpyHostToDevice, c->st);
+  hipMemsetAsync(*dw, 0, nwords * sizeof(unsigned long long), c->st);
+  hipMemsetAsync(*dnl, 0, (size_t)R * q * sizeof(int), c->st);
+  hipLaunchKernelGGL(pack_bins_kernel, dim3((unsigned)nblocks), dim3(64), 0, c->st, draw, dlen, dobs, q, T, nw, *dw, *dnl);
+  hipMemcpyAsync(nl->data(), *dnl, (size_t)R * q * sizeof(int), hipMemcpyDeviceToHost, c->st);
+  hipError_t e = hipStreamSynchronize(c->st);            // (the host vectors and the device temporaries outlive every copy and the kernel)
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(draw); draw = nullptr;
+  if (e != hipSuccess) { release(); return fail("pgpfa_set_observed_bins: %s", hipGetErrorString(e)); }
+  for (int r = 0; r < R; ++r) {
+    long long seen = 0;
+    for (int n = 0; n < q; ++n) seen += (*nl)[(size_t)r * q + n];
+    if (!seen) { release(); return fail("trial %d has no live entry under the per-bin table (with lengths and the observation table folded in)", r); }
+  }
+  for (int n = 0; n < q; ++n) {
+    long long seen = 0;
+    for (int r = 0; r < R; ++r) seen += (*nl)[(size_t)r * q + n];
+    if (!seen) { release(); return fail("neuron %d has no live entry on any trial under the per-bin table", n); }
+  }
+  if (check_dead_counts(c, entry, nullptr, nullptr, nullptr, *dw)) { release(); return 1; }
+  return 0;
+}
+
+// What a setter hands to install_tables: the one table it replaces and the candidate's host copy (an empty vector drops the table).
+struct TableEdit {
+  int which;                                     // TBL_LEN, TBL_ROWS or TBL_BINS
+  std::vector<int> len;                          // TBL_LEN: [R]
+  std::vector<uint8_t> bytes;                    // TBL_ROWS: [R][q]; TBL_BINS: [R][q][T]; 0 / 1
+};
+
+// The one routine through which a table changes.  The candidate combination - the edited table with the other two as they are - is validated against
+// the resident counts (the edited table on its own, then the bin words rebuilt from all three when a per-bin table is part of it) and only then put
+// in place, with everything computed under the tables before marked stale.  On failure the context keeps what it had.
+static int install_tables(pgpfa_ctx* c, const char* entry, TableEdit& ed) {
+  LiveTables& L = c->live;
+  const size_t R = c->R, q = c->q;
+  const int which = ed.which;
+  // device image of a new length / observation table
+  void* dnew = nullptr;
+  const size_t nbytes = which == TBL_LEN ? R * sizeof(int) : R * q;
+  const void* src = which == TBL_LEN ? (const void*)ed.len.data() : (const void*)ed.bytes.data();
+  if (which != TBL_BINS && (which == TBL_LEN ? !ed.len.empty() : !ed.bytes.empty())) {
+    HIPC(hipMalloc(&dnew, nbytes));
+    hipMemcpyAsync(dnew, src, nbytes, hipMemcpyHostToDevice, c->st);
+  }
+  struct Free { void* p; ~Free() { if (p) hipFree(p); } } guard{dnew};
+  const int* dlen = which == TBL_LEN ? (const int*)dnew : L.trial_len;
+  const uint8_t* dobs = which == TBL_ROWS ? (const uint8_t*)dnew : L.obs;
+  if (dnew) CHK(check_dead_counts(c, entry, which == TBL_LEN ? dlen : nullptr, &ed.len, which == TBL_ROWS ? dobs : nullptr, nullptr));
+  // the per-bin words carry the other two tables: built anew from the candidate (a trial it leaves without a live entry fails here)
+  const std::vector<uint8_t>& raw = which == TBL_BINS ? ed.bytes : L.bins_h;
+  unsigned long long* dw = nullptr;
+  int* dnl = nullptr;
+  std::vector<int> nl;
+  if (!raw.empty()) CHK(build_bin_words(c, entry, raw, dlen, dobs, &dw, &dnl, &nl));
+  hipStreamSynchronize(c->st);
+  if (which == TBL_LEN) {
+    if (L.trial_len) { hipFree(L.trial_len); c->bytes -= nbytes; }
+    if (dnew) c->bytes += nbytes;
+    L.trial_len = (int*)dnew;
+    L.trial_len_h.swap(ed.len);
+    c->info["trial_lengths_set"] = dnew ? 1.0 : 0.0;
+  } else if (which == TBL_ROWS) {
+    if (L.obs) { hipFree(L.obs); c->bytes -= nbytes; }
+    if (dnew) c->bytes += nbytes;
+    L.obs = (uint8_t*)dnew;
+    L.obs_h.swap(ed.bytes);
+    c->info["observed_set"] = dnew ? 1.0 : 0.0;
+  } else {
+    L.bins_h.swap(ed.bytes);
+  }
+  guard.p = nullptr;
+  const size_t wbytes = R * (q + 1) * ((c->T + 63) / 64) * sizeof(unsigned long long) + R * q * sizeof(int);
+  if (L.binw) { hipFree(L.binw); hipFree(L.nlive); c->bytes -= wbytes; }
+  if (dw) c->bytes += wbytes;
+  L.binw = dw;
+  L.nlive = dnl;
+  L.nlive_h.swap(nl);
+  c->info["observed_bins_set"] = dw ? 1.0 : 0.0;
+  counts_changed(c, nullptr);                               // sums and posteriors computed under other tables are stale
+  return 0;
+}
+
+// what the three setters check before they look at their table
+static int table_setter_ready(pgpfa_ctx* c, const char* entry) {
   if (!c) return fail("null context");
-  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_observed checks them");
+  if (!c->have_counts) return fail("spike counts have not been uploaded: %s checks them", entry);
   if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
   HIPC(hipSetDevice(c->device));
-  if (!obs) {                                               // back to fully observed trials; what was computed under the table is stale
-    if (c->obs) {
-      if (c->binw) CHK(rebuild_observed_bins(c, c->trial_len, nullptr));   // (the per-bin words carry the table: built anew without it)
-      drop_observed(c);
-      counts_changed(c, nullptr);
-    }
-    return 0;
-  }
+  return 0;
+}
+
+int pgpfa_set_trial_lengths(pgpfa_ctx* c, const int32_t* len) {
+  CHK(table_setter_ready(c, "pgpfa_set_trial_lengths"));
+  TableEdit ed{TBL_LEN};
+  if (!len) return c->live.trial_len ? install_tables(c, "pgpfa_set_trial_lengths", ed) : 0;     // back to R trials of T bins
+  for (int r = 0; r < c->R; ++r)
+    if (len[r] < 1 || len[r] > c->T) return fail("trial %d: length %d is outside 1..T = %d", r, (int)len[r], c->T);
+  ed.len.assign(len, len + c->R);
+  return install_tables(c, "pgpfa_set_trial_lengths", ed);
+}
+
+int pgpfa_set_observed(pgpfa_ctx* c, const uint8_t* obs) {
+  CHK(table_setter_ready(c, "pgpfa_set_observed"));
+  TableEdit ed{TBL_ROWS};
+  if (!obs) return c->live.obs ? install_tables(c, "pgpfa_set_observed", ed) : 0;                 // back to fully observed trials
   const size_t nq = (size_t)c->R * c->q;
-  std::vector<uint8_t> ov(nq);
-  for (size_t i = 0; i < nq; ++i) ov[i] = obs[i] ? 1 : 0;
+  ed.bytes.resize(nq);
+  for (size_t i = 0; i < nq; ++i) ed.bytes[i] = obs[i] ? 1 : 0;
   for (int r = 0; r < c->R; ++r) {
     int seen = 0;
-    for (int n = 0; n < c->q; ++n) seen += ov[(size_t)r * c->q + n];
+    for (int n = 0; n < c->q; ++n) seen += ed.bytes[(size_t)r * c->q + n];
     if (!seen) return fail("trial %d has no observed neuron", r);
   }
   for (int n = 0; n < c->q; ++n) {
     int seen = 0;
-    for (int r = 0; r < c->R; ++r) seen += ov[(size_t)r * c->q + n];
+    for (int r = 0; r < c->R; ++r) seen += ed.bytes[(size_t)r * c->q + n];
     if (!seen) return fail("neuron %d is observed on no trial", n);
   }
-  uint8_t* dobs = nullptr;
-  HIPC(hipMalloc((void**)&dobs, nq));
-  hipMemcpyAsync(dobs, ov.data(), nq, hipMemcpyHostToDevice, c->st);
-  if (check_unobserved_counts(c, dobs)) { hipFree(dobs); return 1; }
-  if (c->binw && rebuild_observed_bins(c, c->trial_len, dobs)) { hipFree(dobs); return 1; }   // (the per-bin words carry the table)
-  drop_observed(c);
-  c->obs = dobs;
-  c->bytes += nq;
-  c->obs_h.swap(ov);
-  c->info["observed_set"] = 1.0;
-  counts_changed(c, nullptr);                               // sums and posteriors computed under another table are stale
-  return 0;
+  return install_tables(c, "pgpfa_set_observed", ed);
 }
 
 int pgpfa_set_observed_bins(pgpfa_ctx* c, const uint8_t* live) {
-  if (!c) return fail("null context");
-  if (!c->have_counts) return fail("spike counts have not been uploaded: pgpfa_set_observed_bins checks them");
-  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
-  HIPC(hipSetDevice(c->device));
-  if (!live) {                                              // back to the length and observation tables alone; what was computed under the table is stale
-    if (c->binw) { drop_observed_bins(c); counts_changed(c, nullptr); }
-    return 0;
-  }
+  CHK(table_setter_ready(c, "pgpfa_set_observed_bins"));
+  TableEdit ed{TBL_BINS};
+  if (!live) return c->live.binw ? install_tables(c, "pgpfa_set_observed_bins", ed) : 0;          // back to the length and observation tables alone
   const size_t n = (size_t)c->R * c->q * c->T;
-  std::vector<uint8_t> bv(n);
-  for (size_t i = 0; i < n; ++i) bv[i] = live[i] ? 1 : 0;
-  c->bins_h.swap(bv);                                       // (rebuild reads the host copy; the one before comes back if the new table is refused)
-  if (rebuild_observed_bins(c, c->trial_len, c->obs)) { c->bins_h.swap(bv); return 1; }
-  counts_changed(c, nullptr);                               // sums and posteriors computed under another table are stale
-  return 0;
+  ed.bytes.resize(n);
+  for (size_t i = 0; i < n; ++i) ed.bytes[i] = live[i] ? 1 : 0;
+  return install_tables(c, "pgpfa_set_observed_bins", ed);
 }
 
-// counts uploaded while a table is set must be zero at its unobserved rows; on failure the context has no counts (the caller uploads again)
-static int recheck_observed(pgpfa_ctx* c) {
-  if (!c->obs) return 0;
-  if (check_unobserved_counts(c, c->obs)) { c->have_counts = false; return 1; }
-  return 0;
-}
-static int recheck_tables(pgpfa_ctx* c) {
-  CHK(recheck_observed(c));
-  return recheck_observed_bins(c);
+// New counts are resident.  A length table belongs to the counts it was checked against and goes, with the bin words rebuilt without it; the
+// observation and per-bin tables stay, and the new counts must be zero at their dead entries.  On failure the context has no counts (the caller
+// uploads again).
+static int tables_after_upload(pgpfa_ctx* c) {
+  LiveTables& L = c->live;
+  TableEdit drop_len{TBL_LEN};
+  int rc = L.obs ? check_dead_counts(c, "pgpfa_upload_counts", nullptr, nullptr, L.obs, nullptr) : 0;
+  if (!rc && L.trial_len) rc = install_tables(c, "pgpfa_upload_counts", drop_len);
+  else if (!rc && L.binw) rc = check_dead_counts(c, "pgpfa_upload_counts", nullptr, nullptr, nullptr, L.binw);
+  if (rc) c->have_counts = false;
+  return rc;
 }
 
 int pgpfa_upload_counts_u8(pgpfa_ctx* c, const uint8_t* Y) {
   if (!c || !Y) return fail("null argument");
   HIPC(hipSetDevice(c->device));
   drop_high_plane(c);
-  drop_trial_lengths(c);                                    // (a length table belongs to the counts it was checked against)
   HIPC(hipMemcpyAsync(c->Y, Y, (size_t)c->R * c->q * c->T, hipMemcpyHostToDevice, c->st));
   HIPC(hipStreamSynchronize(c->st));
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = 0.0;
-  return recheck_tables(c);
+  return tables_after_upload(c);
 }
 
 // counts from a host array of TS (double or uint16): validated and split into byte planes on the device, staged in pieces
@@ -1595,7 +1515,6 @@ static int upload_counts_wide(pgpfa_ctx* c, const TS* Y) {
   hipError_t e = hipMalloc((void**)&flags, 2 * sizeof(int));
   if (e != hipSuccess) { hipFree(tmp); return fail("hipMalloc: %s", hipGetErrorString(e)); }
   drop_high_plane(c);
-  drop_trial_lengths(c);
   int hf[2] = {0, 0};
   int rc = 0;
   for (int pass = 0; pass < 2 && !rc; ++pass) {
@@ -1628,7 +1547,7 @@ static int upload_counts_wide(pgpfa_ctx* c, const TS* Y) {
   c->have_counts = true;
   counts_changed(c, nullptr);
   c->info["counts_two_bytes"] = c->Yhi ? 1.0 : 0.0;
-  return recheck_tables(c);
+  return tables_after_upload(c);
 }
 
 int pgpfa_upload_counts_f64(pgpfa_ctx* c, const double* Y) {

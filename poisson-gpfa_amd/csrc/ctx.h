@@ -24,6 +24,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include "../../include/pgpfa.h"
 #include "types.h"
+#include "live.h"
 
 using namespace pgpfa;
 
@@ -95,21 +96,7 @@ struct pgpfa_ctx {
   // persistent device state
   uint8_t* Y = nullptr;
   uint8_t* Yhi = nullptr;                        // high bytes of the counts: allocated only while the tensor holds a count above 255
-  // Trials of unequal length (pgpfa_set_trial_lengths): bins t >= trial_len[r] of trial r are padding - zero counts, no likelihood term in the
-  // Poisson pass and the (C,d) passes; the GP prior, the solvers and the covariance engines still span all T bins.  NULL: every trial has T bins.
-  int* trial_len = nullptr;                      // device [R]
-  std::vector<int> trial_len_h;                  // host copy (count_moments); empty while trial_len is NULL
-  // Neurons not recorded on some trials (pgpfa_set_observed): obs[r * q + n] == 0 marks a (trial, neuron) pair without a likelihood term - zero counts
-  // (checked), no rate in the Poisson pass, the cold objective and the (C,d) passes.  NULL: every neuron is observed on every trial.
-  uint8_t* obs = nullptr;                        // device [R][q]
-  std::vector<uint8_t> obs_h;                    // host copy (neurons without an observed trial in an M-step list); empty while obs is NULL
-  // Single entries not recorded (pgpfa_set_observed_bins).  The caller's table stays on the host (bins_h, one byte per entry); the device holds it as
-  // bit words of 64 bins with lengths and obs folded in, [R][q + 1][ceil(T/64)] (row q of a trial: OR over its neurons - bin_words, model.h), rebuilt
-  // whenever one of the three tables changes, and the live entries per (trial, neuron).  NULL: no per-bin table.
-  unsigned long long* binw = nullptr;            // device [R][q + 1][ceil(T/64)]
-  int* nlive = nullptr;                          // device [R][q]
-  std::vector<int> nlive_h;                      // host copy (cold objective aside: neurons without a live entry in an M-step list)
-  std::vector<uint8_t> bins_h;                   // the caller's table [R][q][T], 0 / 1; empty while binw is NULL
+  LiveTables live;                               // which entries (trial, neuron, bin) carry a likelihood term: lengths, observation table, per-bin table (live.h)
   double *C = nullptr, *d = nullptr, *tau = nullptr;
   double *Kpad = nullptr, *Kinv = nullptr;      // [p][Tp][Tp]
   double* Xmode = nullptr;                       // [R][p][T]   post_mean / warm start
@@ -220,9 +207,9 @@ struct pgpfa_ctx {
   double *sU = nullptr, *sDinvT = nullptr, *Wbar = nullptr;
   double *Rv = nullptr, *Zv = nullptr, *Pv = nullptr, *Qv = nullptr;
   PcgCtl* pcgctl = nullptr;                      // device-side control block of the inner PCG loop (pcg.h)
-  int* live = nullptr; float *pcg_ratio = nullptr, *pcg_eta = nullptr;   // device live list of the inner solve, per-slot residual ratio / target
+  int* live0 = nullptr; float *pcg_ratio = nullptr, *pcg_eta = nullptr;   // device live list of the inner solve, per-slot residual ratio / target
   int* live1 = nullptr;                          // second live list of the two-kernel step
-  // (pcgctl, list_a, live, pcg_eta, live1 are consecutive pieces of ONE block - 16 + 4 B words - so that a solve's control block, first live list
+  // (pcgctl, list_a, live0, pcg_eta, live1 are consecutive pieces of ONE block - 16 + 4 B words - so that a solve's control block, first live list
   //  and forcing terms go up in one copy: pcg_blk_host is its pinned image)
   int* pcg_blk = nullptr;
   const int* cur_ndev = nullptr;                 // while set: products with a column list take their column count from this device word
@@ -386,6 +373,17 @@ void dispatch_pw(int p, F&& f) {
   }
 }
 
+// template state OBS of the kernels that read a missing-data table (LiveTables::state): OBS_NONE, OBS_ROWS, OBS_BINS (model.h)
+// (cases in the order the instantiations have always been emitted in: the device code of a unit does not depend on this header's history)
+template <typename F>
+void dispatch_obs(int state, F&& f) {
+  switch (state) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+  }
+}
+
 template <typename F>
 void dispatch_pmax(int p, F&& f) {
   if (p <= 4) f(std::integral_constant<int, 4>{});
@@ -460,9 +458,9 @@ int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
 int resolve_trials(pgpfa_ctx* c, int n, const int32_t* idx, Trials* out, bool distinct = false);
 void counts_changed(pgpfa_ctx* c, const std::vector<int>* trials);
-int refuse_observed_bins(const pgpfa_ctx* c, const char* entry);      // fails while a per-bin table is set: entry points that do not know it
-int refuse_observed(const pgpfa_ctx* c, const char* entry);           // fails while an observation table is set: entry points that do not know it
-int refuse_trial_lengths(const pgpfa_ctx* c, const char* entry);      // fails while per-trial bin counts are set: entry points that do not know them
+// Fails while a table is set that the entry point does not know.  allowed: the tables (TBL_*) it understands; with_dual_masked: those it understands
+// only under option dual_masked.  A table outside both is reported first, then lengths, observation table, per-bin table.
+int refuse_tables(const pgpfa_ctx* c, const char* entry, int allowed = 0, int with_dual_masked = 0);
 int ensure_high_plane(pgpfa_ctx* c);
 int ready(pgpfa_ctx* c);
 int ready_estep(pgpfa_ctx* c, bool allow_lowrank);
@@ -499,7 +497,6 @@ int ensure_lambda(pgpfa_ctx* c);
 int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<double>* sD, std::vector<double>* vKv);
 int dual_jitter(pgpfa_ctx* c, int nb);
 // option dual_masked (see pgpfa_ctx::dual_masked)
-int refuse_dual_tables(const pgpfa_ctx* c, const char* entry);       // refuse_trial_lengths + refuse_observed unless the option is on
 bool dual_masking(const pgpfa_ctx* c);                                // the option is on and a table is set: dual variables carry the live mask
 int dual_mask(pgpfa_ctx* c, int nb, double* buf);                     // zero the entries that are not live of a [slot][q][T] array (no-op unless dual_masking)
 int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale);            // the dense engine's jitter: the diagonal scale of assemble, or in the W blocks (length table)

@@ -7,23 +7,11 @@ using namespace pgpfa;
 
 // ---- dual variational E-step (inference.py:188-432) ----------------------------------------------------
 // Option dual_masked: trials of unequal length and unobserved neurons in the dual path (pgpfa_ctx::dual_masked)
-int refuse_dual_tables(const pgpfa_ctx* c, const char* entry) {
-  CHK(refuse_observed_bins(c, entry));                      // (a per-bin table is outside the option too)
-  if (c && c->dual_masked) return 0;
-  CHK(refuse_trial_lengths(c, entry));
-  return refuse_observed(c, entry);
-}
-
-bool dual_masking(const pgpfa_ctx* c) { return c->dual_masked && (c->trial_len || c->obs); }
-
-static bool dual_live(const pgpfa_ctx* c, int trial, size_t e) {       // entry e = n T + t of a trial's dual variables has a likelihood term
-  if (c->trial_len && (int)(e % c->T) >= c->trial_len_h[trial]) return false;
-  return !c->obs || c->obs_h[(size_t)trial * c->q + e / c->T] != 0;
-}
+bool dual_masking(const pgpfa_ctx* c) { return c->dual_masked && (c->live.lengths() || c->live.rows()); }
 
 int dual_mask(pgpfa_ctx* c, int nb, double* buf) {
   if (!dual_masking(c)) return 0;
-  hipLaunchKernelGGL(dual_live_mask_kernel, dim3((unsigned)(((size_t)c->q * c->T + 255) / 256), nb), dim3(256), 0, c->st, buf, c->trial_of_slot, c->trial_len, c->obs,
+  hipLaunchKernelGGL(dual_live_mask_kernel, dim3((unsigned)(((size_t)c->q * c->T + 255) / 256), nb), dim3(256), 0, c->st, buf, c->trial_of_slot, c->live.lengths(), c->live.rows(),
                      c->q, c->T);
   HIPC(hipGetLastError());
   return 0;
@@ -59,8 +47,8 @@ int ensure_trunc_prior(pgpfa_ctx* c) {
 // log det(P_a + J_a) of the reference's truncated trial minus the log det of the padded jittered precision the engines factor:
 // sum_k (log det K_{k,T} - log det K_{k,T_r})   (0 without a length table, and exactly 0 for a trial of all T bins)
 static double trunc_logdet_correction(const pgpfa_ctx* c, int trial) {
-  if (!c->dual_masked || !c->trial_len) return 0.0;
-  const int T = c->T, L = c->trial_len_h[trial];
+  if (!c->dual_masked || !c->live.lengths()) return 0.0;
+  const int T = c->T, L = c->live.length(trial);
   double s = 0.0;
   for (int k = 0; k < c->p; ++k) s += c->trunc_ld[(size_t)k * (T + 1) + T] - c->trunc_ld[(size_t)k * (T + 1) + L];
   return s;
@@ -70,7 +58,7 @@ static double trunc_logdet_correction(const pgpfa_ctx* c, int trial) {
 // trial and goes into the W blocks of the slots [0, nb) instead (dual_jitter), and the assembly runs with scale 1.
 int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale) {
   *scale = 1.0 + 1e-6;
-  if (c->dual_masked && c->trial_len) { CHK(dual_jitter(c, nb)); *scale = 1.0; }
+  if (c->dual_masked && c->live.lengths()) { CHK(dual_jitter(c, nb)); *scale = 1.0; }
   return 0;
 }
 
@@ -134,7 +122,7 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
 }
 
 int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost, double* grad) {
-  CHK(refuse_dual_tables(c, "pgpfa_dual_costgrad"));
+  CHK(refuse_tables(c, "pgpfa_dual_costgrad", 0, TBL_LEN | TBL_ROWS));
   // (the low-rank engine, and any evaluation under a table, is the batched evaluation with one trial)
   if (c && c->have_counts && c->have_params && ((c->dual_lowrank && want_lowrank(c)) || dual_masking(c))) {
     // the low-rank engine is the batched evaluation with one trial
@@ -179,9 +167,7 @@ int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost
 
 // VIPostMean (inference.py:193-194): -K_big C_big (lambda - y) for one trial, latent-major [p*T].
 int pgpfa_dual_post_mean(pgpfa_ctx* c, int trial, const double* lam, double* mean) {
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_post_mean"));
-  CHK(refuse_observed(c, "pgpfa_dual_post_mean"));
-  CHK(refuse_observed_bins(c, "pgpfa_dual_post_mean"));
+  CHK(refuse_tables(c, "pgpfa_dual_post_mean"));
   CHK(ready(c));
   if (!lam || !mean) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
@@ -232,9 +218,7 @@ static int dual_post_cov_dev(pgpfa_ctx* c, double* cov, double* prec) {
 }
 
 int pgpfa_dual_post_cov(pgpfa_ctx* c, int trial, const double* lam, double* cov, double* prec) {
-  CHK(refuse_trial_lengths(c, "pgpfa_dual_post_cov"));
-  CHK(refuse_observed(c, "pgpfa_dual_post_cov"));
-  CHK(refuse_observed_bins(c, "pgpfa_dual_post_cov"));
+  CHK(refuse_tables(c, "pgpfa_dual_post_cov"));
   CHK(ready(c));
   if (!lam || !cov) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
@@ -261,10 +245,10 @@ int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out) {
 
 // the reference's 1e-6 relative jitter on the diagonal of the posterior precision, applied to the W blocks of the slots [0, nb) in place
 int dual_jitter(pgpfa_ctx* c, int nb) {
-  if (c->dual_masked && c->trial_len) {
+  if (c->dual_masked && c->live.lengths()) {
     CHK(ensure_trunc_prior(c));
     hipLaunchKernelGGL(dual_jitter_len_kernel, dim3((unsigned)((c->T * c->p + 255) / 256), nb), dim3(256), 0, c->st, c->W, (long long)c->T * c->p * c->p,
-                       c->Kinv, c->Tp, c->T, c->p, 1e-6, c->trial_of_slot, c->trial_len, c->trunc_q);
+                       c->Kinv, c->Tp, c->T, c->p, 1e-6, c->trial_of_slot, c->live.lengths(), c->trunc_q);
     HIPC(hipGetLastError());
     return 0;
   }
@@ -403,7 +387,7 @@ int var_offsets(pgpfa_ctx* c, int nb, double* out) {
 int pgpfa_dual_fixed_point(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int start, int max_outer, double tol, double* fopt, int32_t* outer,
                            int32_t* vstatus, double* lam_out) {
   if (!c) return fail("null context");
-  CHK(refuse_dual_tables(c, "pgpfa_dual_fixed_point"));
+  CHK(refuse_tables(c, "pgpfa_dual_fixed_point", 0, TBL_LEN | TBL_ROWS));
   if (!fopt || !vstatus) return fail("null argument");
   if (max_outer < 1 || !(tol > 0.0)) return fail("max_outer and tol must be positive");
   if (start < 0 || start > 3) return fail("start must be 0 (cold), 1 (rho is the start), 2 (rho is a previous optimum) or 3 (the resident optimum)");
@@ -442,7 +426,7 @@ int check_distinct(const std::vector<int>& v) {
 int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const double* lam, double* cost, double* grad) {
   PhaseRange range_phase("pgpfa.dual_costgrad_batch");
   if (!c) return fail("null context");
-  CHK(refuse_dual_tables(c, "pgpfa_dual_costgrad_batch"));
+  CHK(refuse_tables(c, "pgpfa_dual_costgrad_batch", 0, TBL_LEN | TBL_ROWS));
   if (!lam || !cost) return fail("null argument");
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
@@ -453,7 +437,7 @@ int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const dou
   const size_t m = (size_t)c->q * c->T;
   const bool masked = dual_masking(c);                              // (entries that are not live are ignored on input and zeroed on the device)
   for (size_t i = 0; i < (size_t)N * m; ++i)
-    if (!(lam[i] > 0.0) && !(masked && !dual_live(c, tr.v[i / m], i % m))) return fail("lambda must be positive (trial %d, entry %zu = %g)", tr.v[i / m], i % m, lam[i]);
+    if (!(lam[i] > 0.0) && !(masked && !c->live.entry_live(tr.v[i / m], i % m))) return fail("lambda must be positive (trial %d, entry %zu = %g)", tr.v[i / m], i % m, lam[i]);
   CHK(check_distinct(tr.v));
   for (int c0 = 0; c0 < N; c0 += c->B) {
     const int nb = std::min(c->B, N - c0);
@@ -476,7 +460,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
                      int32_t* iters) {
   PhaseRange range_phase("pgpfa.dual_lbfgs");
   if (!c) return fail("null context");
-  CHK(refuse_dual_tables(c, "pgpfa_dual_lbfgs"));
+  CHK(refuse_tables(c, "pgpfa_dual_lbfgs", 0, TBL_LEN | TBL_ROWS));
   if (!rho || !fopt) return fail("null argument");
   if (max_iter < 1) return fail("max_iter must be positive");
   Trials tr;
@@ -693,7 +677,7 @@ int pgpfa_dual_lbfgs(pgpfa_ctx* c, int n, const int32_t* idx, double* rho, int m
 // the dual variables resident for the listed trials (the optimum of the last pgpfa_dual_fixed_point, or what pgpfa_dual_finalize was given)
 int pgpfa_get_dual_lambda(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {
   if (!c || !out) return fail("null argument");
-  CHK(refuse_dual_tables(c, "pgpfa_get_dual_lambda"));
+  CHK(refuse_tables(c, "pgpfa_get_dual_lambda", 0, TBL_LEN | TBL_ROWS));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   HIPC(hipSetDevice(c->device));
@@ -710,7 +694,7 @@ int pgpfa_get_dual_lambda(pgpfa_ctx* c, int n, const int32_t* idx, double* out) 
 int pgpfa_dual_finalize(pgpfa_ctx* c, int n, const int32_t* idx, const double* lam, double* nlp_sum) {
   PhaseRange range_phase("pgpfa.dual_finalize");
   if (!c) return fail("null context");
-  CHK(refuse_dual_tables(c, "pgpfa_dual_finalize"));
+  CHK(refuse_tables(c, "pgpfa_dual_finalize", 0, TBL_LEN | TBL_ROWS));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
   const int N = (int)tr.v.size();

@@ -15,15 +15,10 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   a.X = X; a.sX = c->ld; a.G = G; a.sG = c->ld; a.W = W; a.sW = (long long)c->T * c->p * c->p;
   a.fpart = c->fpart; a.slots = d_list; a.trial_of_slot = c->trial_of_slot;
   a.mask = c->mask_active ? c->mask_of_slot : nullptr;
-  a.len = c->trial_len;                                          // NULL unless pgpfa_set_trial_lengths gave the trials bin counts of their own
-  // NULL unless pgpfa_set_observed marked (trial, neuron) pairs as not recorded.  Only the kernels that evaluate exp(h) read the table: the counts at
-  // unobserved rows are zero (checked when the table is set), so the count terms (cd_ym_*, count_moments_kernel) and everything behind this pass - the
-  // PCG, both covariance engines, the evidence, the single-precision covariance phase, rates and samples - see G, W and the objective of the reduced model.
-  a.obs = c->obs;
-  // A per-bin table (pgpfa_set_observed_bins) rides in the same field as words of 64 bins with lengths and the byte table folded in; the kernels
-  // that read it are the instantiations of template state 2 (bin_words, model.h).
-  const bool bins = c->binw != nullptr;
-  if (bins) a.obs = reinterpret_cast<const uint8_t*>(c->binw);
+  // NULL unless a table is set (live.h).  Only the kernels that evaluate exp(h) read the observation table: the counts at unobserved rows are zero
+  // (checked when the table is set), so the count terms (cd_ym_*, count_moments_kernel) and everything behind this pass - the PCG, both covariance
+  // engines, the evidence, the single-precision covariance phase, rates and samples - see G, W and the objective of the reduced model.
+  c->live.fill(a);
   a.off = c->var_active ? c->voff : nullptr; a.sOff = (long long)c->q * c->T;
   a.lam_out = c->lam_out_active ? c->lamd : nullptr; a.sLam = (long long)c->q * c->T;
   a.q = c->q; a.p = c->p; a.T = c->T; a.ntile = (c->T + 63) / 64; a.full = full;
@@ -38,12 +33,12 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
   if (gemm_form) {
     CHK(ensure_lambda(c));
     prof_begin(c, TAG_POISSON, fl);
-    if (bins)                                                     // (lengths and the byte table are folded into the words)
+    if (c->live.words())                                          // (lengths and the byte table are folded into the words)
       hipLaunchKernelGGL(rates_wide_bins_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
-                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, (const unsigned long long*)c->binw, c->q, c->p, c->T);
+                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->live.words(), c->q, c->p, c->T);
     else
       hipLaunchKernelGGL(rates_wide_kernel, grid, dim3(256), (size_t)c->p * 64 * sizeof(double), c->st, c->Y, c->Yhi, c->C, c->d, X, (long long)c->ld,
-                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->trial_len, c->obs, c->q, c->p, c->T);
+                         a.off, c->lamd, c->dgrad, c->fpart, d_list, c->trial_of_slot, c->live.lengths(), c->live.rows(), c->q, c->p, c->T);
     prof_end(c);
     if (full) {
       const int np = c->p * (c->p + 1) / 2;
@@ -72,26 +67,17 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
     const dim3 gridm(a.ntile, nl);
     dispatch_pw(c->p, [&](auto pm) {
       constexpr int PW = decltype(pm)::value;
-      if constexpr (PW <= 10) {
-        if (bins) {                                               // (the instantiations that read the per-bin table)
-          if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-          else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-        } else if (a.obs) {                                       // (the instantiations that read the observation table)
-          if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-          else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-        } else if (nbt == 2) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-        else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-      } else if constexpr (PW <= 16) {
-        if (bins) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, 2>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-        else if (a.obs) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, true>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-        else hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
-      }
+      dispatch_obs(c->live.state(), [&](auto ob) {
+        constexpr int OBS = decltype(ob)::value;
+        if constexpr (PW <= 10) {
+          if (nbt == 2) { hipLaunchKernelGGL((poisson_mfma_kernel<PW, 2, OBS>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad); return; }
+        }
+        if constexpr (PW <= 16) hipLaunchKernelGGL((poisson_mfma_kernel<PW, 1, OBS>), gridm, dim3(256), 0, c->st, a, c->CCu, c->C16, c->qpad);
+      });
     });
   } else {
     dispatch_pw(c->p, [&](auto pm) {
-      if (bins) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, 2>), grid, block, 0, c->st, a);
-      else if (a.obs) hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, true>), grid, block, 0, c->st, a);
-      else hipLaunchKernelGGL(poisson_pass_kernel<decltype(pm)::value>, grid, block, 0, c->st, a);
+      dispatch_obs(c->live.state(), [&](auto ob) { hipLaunchKernelGGL((poisson_pass_kernel<decltype(pm)::value, decltype(ob)::value>), grid, block, 0, c->st, a); });
     });
   }
   prof_end(c);
@@ -647,7 +633,7 @@ static int eval_start_guarded(pgpfa_ctx* c, Chunk& ch, bool guard, EstepStats& s
   if (guard) {
     // (enqueued ahead of the evaluation: its result comes back with that one's read-back)
     hipLaunchKernelGGL(cold_objective_kernel, dim3(nb), dim3(256), 0, c->st, c->Y, c->Yhi, c->d, c->trial_of_slot,
-                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->trial_len, c->obs, c->q, c->T, c->sc_alpha, (const int*)c->nlive);
+                       c->mask_active ? c->mask_of_slot : (const int*)nullptr, c->live.lengths(), c->live.rows(), c->q, c->T, c->sc_alpha, c->live.live_counts());
     CHK(dl_enqueue(c, ch.ftry.data(), c->sc_alpha, nb * sizeof(double)));
   }
   CHK(eval_start(c, ch));
@@ -822,7 +808,7 @@ static int solve_two_kernel(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, Newton
     CHK(upload_nosync(c, c->pcg_blk, img.data(), img.size() * sizeof(int)));
   } else {
     CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
-    CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
+    CHK(copy_dev(c, c->live0, c->list_a, sizeof(int) * na));
     CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
   }
   c->h_pcg[0] = 0; c->h_pcg[1] = 0; c->h_pcg[2] = na;
@@ -830,7 +816,7 @@ static int solve_two_kernel(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, Newton
   cp.GbT = c->GbT; cp.WbT = reinterpret_cast<const float*>(c->WbT); cp.W32T = c->W32; cp.sW32 = sf.sW32; cp.Tw = sf.Tw;
   cp.X = c->Dl; cp.R = c->Rv; cp.P = c->Pv; cp.Q = c->Qv; cp.Z = c->Zv; cp.S = c->Sv; cp.Y = c->Xt; cp.sV = ld;
   cp.part = c->sc_part2; cp.gam = c->cg_scal; cp.alp = c->cg_scal + 2 * (size_t)c->B; cp.rr = c->sc_rr; cp.rr0 = c->sc_rr0; cp.eta = c->pcg_eta;
-  cp.ctl = c->pcgctl; cp.live0 = c->live; cp.live1 = c->live1;
+  cp.ctl = c->pcgctl; cp.live0 = c->live0; cp.live1 = c->live1;
   cp.eps = c->eps; cp.T = T; cp.p = p; cp.inner_min = c->pcg_inner_min; cp.ntile = (T + TB - 1) / TB; cp.B = c->B; cp.xcd_map = c->pcg_xcd;
   cp.X32 = reinterpret_cast<float*>(c->Zv) + (size_t)ld * ((size_t)c->B + 128);     // (the single-precision z fills the first half of Zv)
   cp.Tl = sf.Tl; cp.Tx = T; cp.vec32 = sf.v32 ? 1 : 0; cp.fold_close = f2 ? 1 : 0; cp.host = (volatile int*)c->d_hpcg; cp.Gl = c->Gl; cp.KX = c->KX; cp.Gt = c->Gt;
@@ -865,7 +851,7 @@ static int solve_two_kernel(pgpfa_ctx* c, Chunk& ch, const SolveForm& sf, Newton
     // the preconditioner products for the NEXT iteration run over the list this launch has just written
     c->live_gemm_collect = (it == 0);
     c->cur_ndev = &c->pcgctl->nl[(it & 1) ^ 1];
-    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, (it & 1) ? c->live : c->live1, bound, f2 ? sf.Tl : 0, sf.v32));
+    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, (it & 1) ? c->live0 : c->live1, bound, f2 ? sf.Tl : 0, sf.v32));
     if (device_stopped(c, it, 2)) break;
   }
   // (pcg_form 2: kernel A of step i + 1 closes step i; the last step enqueued is closed here unless the solve had stopped before it)
@@ -888,7 +874,7 @@ static int solve_split(pgpfa_ctx* c, Chunk& ch, NewtonState& nw) {
   // the live list starts as the active list; every slot carries its own forcing term (with pcg_retire = 0: the common one)
   const std::vector<float> eta_s = forcing_terms(c, ch, nw, c->pcg_retire);
   CHK(upload_nosync(c, c->pcg_eta, eta_s.data(), sizeof(float) * nb));
-  CHK(copy_dev(c, c->live, c->list_a, sizeof(int) * na));
+  CHK(copy_dev(c, c->live0, c->list_a, sizeof(int) * na));
   PcgCtl h0{};
   h0.nlive = na;
   CHK(upload_nosync(c, c->pcgctl, &h0, sizeof(PcgCtl)));
@@ -912,30 +898,30 @@ static int solve_split(pgpfa_ctx* c, Chunk& ch, NewtonState& nw) {
   c->live_gemms.clear();
   for (int it = 0; it < c->pcg_inner_max; ++it) {
     c->live_gemm_collect = (it == 0);
-    CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, skip, c->live, na));
+    CHK(prior_mv_all(c, nb, c->Pv, c->Qv, nullptr, skip, c->live0, na));
     dispatch_pw(p, [&](auto pw) {
       constexpr int PW = decltype(pw)::value;
       if constexpr (PW <= 16) {
         if (c->pcg_w32)
           hipLaunchKernelGGL(pcg_hessvec32_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W32, sW32, c->Pv, c->Qv, ld, T, p,
-                             c->live, c->sc_pq, skip, (const PcgCtl*)c->pcgctl);
+                             c->live0, c->sc_pq, skip, (const PcgCtl*)c->pcgctl);
         else
           hipLaunchKernelGGL(pcg_hessvec_dot_kernel<PW>, dim3(ntile, na), dim3(256), 0, c->st, c->W, (long long)T * p * p, c->Pv, c->Qv,
-                             ld, T, p, c->live, c->sc_pq, (const int*)&c->pcgctl->nlive);
+                             ld, T, p, c->live0, c->sc_pq, (const int*)&c->pcgctl->nlive);
         hipLaunchKernelGGL(pcg_xr_apply_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Dl, c->Rv, c->Pv, c->Qv, c->Xt, ld, T, p,
-                           c->live, na, c->sc_rz, c->sc_pq, ntile, skip, (const PcgCtl*)c->pcgctl);
+                           c->live0, na, c->sc_rz, c->sc_pq, ntile, skip, (const PcgCtl*)c->pcgctl);
       }
     });
-    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, c->live, na));
+    CHK(shared_solve(c, nb, c->Rv, c->Zv, skip, false, false, c->live0, na));
     dispatch_pw(p, [&](auto pw) {
       constexpr int PW = decltype(pw)::value;
       if constexpr (PW <= 16)
-        hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->live,
+        hipLaunchKernelGGL(pcg_apply2_dots_kernel<PW>, gbin, dim3(256), 0, c->st, c->Gbar, c->Rv, c->Xt, c->eps, c->Zv, ld, T, p, c->live0,
                            na, c->sc_part2, skip, (const PcgCtl*)c->pcgctl);
     });
-    hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->live, c->sc_part2, ntile,
+    hipLaunchKernelGGL(pcg_update_p2_kernel, dim3(na), dim3(256), 0, c->st, c->Zv, c->Pv, ld, nvec, c->live0, c->sc_part2, ntile,
                        c->sc_rz, c->sc_rr, c->sc_rr0, 0, c->pcgctl, c->pcg_ratio);
-    hipLaunchKernelGGL(pcg_check_kernel, dim3(1), dim3(256), 0, c->st, c->pcgctl, (volatile int*)c->d_hpcg, c->live,
+    hipLaunchKernelGGL(pcg_check_kernel, dim3(1), dim3(256), 0, c->st, c->pcgctl, (volatile int*)c->d_hpcg, c->live0,
                        (const float*)c->pcg_ratio, (const float*)c->pcg_eta, c->pcg_inner_min);
     if (device_stopped(c, it, 3)) break;
   }
@@ -1543,9 +1529,7 @@ int pgpfa_get_log_evidence(pgpfa_ctx* c, int n, const int32_t* idx, double* out)
 
 int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, double* err_sum) {
   if (!c || !y_pred || !err_sum) return fail("null argument");
-  CHK(refuse_trial_lengths(c, "pgpfa_loo_predict"));
-  CHK(refuse_observed(c, "pgpfa_loo_predict"));
-  CHK(refuse_observed_bins(c, "pgpfa_loo_predict"));
+  CHK(refuse_tables(c, "pgpfa_loo_predict"));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   const int q = c->q, T = c->T;

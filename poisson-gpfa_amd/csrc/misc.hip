@@ -52,7 +52,7 @@ int pgpfa_count_moments(pgpfa_ctx* c, int n, const int32_t* idx, int64_t* sum, i
   }
   // (bins past a trial's length hold zero counts - they add nothing to the sums above - and are no samples)
   int64_t ns = 0;
-  for (int t : tr.v) ns += c->trial_len ? c->trial_len_h[t] : T;
+  for (int t : tr.v) ns += c->live.length(t);
   *n_samples = ns;
   return 0;
 }
@@ -62,9 +62,7 @@ int pgpfa_count_moments(pgpfa_ctx* c, int n, const int32_t* idx, int64_t* sum, i
 int pgpfa_generate(pgpfa_ctx* c, unsigned long long seed, int n, const int32_t* idx, double* X_out, uint8_t* Y_out) {
   if (!c) return fail("null context");
   if (!c->have_params) return fail("set_params has not been called");
-  CHK(refuse_trial_lengths(c, "pgpfa_generate"));
-  CHK(refuse_observed(c, "pgpfa_generate"));
-  CHK(refuse_observed_bins(c, "pgpfa_generate"));
+  CHK(refuse_tables(c, "pgpfa_generate"));
   if (c->T > 65536 || c->q > 65535) return fail("generator supports up to 65535 neurons and 65536 bins");
   HIPC(hipSetDevice(c->device));
   Trials tr;

@@ -198,6 +198,10 @@ __device__ __forceinline__ const unsigned long long* bin_words(const uint8_t* ob
 
 constexpr int PNC = 32;
 
+// Template state OBS of the kernels that read a missing-data table: none set, an observation table in `obs`, bit words of a per-bin table in `obs`
+// (an int and not an enum: the kernels' symbols carry the value)
+constexpr int OBS_NONE = 0, OBS_ROWS = 1, OBS_BINS = 2;
+
 // OBS: the instantiation launched while an observation table is set (pgpfa_set_observed); without one the kernel is the code it was (the narrow widths
 // sit at the scalar-register class of their occupancy, which a run-time test of one more pointer costs them)
 // OBS == 2: a per-bin table (bin_words): a wave holds one neuron and the workgroup 64 bins, so one scalar word covers a wave's entries

@@ -15,9 +15,9 @@ static int ensure_cdym(pgpfa_ctx* c) {
   const int q = c->q, p = c->p, ntr = (int)c->last_trials_h.size();
   const int nbk = std::max(1, std::min(1024, ntr));
   if (c->mfma && c->cd_mfma && p + 1 <= 16)
-    hipLaunchKernelGGL(cd_ym_mfma_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->trial_len, ntr, q, p, c->T, c->cdym_part);
+    hipLaunchKernelGGL(cd_ym_mfma_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->live.lengths(), ntr, q, p, c->T, c->cdym_part);
   else
-    hipLaunchKernelGGL(cd_ym_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->trial_len, ntr, q, p, c->T, c->cdym_part);
+    hipLaunchKernelGGL(cd_ym_kernel, dim3(nbk), dim3(256), 0, c->st, c->Y, c->Yhi, c->Xmode, c->last_trials, c->live.lengths(), ntr, q, p, c->T, c->cdym_part);
   hipLaunchKernelGGL(reduce_parts_kernel, dim3(((p + 1) * q + 31) / 32), dim3(256), 0, c->st, c->cdym_part, nbk, (p + 1) * q, c->cdym);
   HIPC(hipGetLastError());
   c->cdym_valid = true;
@@ -27,18 +27,11 @@ static int ensure_cdym(pgpfa_ctx* c) {
 // info key "last_cd_unobserved_neurons": neurons that no trial of the last E-step's list observes (their sums are exactly zero)
 static void note_cd_unobserved(pgpfa_ctx* c) {
   int none = 0;
-  if (c->binw) {                                            // per-bin table: a neuron without a live entry on the listed trials (lengths and the byte table are folded in)
-    for (int n = 0; n < c->q; ++n) {
-      bool seen = false;
-      for (size_t i = 0; i < c->last_trials_h.size() && !seen; ++i) seen = c->nlive_h[(size_t)c->last_trials_h[i] * c->q + n] != 0;
-      none += !seen;
-    }
-  } else if (c->obs)
-    for (int n = 0; n < c->q; ++n) {
-      bool seen = false;
-      for (size_t i = 0; i < c->last_trials_h.size() && !seen; ++i) seen = c->obs_h[(size_t)c->last_trials_h[i] * c->q + n] != 0;
-      none += !seen;
-    }
+  for (int n = 0; n < c->q; ++n) {
+    bool seen = false;
+    for (size_t i = 0; i < c->last_trials_h.size() && !seen; ++i) seen = c->live.seen(c->last_trials_h[i], n);
+    none += !seen;
+  }
   c->info["last_cd_unobserved_neurons"] = (double)none;
 }
 
@@ -48,9 +41,7 @@ static int cd_sweep(pgpfa_ctx* c) {
   const int len = (p + 2) * q;
   CdArgs a{};
   a.Y = c->Y; a.Yhi = c->Yhi; a.mean = c->Xmode; a.vsm = c->vsm; a.vec = c->vec;
-  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); a.len = c->trial_len; a.obs = c->obs;
-  const bool bins = c->binw != nullptr;                       // per-bin table: words of 64 bins in the same field, template state 2 (bin_words, model.h)
-  if (bins) a.obs = reinterpret_cast<const uint8_t*>(c->binw);
+  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); c->live.fill(a);
   a.part = c->cdpart; a.q = q; a.p = p; a.T = T; a.dbg = c->cd_debug;
   const double flops = (double)a.ntr * q * T * (2.0 * p * p + 8.0 * p);
   if (c->mfma && c->cd_mfma && p <= 10) {
@@ -64,9 +55,9 @@ static int cd_sweep(pgpfa_ctx* c) {
         const int tiles = (q + 15) / 16, groups = (tiles + 7) / 8, tpg = (tiles + groups - 1) / groups;
         nby = std::max(1, std::min(a.ntr * ntt, std::max(64, 512 / groups)));      // one resident workgroup per CU: about one round of blocks
         const int waves = 8;
-        if (bins) hipLaunchKernelGGL((mstep_cd_mfma_kernel<PW, 2>), dim3(nby, groups), dim3(64, waves), cd_mfma_lds_bytes<PW>(), c->st, a, tpg);
-        else if (a.obs) hipLaunchKernelGGL((mstep_cd_mfma_kernel<PW, true>), dim3(nby, groups), dim3(64, waves), cd_mfma_lds_bytes<PW>(), c->st, a, tpg);
-        else hipLaunchKernelGGL(mstep_cd_mfma_kernel<PW>, dim3(nby, groups), dim3(64, waves), cd_mfma_lds_bytes<PW>(), c->st, a, tpg);
+        dispatch_obs(c->live.state(), [&](auto ob) {
+          hipLaunchKernelGGL((mstep_cd_mfma_kernel<PW, decltype(ob)::value>), dim3(nby, groups), dim3(64, waves), cd_mfma_lds_bytes<PW>(), c->st, a, tpg);
+        });
       }
     });
     prof_end(c);
@@ -80,9 +71,9 @@ static int cd_sweep(pgpfa_ctx* c) {
   prof_begin(c, TAG_CD, flops);
   dispatch_pw(p, [&](auto pw) {
     constexpr int PW = decltype(pw)::value;
-    if (bins) hipLaunchKernelGGL((mstep_cd_kernel<PW, 2>), dim3((q + 63) / 64, nby), dim3(64, CdKy<PW>::v), 0, c->st, a);
-    else if (a.obs) hipLaunchKernelGGL((mstep_cd_kernel<PW, true>), dim3((q + 63) / 64, nby), dim3(64, CdKy<PW>::v), 0, c->st, a);
-    else hipLaunchKernelGGL(mstep_cd_kernel<PW>, dim3((q + 63) / 64, nby), dim3(64, CdKy<PW>::v), 0, c->st, a);
+    dispatch_obs(c->live.state(), [&](auto ob) {
+      hipLaunchKernelGGL((mstep_cd_kernel<PW, decltype(ob)::value>), dim3((q + 63) / 64, nby), dim3(64, CdKy<PW>::v), 0, c->st, a);
+    });
   });
   prof_end(c);
   hipLaunchKernelGGL(reduce_parts_kernel, dim3((len + 31) / 32), dim3(256), 0, c->st, c->cdpart, nby, len, c->cdout);
@@ -174,9 +165,7 @@ int pgpfa_mstep_cd_newton_pass(pgpfa_ctx* c, const double* vecCd, const double* 
   if (prior_center) CHK(upload_nosync(c, c->cdcenter, prior_center, (size_t)q * D * sizeof(double)));
   CdArgs a{};
   a.Y = c->Y; a.Yhi = c->Yhi; a.mean = c->Xmode; a.vsm = c->vsm; a.vec = c->vec;
-  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); a.len = c->trial_len; a.obs = c->obs;
-  const bool bins = c->binw != nullptr;                       // per-bin table: words of 64 bins in the same field, template state 2 (bin_words, model.h)
-  if (bins) a.obs = reinterpret_cast<const uint8_t*>(c->binw);
+  a.trials = c->last_trials; a.ntr = (int)c->last_trials_h.size(); c->live.fill(a);
   a.part = c->cdhpart; a.q = q; a.p = p; a.T = T; a.dbg = c->cd_debug;
   note_cd_unobserved(c);
   int nby = std::max(1, std::min(a.ntr * 4, 128));
@@ -190,35 +179,25 @@ int pgpfa_mstep_cd_newton_pass(pgpfa_ctx* c, const double* vecCd, const double* 
         const int ntt = (T + CdH<PW>::BT - 1) / CdH<PW>::BT;
         const int tiles = (q + 15) / 16, groups = (tiles + CDH_NW - 1) / CDH_NW, tpg = (tiles + groups - 1) / groups;
         nby = std::max(1, std::min(a.ntr * ntt, std::min(128, std::max(64, 512 / groups))));
-        // (per launch: the attribute belongs to the function object of the current device, and contexts of one process may sit on different devices)
-        if (bins) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mstep_cd_hess_mfma_kernel<PW, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        dispatch_obs(c->live.state(), [&](auto ob) {
+          constexpr int OBS = decltype(ob)::value;
+          // (per launch: the attribute belongs to the function object of the current device, and contexts of one process may sit on different devices)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mstep_cd_hess_mfma_kernel<PW, OBS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)cd_hess_mfma_lds_bytes<PW>());
-          hipLaunchKernelGGL((mstep_cd_hess_mfma_kernel<PW, 2>), dim3(nby, groups), dim3(64, CDH_NW), cd_hess_mfma_lds_bytes<PW>(), c->st, a, tpg);
-          return;
-        }
-        if (a.obs) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mstep_cd_hess_mfma_kernel<PW, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)cd_hess_mfma_lds_bytes<PW>());
-          hipLaunchKernelGGL((mstep_cd_hess_mfma_kernel<PW, true>), dim3(nby, groups), dim3(64, CDH_NW), cd_hess_mfma_lds_bytes<PW>(), c->st, a, tpg);
-          return;
-        }
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mstep_cd_hess_mfma_kernel<PW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)cd_hess_mfma_lds_bytes<PW>());
-        hipLaunchKernelGGL(mstep_cd_hess_mfma_kernel<PW>, dim3(nby, groups), dim3(64, CDH_NW), cd_hess_mfma_lds_bytes<PW>(), c->st, a, tpg);
+          hipLaunchKernelGGL((mstep_cd_hess_mfma_kernel<PW, OBS>), dim3(nby, groups), dim3(64, CDH_NW), cd_hess_mfma_lds_bytes<PW>(), c->st, a, tpg);
+        });
         return;
       }
     }
-    if constexpr (PW <= 12) {
-      if (bins) hipLaunchKernelGGL((mstep_cd_hess_kernel<PW, 2>), dim3((q + 63) / 64, nby), dim3(64, CDH_KY), 0, c->st, a);
-      else if (a.obs) hipLaunchKernelGGL((mstep_cd_hess_kernel<PW, true>), dim3((q + 63) / 64, nby), dim3(64, CDH_KY), 0, c->st, a);
-      else hipLaunchKernelGGL(mstep_cd_hess_kernel<PW>, dim3((q + 63) / 64, nby), dim3(64, CDH_KY), 0, c->st, a);
-    } else {
-      constexpr int NG = CdGroups<PW>::NG;               // Hessian rows dealt to NG row groups (blockIdx.z)
-      if (bins) hipLaunchKernelGGL((mstep_cd_hess_rows_kernel<PW, NG, 2>), dim3((q + 63) / 64, nby, NG), dim3(64, CDH_KY), 0, c->st, a);
-      else if (a.obs) hipLaunchKernelGGL((mstep_cd_hess_rows_kernel<PW, NG, true>), dim3((q + 63) / 64, nby, NG), dim3(64, CDH_KY), 0, c->st, a);
-      else hipLaunchKernelGGL((mstep_cd_hess_rows_kernel<PW, NG>), dim3((q + 63) / 64, nby, NG), dim3(64, CDH_KY), 0, c->st, a);
-    }
+    dispatch_obs(c->live.state(), [&](auto ob) {
+      constexpr int OBS = decltype(ob)::value;
+      if constexpr (PW <= 12) {
+        hipLaunchKernelGGL((mstep_cd_hess_kernel<PW, OBS>), dim3((q + 63) / 64, nby), dim3(64, CDH_KY), 0, c->st, a);
+      } else {
+        constexpr int NG = CdGroups<PW>::NG;               // Hessian rows dealt to NG row groups (blockIdx.z)
+        hipLaunchKernelGGL((mstep_cd_hess_rows_kernel<PW, NG, OBS>), dim3((q + 63) / 64, nby, NG), dim3(64, CDH_KY), 0, c->st, a);
+      }
+    });
   });
   prof_end(c);
   hipLaunchKernelGGL(reduce_parts_kernel, dim3((NH * q + 31) / 32), dim3(256), 0, c->st, c->cdhpart, nby, NH * q, c->cdhout);

@@ -171,7 +171,7 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
     if (want_counts) {
       HIPC(hipMemsetAsync(dOver, 0, sizeof(int) * nb, c->st));
       PsCountP cp{};
-      cp.X = dX; cp.C = c->C; cp.d = c->d; cp.len = c->trial_len; cp.trial_of_slot = c->trial_of_slot;
+      cp.X = dX; cp.C = c->C; cp.d = c->d; cp.len = c->live.lengths(); cp.trial_of_slot = c->trial_of_slot;
       cp.Y = dY; cp.csum = a.count_sum ? dCs : nullptr; cp.over = dOver;
       cp.S = S; cp.q = q; cp.p = p; cp.T = T; cp.seed = a.seed;
       hipLaunchKernelGGL(psample_counts_kernel, dim3((unsigned)S, nb), dim3(256), 0, c->st, cp);

@@ -81,7 +81,7 @@ int pgpfa_posterior_rates(pgpfa_ctx* c, int n, const int32_t* idx, const int32_t
   if (group_count) {                                          // integers of the two host tables
     std::fill(group_count, group_count + (size_t)n_groups * T, 0);
     for (int i = 0; i < N; ++i) {
-      const int Tr = c->trial_len ? c->trial_len_h[tr.v[i]] : T;
+      const int Tr = c->live.length(tr.v[i]);
       for (int t = 0; t < Tr; ++t) ++group_count[(size_t)group[i] * T + t];
     }
   }
@@ -138,7 +138,7 @@ int pgpfa_posterior_rates(pgpfa_ctx* c, int n, const int32_t* idx, const int32_t
   HIPC(hipMemcpyAsync(d_trial, tr.v.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->st));
 
   RatesP a{};
-  a.Xmode = c->Xmode; a.vsm = c->vsm; a.tbl = c->rates_tbl; a.d = c->d; a.Y = c->Y; a.Yhi = c->Yhi; a.len = c->trial_len;
+  a.Xmode = c->Xmode; a.vsm = c->vsm; a.tbl = c->rates_tbl; a.d = c->d; a.Y = c->Y; a.Yhi = c->Yhi; a.len = c->live.lengths();
   a.ptrial = d_trial; a.ipos = d_pos;
   a.eta = d_eta; a.var = d_var; a.ellp = d_ellp; a.gsum = d_gsum;
   a.q = q; a.p = p; a.T = T; a.P4 = P4; a.KS = KS; a.qpad = qpad; a.nbt = nbt;

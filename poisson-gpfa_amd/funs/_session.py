@@ -367,6 +367,8 @@ class DeviceDualOptimRes(LazyTrialList):
 
 # ----------------------------------------------------------------------------------------------
 class Session:
+    lengths = observed = observed_bins = None                # no table set (what a session object made without __init__ sees too)
+
     def __init__(self, Y, p, bin_ms, lengths=None, observed=None):
         R, q, T = Y.shape
         self.R, self.q, self.T, self.p = R, q, T, p
@@ -476,15 +478,12 @@ class Session:
     def live_mask(self, trials):
         """Boolean (n, q*T) array over the padded dual variables of the listed trials: True where entry (neuron, bin) has a likelihood term - the bin
         lies inside the trial's own T_r bins and the neuron was recorded on the trial.  None when no table is set (every entry is live)."""
-        if self.lengths is None and getattr(self, 'observed', None) is None and getattr(self, 'observed_bins', None) is None:
+        if self.lengths is None and self.observed is None and self.observed_bins is None:
             return None
         trials = np.asarray(trials, dtype=np.int64)
-        live = np.ones((len(trials), self.q, self.T), dtype=bool)
-        if self.lengths is not None:
-            live &= (np.arange(self.T)[None, :] < self.lengths[trials][:, None])[:, None, :]
-        if self.observed is not None:
-            live &= self.observed[trials][:, :, None]
-        if getattr(self, 'observed_bins', None) is not None:
+        live = _inside(None if self.lengths is None else self.lengths[trials], None if self.observed is None else self.observed[trials],
+                       len(trials), self.q, self.T)
+        if self.observed_bins is not None:
             live &= self.observed_bins[trials]
         return live.reshape(len(trials), -1)
 
@@ -493,21 +492,16 @@ class Session:
         live = self.live_mask(np.arange(self.R))
         return np.ones((self.R, self.q, self.T), dtype=bool) if live is None else live.reshape(self.R, self.q, self.T)
 
-    def refuse_unequal(self, what):
-        """Entry points that do not know per-trial lengths must not run on padded data as if the padding were observed."""
-        if self.lengths is not None:
+    def refuse_tables(self, what, allow=()):
+        """Entry points must not run on a table they do not know as if its padding, zero-filled rows or zero-filled entries were data.  allow: the
+        tables `what` understands, of 'lengths', 'observed', 'observed_bins'."""
+        if self.lengths is not None and 'lengths' not in allow:
             raise NotImplementedError('%s does not support trials of unequal length yet (this experiment has %d..%d bins per trial); '
                                       'only the Laplace EM path does' % (what, int(self.lengths.min()), int(self.lengths.max())))
-
-    def refuse_unobserved(self, what):
-        """Entry points that do not know the observation table must not treat the zero-filled rows of unrecorded neurons as silence."""
-        if getattr(self, 'observed', None) is not None:
+        if self.observed is not None and 'observed' not in allow:
             raise NotImplementedError('%s does not support unobserved neurons yet (this experiment has %d unobserved (trial, neuron) pairs); '
                                       'only the Laplace EM path does' % (what, int((~self.observed).sum())))
-
-    def refuse_masked_bins(self, what):
-        """Entry points that do not know the per-bin table must not treat the zero-filled entries it marks as not recorded as counts of zero."""
-        if getattr(self, 'observed_bins', None) is not None:
+        if self.observed_bins is not None and 'observed_bins' not in allow:
             raise NotImplementedError('%s does not support a per-bin observation table yet (this experiment has %d entries marked as not recorded by '
                                       "'observedBins'); only the Laplace EM path does" % (what, int((~self.observed_bins).sum())))
 
@@ -548,6 +542,16 @@ def check_observed(observed, R, q):
     return np.ascontiguousarray(ob)
 
 
+def _inside(lengths, observed, R, q, T):
+    """Boolean (R, q, T) array: True at the bins inside the trials' lengths (None: all T) of the neurons the observation table (None: all) records."""
+    live = np.ones((R, q, T), dtype=bool)
+    if lengths is not None:
+        live &= (np.arange(T)[None, :] < np.asarray(lengths).reshape(-1)[:, None])[:, None, :]
+    if observed is not None:
+        live &= np.asarray(observed, dtype=bool)[:, :, None]
+    return live
+
+
 def compose_observed_bins(table, lengths, observed, R, q, T):
     """The per-bin table as a contiguous boolean (R, q, T) array, or None when it marks every entry inside the lengths (may be None) and the
     observation table (may be None) as recorded.  ValueError for a wrong shape, and for a trial or a neuron that the three tables together leave
@@ -556,11 +560,7 @@ def compose_observed_bins(table, lengths, observed, R, q, T):
     if ob.shape != (R, q, T):
         raise ValueError('per-bin table must have shape (trials, ydim, T) = (%d, %d, %d), got %s' % (R, q, T, ob.shape))
     ob = ob != 0
-    base = np.ones((R, q, T), dtype=bool)
-    if lengths is not None:
-        base &= (np.arange(T)[None, :] < np.asarray(lengths).reshape(-1)[:, None])[:, None, :]
-    if observed is not None:
-        base &= np.asarray(observed, dtype=bool)[:, :, None]
+    base = _inside(lengths, observed, R, q, T)
     if np.all(ob[base]):
         return None
     live = ob & base

@@ -509,10 +509,9 @@ def dualVariational(experiment, params, optimizeLogLambda=False, prevOptimRes=No
     import scipy.optimize as op
     sess, trial_idx = _prepare(experiment, params)
     masked = bool(DUAL_MASKED)
-    sess.refuse_masked_bins('dualVariational')              # (a per-bin table is outside DUAL_MASKED too)
+    sess.refuse_tables('dualVariational', allow=('lengths', 'observed'))     # (a per-bin table is outside DUAL_MASKED too)
     if not masked:
-        sess.refuse_unequal('dualVariational')
-        sess.refuse_unobserved('dualVariational')
+        sess.refuse_tables('dualVariational')
     sess.ctx.set_option('dual_masked', int(masked))
     n_all = len(trial_idx)
     local_shard = bool(getattr(experiment, '_pgpfa_local_shard', False))

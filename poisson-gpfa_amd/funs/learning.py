@@ -31,9 +31,7 @@ def _resident_session(infRes, experiment, xdim):
     sess, trial_idx = session_for(experiment, xdim)
     lo, hi = sess.local_slice(len(trial_idx))
     # (the padded bins of a short trial hold the prior conditional, which only the device's own E-step produces)
-    sess.refuse_unequal('an M-step on a posterior computed elsewhere')
-    sess.refuse_unobserved('an M-step on a posterior computed elsewhere')
-    sess.refuse_masked_bins('an M-step on a posterior computed elsewhere')
+    sess.refuse_tables('an M-step on a posterior computed elsewhere')
     pm = np.stack([np.asarray(infRes['post_mean'][i]) for i in range(lo, hi)])
     pv = np.stack([np.asarray(infRes['post_vsm'][i]) for i in range(lo, hi)])
     pg = np.stack([np.asarray(infRes['post_vsmGP'][i]) for i in range(lo, hi)])

@@ -17,9 +17,7 @@ def PosteriorMCMC(experiment, params, maxSampleIter, trial):
     xdim = C.shape[1]
     T = int(experiment.T)
     sess, trial_idx = inference._prepare(experiment, params)
-    sess.refuse_unequal('PosteriorMCMC')
-    sess.refuse_unobserved('PosteriorMCMC')
-    sess.refuse_masked_bins('PosteriorMCMC')
+    sess.refuse_tables('PosteriorMCMC')
     tr = trial_idx[np.asarray([trial])]
     # chol(K_big) is block diagonal: one T x T Cholesky factor per latent (mcmc.py:29)
     K = sess.ctx.gram()
@@ -81,9 +79,7 @@ def PosteriorMCMC_batch(experiment, params, maxSampleIter, trials, seeds):
     if len(seeds) != len(trials):
         raise ValueError('one seed per chain')
     sess, trial_idx = inference._prepare(experiment, params)
-    sess.refuse_unequal('PosteriorMCMC_batch')
-    sess.refuse_unobserved('PosteriorMCMC_batch')
-    sess.refuse_masked_bins('PosteriorMCMC_batch')
+    sess.refuse_tables('PosteriorMCMC_batch')
     dev = trial_idx[trials]
     K = sess.ctx.gram()
     chol = [np.linalg.cholesky(K[k]) for k in range(xdim)]

@@ -95,9 +95,7 @@ def leaveOneOutPrediction(params, experiment):
     from . import _session
     xdim = np.shape(params['C'])[1]
     sess, trial_idx = _session.session_for(experiment, xdim)
-    sess.refuse_unequal('leaveOneOutPrediction')
-    sess.refuse_unobserved('leaveOneOutPrediction')
-    sess.refuse_masked_bins('leaveOneOutPrediction')
+    sess.refuse_tables('leaveOneOutPrediction')
     lo, hi = (0, len(trial_idx)) if getattr(experiment, '_pgpfa_local_shard', False) else sess.local_slice(len(trial_idx))
     sess.set_params(params)
     y_loc, err_loc = sess.ctx.loo_predict(trial_idx[lo:hi])

@@ -302,10 +302,13 @@ def test_refusals_name_the_per_bin_table():
     bins[1, 2, 3] = False
     sess = _fake_session(3, 4, 6, bins=bins)
     with pytest.raises(NotImplementedError, match='per-bin'):
-        sess.refuse_masked_bins('dualVariational')
+        sess.refuse_tables('dualVariational')
+    with pytest.raises(NotImplementedError, match='per-bin'):
+        sess.refuse_tables('dualVariational', allow=('lengths', 'observed'))
+    sess.refuse_tables('dualVariational', allow=('observed_bins',))
     sess.observed_bins = None
-    sess.refuse_masked_bins('dualVariational')
-    object.__new__(_session.Session).refuse_masked_bins('anything')
+    sess.refuse_tables('dualVariational')
+    object.__new__(_session.Session).refuse_tables('anything')
 
 
 # ---- 3. moments, hold-out subset ------------------------------------------------------------------------------------------------------------------
@@ -403,4 +406,4 @@ def test_header_binding_and_library_agree_on_pgpfa_set_observed_bins():
     assert re.search(r'int\s+pgpfa_set_observed_bins\s*\(\s*pgpfa_ctx\s*\*\s*ctx\s*,\s*const\s+uint8_t\s*\*\s*live', header)
     assert 'pgpfa_set_observed_bins' in _hip.EXPORTED_SYMBOLS and hasattr(lib, 'pgpfa_set_observed_bins')
     assert '"observed_bins_set"' in header
-    assert hasattr(_hip.Context, 'set_observed_bins') and hasattr(_session.Session, 'refuse_masked_bins') and hasattr(util, 'binHoldout')
+    assert hasattr(_hip.Context, 'set_observed_bins') and hasattr(_session.Session, 'refuse_tables') and hasattr(util, 'binHoldout')

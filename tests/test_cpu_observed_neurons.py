@@ -98,11 +98,14 @@ def test_refusals_name_the_unobserved_neurons():
     table[1, 2] = False
     sess = _fake_session(table, None, 6)
     with pytest.raises(NotImplementedError, match='unobserved neurons'):
-        sess.refuse_unobserved('dualVariational')
+        sess.refuse_tables('dualVariational')
+    with pytest.raises(NotImplementedError, match='unobserved neurons'):
+        sess.refuse_tables('dualVariational', allow=('lengths', 'observed_bins'))
+    sess.refuse_tables('dualVariational', allow=('observed',))
     sess.observed = None
-    sess.refuse_unobserved('dualVariational')
+    sess.refuse_tables('dualVariational')
     plain = object.__new__(_session.Session)               # a session object made without __init__ (the fakes of the other CPU tests)
-    plain.refuse_unobserved('anything')
+    plain.refuse_tables('anything')
 
 
 def test_count_moments_under_a_table():

@@ -119,7 +119,7 @@ def test_equal_trials_get_the_device_arrays_unchanged():
     assert sess.lengths is None
     res = _session.DeviceInfRes(sess, np.arange(3, dtype=np.int32), (0, 3))
     assert res['post_mean'][1].shape == (2, 6) and res['post_cov'][2].shape == (12, 12) and res['post_vsmGP'][0].shape == (6, 6, 2)
-    sess.refuse_unequal('anything')                                 # no table, no refusal
+    sess.refuse_tables('anything')                                  # no table, no refusal
 
 
 def test_host_modes_of_a_trials_own_length_are_padded_with_zeros():
@@ -134,7 +134,10 @@ def test_host_modes_of_a_trials_own_length_are_padded_with_zeros():
     with pytest.raises(ValueError, match='trial 1 has 3 bins'):
         sess.pad_modes([1], [np.ones(p * 4)])
     with pytest.raises(NotImplementedError, match='trials of unequal length'):
-        sess.refuse_unequal('dualVariational')
+        sess.refuse_tables('dualVariational')
+    with pytest.raises(NotImplementedError, match='trials of unequal length'):
+        sess.refuse_tables('dualVariational', allow=('observed', 'observed_bins'))
+    sess.refuse_tables('dualVariational', allow=('lengths',))
 
 
 def test_header_binding_and_library_agree_on_the_new_entry_point():

@@ -807,3 +807,33 @@ def test_the_order_of_the_three_calls_does_not_matter():
     same2 = [np.array_equal(a, b) for a, b in zip(dropped, only)]
     print('orders l-o-b and b-o-l bit-identical: %s; lengths and observed dropped against never set: %s' % (same, same2))
     assert all(same) and all(same2)
+
+
+def test_an_upload_that_drops_the_lengths_rebuilds_the_bin_words_without_them():
+    """upload, lengths, bin table, the same counts again: the upload drops the lengths, and the bin words - built with the lengths folded in - must
+    lose them too: objective, modes and blocks bit-identical to a context that only ever had the bin table.  (Before the tables had one owner the words
+    kept the lengths while every reader of the length table saw T bins.)"""
+    from funs import _hip
+    params, Yr, bins, lens, observed, T, live, ref = _case('c1', ragged=True)
+    q, p = Yr[0].shape[0], 3
+    Y = padded_counts(Yr, live, T)
+    got = []
+    for with_lengths in (True, False):
+        ctx = _hip.Context(q, p, T, R8, BIN_MS)
+        try:
+            ctx.upload_counts(Y)
+            ctx.set_params(params['C'], params['d'], params['tau'])
+            if with_lengths:
+                ctx.set_trial_lengths(lens)
+            ctx.set_observed_bins(bins)
+            if with_lengths:
+                ctx.upload_counts(Y)
+            assert ctx.info('trial_lengths_set') == 0.0 and ctx.info('observed_bins_set') == 1.0
+            obj, _, st = ctx.estep_laplace()
+            assert np.all(st == 0)
+            got.append([np.array([obj]), ctx.post_mean(), ctx.post_vsm()])
+        finally:
+            ctx.close()
+    same = [np.array_equal(a, b) for a, b in zip(*got)]
+    print('re-upload under lengths + bin table against the bin table alone, bit-identical (objective, post_mean, post_vsm): %s' % same)
+    assert all(same)

@@ -172,6 +172,8 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * it was asked for stays within 256 MiB; > 0: that many trials per chunk.  No output depends on it, bit for bit - the group sums are carried from
  * chunk to chunk in list order; it exists for the tests of exactly that),
  * "sample_chunk_trials" (0 - the default: pgpfa_posterior_sample walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
+ * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
+ * "interp_chunk_trials" (0 - the default: pgpfa_posterior_at walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
 /* Options that pgpfa_set_params builds from - "eps_noise" (Gram matrices, their inverses, the low-rank factors), "lowrank_tol" (the low-rank
@@ -346,6 +348,34 @@ int pgpfa_posterior_sample(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
                            double*   X         /* [n][S][p][T] or NULL */,
                            uint16_t* Y         /* [n][S][q][T] or NULL */,
                            int32_t*  count_sum /* [n][S][q]    or NULL */);
+
+/* The latent posterior at arbitrary time points.  The Gaussian posterior N(m, Sigma) over the T grid times t_j = j bin_ms resident for trial
+ * r = idx[i] - the posterior being whatever is resident for the trial, as pgpfa_posterior_rates defines it - extends to any time s (ms from the
+ * trial's first bin) by the prior conditional of the GP.  Per latent k, with K_k the Gram matrix of pgpfa_get_gram and V_k = post_vsmGP[:, :, k]:
+ *   kx_k(s)[j]    = (1 - eps) exp(-1/2 (s - j bin)^2 / (1000 tau_k)^2) + eps [s == j bin]      (the white-noise term only AT a grid time)
+ *   a_k(s)        = K_k^-1 kx_k(s)
+ *   mean[i][k][s] = a_k(s) . m_k
+ *   var[i][k][s]  = 1 - a_k(s) . kx_k(s) + a_k(s)^T V_k a_k(s),  stored as max(., 0)
+ * At a grid time this is post_mean[k][j] and post_vsmGP[j][j][k]; off the grid it is the marginal of the model extended by s as a bin without a
+ * likelihood term; far from the trial mean -> 0 and var -> 1, the prior.  times_ms: any finite doubles - negative or beyond the last bin
+ * (extrapolation), unsorted, repeated -, one grid [S] for all listed trials or, with per_trial != 0, one grid [n][S] per list entry (event
+ * alignment: event_ms[r] + lags).  Trials of unequal length: the padded bins hold the prior conditional, so interpolating from all T bins equals
+ * interpolating the trial's own T_r-bin posterior from its own grid.  Only the marginals per latent are given: the cross-latent covariance at s
+ * needs the off-diagonal T x T blocks of Sigma, which are not resident.
+ * The posterior of an E-step is evaluated under the timescales of that E-step (restored around the call when the context has moved on, per
+ * (snapshot, kind of posterior) group as pgpfa_posterior_sample does); one uploaded with pgpfa_set_posterior under the current parameters.  Under
+ * the sum-only plan ("keep_trial_vsmgp" 0) the blocks of the listed trials are rebuilt on demand, as pgpfa_get_post_vsmgp does.
+ * A trial's result does not depend on its position in the list, on which other trials are listed or on how the list is cut into chunks (option
+ * "interp_chunk_trials"), bit for bit; a trial listed twice gives the same numbers twice.  No floating-point atomics.
+ * Fails, naming what is wrong: S < 1; both outputs NULL; a time that is not finite, naming its position; set_params not called; a trial without a
+ * posterior - no E-step, pgpfa_dual_finalize or pgpfa_set_posterior has written one since its counts were uploaded -, naming the trial; a
+ * variational posterior of a trial shorter than T (its jitter comes from the trial's own T_r-bin Gram inverse, for which the padded-grid identity
+ * is not established: refused rather than approximated); an asynchronous timescale pass in flight.
+ * Leaves untouched: post_mean, post_vsm, post_vsmGP and their resident marks, the sums pgpfa_mstep_precomp reads, mode serials, snapshots, log
+ * evidence, the resident counts and the three missing-data tables.  Uses the chunk workspace as pgpfa_get_post_vsmgp does when blocks are rebuilt. */
+int pgpfa_posterior_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                       int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
+                       double* mean /* [n][p][S] or NULL */, double* var /* [n][p][S] or NULL */);
 
 /* ---- M-step ----------------------------------------------------------------------- */
 /* MStepObservationCost(_grad) (learning.py:20-91) over the trials of the last E-step /

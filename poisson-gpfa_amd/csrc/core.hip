@@ -1103,6 +1103,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "dual_masked") { if (v != 0.0 && v != 1.0) return fail("dual_masked is 0 or 1"); c->dual_masked = (int)v; }
   else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
   else if (k == "sample_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("sample_chunk_trials is a count of trials, or 0"); c->sample_chunk = (int)v; }
+  else if (k == "interp_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("interp_chunk_trials is a count of trials, or 0"); c->interp_chunk = (int)v; }
   else if (k == "rates_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("rates_chunk_trials is a count of trials, or 0"); c->rates_chunk = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);

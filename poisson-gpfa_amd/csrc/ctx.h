@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, workspace, copies; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -324,6 +324,7 @@ struct pgpfa_ctx {
   double* rates_tbl = nullptr; double rates_tbl_params = -1.0;
   int rates_chunk = 0;                            // trials per chunk of a call (0: from the 256 MiB bound on the staging of the per-trial planes)
   int sample_chunk = 0;                           // option sample_chunk_trials: the same for pgpfa_posterior_sample (psample.hip); no output depends on it
+  int interp_chunk = 0;                           // option interp_chunk_trials: the same for pgpfa_posterior_at (interp.hip); no output depends on it
 };
 
 template <typename T>

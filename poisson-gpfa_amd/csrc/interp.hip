@@ -1,0 +1,187 @@
+// libpgpfa_hip.so - interp.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): the latent posterior at arbitrary time
+// points (pgpfa_posterior_at)
+#include "ctx.h"
+#include "interp.h"
+
+using namespace pgpfa;
+
+namespace {
+
+constexpr size_t INTERP_STAGE_BYTES = (size_t)256 << 20;     // bound on the device staging of one chunk (per-trial cross Grams, weights, results)
+constexpr size_t INTERP_LDS_MAX = (size_t)160 << 10;          // LDS of a CU: the row panel of interp_var_kernel has to fit
+constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
+
+struct DevBufs {                                              // scratch of one call: freed on every way out
+  std::vector<void*> v;
+  ~DevBufs() { for (void* p : v) hipFree(p); }
+  template <typename T> int get(T** out, size_t count) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail("pgpfa_posterior_at: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
+    v.push_back(p);
+    *out = reinterpret_cast<T*>(p);
+    return 0;
+  }
+};
+
+struct MarkKeeper {                                           // the resident marks of post_vsmGP are what they were when the call returns
+  pgpfa_ctx* c;
+  std::vector<std::pair<int, char>> saved;
+  ~MarkKeeper() { for (auto& kv : saved) c->vsmgp_ok[kv.first] = kv.second; }
+};
+
+struct AtArgs {
+  const std::vector<int>* trials;     // trial of every list position
+  int S; const double* times; bool per_trial;
+  double* mean; double* var;
+};
+
+// kx and A = Kinv kx of `grids` time grids whose times are on the device
+int weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A) {
+  const int p = c->p, T = c->T;
+  hipLaunchKernelGGL(interp_cross_kernel, dim3(T16, p, grids), dim3(256), 0, c->st, d_times, c->tau, c->bin, c->eps, T, T16, S, Spad, p, kx);
+  HIPC(hipGetLastError());
+  // A[t][s] = sum_u Kinv[t][u] kx[u][s]: column-major C (Spad x T, ld Spad) = kx (Spad x T16) Kinv^T.  Kinv is the identity in its padding and the
+  // rows u >= T of kx are zero.  The batch is declared as the low half of a two-level one (latents below, grids above) and the tile is fixed, which
+  // keeps the launch off the split-K path: the bits of a trial's weights must not follow the number of grids in a chunk.
+  const long long slab = (long long)T16 * Spad;
+  GemmP g{};
+  g.A = kx; g.sA = slab; g.lda = Spad;
+  g.B = c->Kinv; g.sB = (long long)c->Tp * c->Tp; g.ldb = c->Tp;
+  g.C = A; g.sC = slab; g.ldc = Spad;
+  g.M = Spad; g.N = T; g.K = T16; g.alpha = 1.0; g.beta = 0.0;
+  g.slots = nullptr; g.nb_lo = p; g.nbatch = p * grids; g.sA_hi = (long long)p * slab; g.sB_hi = 0; g.sC_hi = (long long)p * slab;
+  g.mode = GEMM_FULL; g.kflags = 0; g.bm = 64;
+  return gemm(c, false, g);
+}
+
+// the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
+int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
+  const int p = c->p, T = c->T, S = a.S;
+  const int T4 = round_up(T, 4), T16 = round_up(T, 16), Spad = round_up(S, 16), VS = interp_row_stride(T4);
+  const size_t lds = ((size_t)16 * VS + std::min(Spad, INTERP_SBLK)) * sizeof(double);
+  if (a.var && lds > INTERP_LDS_MAX) return fail("pgpfa_posterior_at: a row panel of %d bins does not fit the LDS of a compute unit (%zu bytes)", T, lds);
+  const int N = (int)pos.size();
+  std::vector<int> tos(N);
+  for (int i = 0; i < N; ++i) tos[i] = (*a.trials)[pos[i]];
+
+  DevBufs dev;
+  MarkKeeper keep{c, {}};
+  if (a.var) {
+    CHK(ensure_vsmgp_buffer(c));
+    // blocks rebuilt on demand under the sum-only plan (same snapshot, so no parameter switch).  The rebuild also rewrites post_vsm of those trials
+    // - by another kernel than the sum-only E-step, so not to the bit: their post_vsm is set aside and put back, and so are the resident marks
+    std::vector<int> rebuilt;
+    for (int t : tos) {
+      keep.saved.emplace_back(t, c->vsmgp_ok[t]);
+      if (!c->vsmgp_ok[t] && std::find(rebuilt.begin(), rebuilt.end(), t) == rebuilt.end()) rebuilt.push_back(t);
+    }
+    if (!rebuilt.empty()) {
+      const size_t lv = (size_t)T * p * p;
+      double* d_vsm = nullptr;
+      CHK(dev.get(&d_vsm, rebuilt.size() * lv));
+      for (size_t i = 0; i < rebuilt.size(); ++i)
+        HIPC(hipMemcpyAsync(d_vsm + i * lv, c->vsm + (size_t)rebuilt[i] * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+      const int rc = ensure_trial_vsmgp(c, tos);
+      for (size_t i = 0; i < rebuilt.size(); ++i)
+        HIPC(hipMemcpyAsync(c->vsm + (size_t)rebuilt[i] * lv, d_vsm + i * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+      CHK(rc);
+    }
+  }
+
+  // chunks of the group: device staging per trial
+  const size_t slab = (size_t)p * T16 * Spad;
+  const size_t per_trial = ((a.mean ? 1 : 0) + (a.var ? 1 : 0)) * (size_t)p * Spad * sizeof(double) + (a.per_trial ? (2 * slab + S) * sizeof(double) : 0);
+  int chunk = N;
+  if (c->interp_chunk > 0) chunk = std::min(N, c->interp_chunk);
+  else chunk = (int)std::min<size_t>((size_t)N, std::max<size_t>(1, INTERP_STAGE_BYTES / per_trial));
+  const int grids = a.per_trial ? chunk : 1;
+
+  double *d_times = nullptr, *d_kx = nullptr, *d_A = nullptr, *d_mean = nullptr, *d_var = nullptr;
+  int* d_trial = nullptr;
+  CHK(dev.get(&d_times, (size_t)grids * S));
+  CHK(dev.get(&d_kx, (size_t)grids * slab + GEMM_ROW_SLACK));
+  CHK(dev.get(&d_A, (size_t)grids * slab + GEMM_ROW_SLACK));
+  CHK(dev.get(&d_trial, (size_t)N));
+  if (a.mean) CHK(dev.get(&d_mean, (size_t)chunk * p * Spad));
+  if (a.var) CHK(dev.get(&d_var, (size_t)chunk * p * Spad));
+  HIPC(hipMemsetAsync(d_kx, 0, ((size_t)grids * slab + GEMM_ROW_SLACK) * sizeof(double), c->st));
+  HIPC(hipMemsetAsync(d_A, 0, ((size_t)grids * slab + GEMM_ROW_SLACK) * sizeof(double), c->st));     // rows t >= T stay zero for the whole call
+  HIPC(hipMemcpyAsync(d_trial, tos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->st));
+  if (!a.per_trial) {
+    HIPC(hipMemcpyAsync(d_times, a.times, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->st));
+    CHK(weights(c, d_times, 1, S, Spad, T16, d_kx, d_A));   // once per snapshot group, not per trial
+  }
+  if (a.var && lds > ((size_t)48 << 10))
+    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(interp_var_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+
+  InterpP k{};
+  k.vsmgp = c->vsmgp; k.Xmode = c->Xmode; k.A = d_A; k.kx = d_kx; k.mean = d_mean; k.var = d_var;
+  k.sG = a.per_trial ? (long long)slab : 0;
+  k.p = p; k.T = T; k.T4 = T4; k.T16 = T16; k.Spad = Spad; k.VS = VS;
+  std::vector<double> h_times;
+  for (int c0 = 0; c0 < N; c0 += chunk) {
+    const int nc = std::min(chunk, N - c0);
+    if (a.per_trial) {
+      h_times.resize((size_t)nc * S);
+      for (int i = 0; i < nc; ++i) std::copy(a.times + (size_t)pos[c0 + i] * S, a.times + (size_t)(pos[c0 + i] + 1) * S, h_times.begin() + (size_t)i * S);
+      HIPC(hipMemcpyAsync(d_times, h_times.data(), h_times.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
+      CHK(weights(c, d_times, nc, S, Spad, T16, d_kx, d_A));
+    }
+    k.ptrial = d_trial + c0;
+    if (a.mean) hipLaunchKernelGGL(interp_mean_kernel, dim3((Spad + 255) / 256, p, nc), dim3(256), 0, c->st, k);
+    if (a.var) hipLaunchKernelGGL(interp_var_kernel, dim3((Spad + INTERP_SBLK - 1) / INTERP_SBLK, p, nc), dim3(256), lds, c->st, k);
+    HIPC(hipGetLastError());
+    // results of the chunk, by list position
+    for (int i = 0; i < nc; ++i) {
+      const size_t ps = (size_t)pos[c0 + i];
+      if (a.mean)
+        HIPC(hipMemcpy2DAsync(a.mean + ps * p * S, (size_t)S * sizeof(double), d_mean + (size_t)i * p * Spad, (size_t)Spad * sizeof(double), (size_t)S * sizeof(double), p,
+                              hipMemcpyDeviceToHost, c->st));
+      if (a.var)
+        HIPC(hipMemcpy2DAsync(a.var + ps * p * S, (size_t)S * sizeof(double), d_var + (size_t)i * p * Spad, (size_t)Spad * sizeof(double), (size_t)S * sizeof(double), p,
+                              hipMemcpyDeviceToHost, c->st));
+    }
+    HIPC(hipStreamSynchronize(c->st));                         // the staging is reused by the next chunk
+    HIPC(hipGetLastError());
+  }
+  return 0;
+}
+
+}  // namespace
+
+int pgpfa_posterior_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, const double* times_ms, int per_trial, double* mean, double* var) {
+  if (!c) return fail("null context");
+  if (S < 1) return fail("pgpfa_posterior_at: S = %d, at least one query time is needed", S);
+  if (!mean && !var) return fail("pgpfa_posterior_at: no output asked for (mean and var are both NULL)");
+  if (!times_ms) return fail("pgpfa_posterior_at: times_ms is NULL");
+  Trials tr;
+  CHK(resolve_trials(c, n, idx, &tr));
+  const int N = (int)tr.v.size();
+  for (int i = 0; i < (per_trial ? N : 1); ++i)
+    for (int s = 0; s < S; ++s)
+      if (!std::isfinite(times_ms[(size_t)i * S + s])) {
+        if (per_trial) return fail("pgpfa_posterior_at: query time %d of list entry %d (trial %d) is not finite", s, i, tr.v[i]);
+        return fail("pgpfa_posterior_at: query time %d is not finite", s);
+      }
+  if (!c->have_params) return fail("set_params has not been called");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  // a posterior is resident for a trial as pgpfa_posterior_rates defines it
+  for (int t : tr.v)
+    if (c->mode_serial[t] < 0 && c->trial_snap[t] < 0 && !c->vsmgp_ok[t])
+      return fail("no posterior for trial %d: neither an E-step nor pgpfa_set_posterior has written one since its counts were uploaded", t);
+  for (int t : tr.v)
+    if (c->trial_dual[t] && c->live.length(t) < c->T)
+      return fail("the variational posterior of trial %d covers %d of %d bins: its jitter comes from the trial's own %d-bin Gram inverse, so the padded grid "
+                  "does not carry its prior conditional; pgpfa_posterior_at refuses rather than approximates", t, c->live.length(t), c->T, c->live.length(t));
+  AtArgs a{};
+  a.trials = &tr.v; a.S = S; a.times = times_ms; a.per_trial = per_trial != 0; a.mean = mean; a.var = var;
+  std::map<std::pair<int, int>, std::vector<int>> groups;     // positions by (snapshot, kind of posterior), as ensure_trial_vsmgp groups its rebuilds
+  for (size_t i = 0; i < tr.v.size(); ++i) groups[std::make_pair(c->trial_snap[tr.v[i]], (int)c->trial_dual[tr.v[i]])].push_back((int)i);
+  for (auto& kv : groups) {
+    const std::vector<int>& pos = kv.second;
+    CHK(with_snapshot(c, kv.first.first, [&]() { return at_group(c, a, pos); }));
+  }
+  return 0;
+}

@@ -47,6 +47,7 @@ _SIGNATURES = {
     'pgpfa_set_posterior': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_rates': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p],
     'pgpfa_posterior_sample': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p, ct.POINTER(ct.c_uint16), c_int32_p],
+    'pgpfa_posterior_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p],
     'pgpfa_rates_group_csr': [ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_int, c_int32_p, c_int32_p],
     'pgpfa_mstep_cd_costgrad': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p],
     'pgpfa_mstep_cd_newton_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
@@ -409,6 +410,29 @@ class Context:
         check(self.lib.pgpfa_posterior_sample(self.h, n, iptr(ii), S, ct.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), None if zin is None else dptr(zin),
                                               dptr(out['noise']) if 'noise' in out else None, dptr(out['x']) if 'x' in out else None,
                                               None if y is None else y.ctypes.data_as(ct.POINTER(ct.c_uint16)), iptr(out.get('count_sum'))))
+        return out
+
+    def posterior_at(self, times, idx=None, want=('mean', 'var')):
+        """Marginal posterior of every latent of the listed trials (repeats allowed) at arbitrary times in ms from the trial's first bin
+        (include/pgpfa.h: pgpfa_posterior_at).  times: (S,) - one grid for all listed trials - or (n, S), one grid per list entry.  want: 'mean'
+        and / or 'var', each [n][p][S].  Returns a dict of exactly the arrays asked for."""
+        n, ii = self._n_idx(idx)
+        unknown = set(want) - {'mean', 'var'}
+        if unknown:
+            raise ValueError('unknown output(s) %s' % sorted(unknown))
+        if not want:
+            raise ValueError('no output asked for')
+        tt = as_f64(times)
+        if tt.ndim == 1:
+            per_trial = 0
+        elif tt.ndim == 2 and tt.shape[0] == n:
+            per_trial = 1
+        else:
+            raise ValueError('times must have shape (S,) or (n, S) = (%d, S), got %s' % (n, tt.shape))
+        S = tt.shape[-1]
+        out = {k: np.empty((n, self.p, S)) for k in ('mean', 'var') if k in want}
+        check(self.lib.pgpfa_posterior_at(self.h, n, iptr(ii), S, dptr(tt), per_trial, dptr(out['mean']) if 'mean' in out else None,
+                                          dptr(out['var']) if 'var' in out else None))
         return out
 
     # -- dual variational ---------------------------------------------------------------------

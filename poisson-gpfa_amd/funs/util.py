@@ -285,6 +285,92 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
     return out
 
 
+_AT_KEYS = ('mean', 'var', 'lower', 'upper')
+
+
+def _condition_means_at(mean, times, group, n_groups, spans):
+    """Condition averages of per-trial trajectories on a common axis, on the host and in list order (so the result is reproducible):
+    trial i enters group[i]'s average at query time s only where 0 <= s <= spans[i], its own recorded span.  mean: (n, xdim, S); times: (S,)
+    or (n, S).  Returns (condition_mean (G, xdim, S) - 0 where no trial has the time -, condition_count (G, S))."""
+    n, xdim, S = mean.shape
+    tt = np.broadcast_to(times, (n, S))
+    total = np.zeros((n_groups, xdim, S))
+    count = np.zeros((n_groups, S), dtype=np.int32)
+    for i in range(n):
+        inside = (tt[i] >= 0.0) & (tt[i] <= spans[i])
+        total[group[i]] += np.where(inside[None, :], mean[i], 0.0)
+        count[group[i]] += inside
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(count[:, None, :] > 0, total / count[:, None, :], 0.0), count
+
+
+def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=None, level=0.95, want=('mean', 'lower', 'upper')):
+    """The latent trajectories of the listed trials at arbitrary time points, with a credible band: the GP posterior over the bin grid extended
+    to any time by the prior conditional (pgpfa_posterior_at; the reference hands the posterior out on the grid only).  Three uses: a trajectory
+    aligned to an event that falls at another time in every trial, a finely sampled trajectory for a figure, and condition means on a common axis
+    over trials of unequal length.  post_vsmGP never comes to the host.
+
+    times: ms from a trial's first bin (bin j sits at j * binSize), any finite values - before the first or beyond the last bin extrapolates, far
+    away gives the prior (mean 0, variance 1).  A 1-D array is one grid for all listed trials; a 2-D (n, S) array gives every listed trial its own
+    grid (event alignment: event_ms[r] + lags).
+    infRes None: one Laplace E-step at `params` over the experiment first.  A DeviceInfRes of this experiment's session whose entries are still
+    the resident ones: that posterior, evaluated under the timescales of the E-step that produced it.  Anything else raises ValueError.
+    trials: positions in experiment.data (None: all; repeats allowed).  conditions: one integer label per listed trial.
+    want: any of 'mean', 'var' (marginal posterior mean and variance of every latent), 'lower' / 'upper' (mean -+ z sqrt(var), the central
+    `level` band).  Returns a dict of the asked keys as (n, xdim, S) arrays plus 'times'; with `conditions` also 'condition_mean' (G, xdim, S) -
+    the mean over the condition's trials of the posterior mean, a trial entering at s only inside its own recorded span 0 <= s <= (T_r - 1)
+    binSize; 0 where no trial has the time -, 'condition_count' (G, S) and 'condition_labels' (G)."""
+    from . import _session, inference
+    want = tuple(want)
+    unknown = [k for k in want if k not in _AT_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_AT_KEYS)))
+    z = _band_z(level)
+    tt = np.asarray(times, dtype=np.float64)
+    tt = np.ascontiguousarray(tt) if tt.ndim else tt            # (ascontiguousarray would turn a scalar into a grid of one time)
+    if tt.ndim not in (1, 2) or tt.shape[-1] < 1:
+        raise ValueError('times: shape (S,) or (n, S) with S >= 1 expected, got %s' % (tt.shape,))
+    if not np.all(np.isfinite(tt)):                    # (before the session is touched: nothing reaches the device)
+        raise ValueError('times: entry %s is not finite' % (tuple(int(i) for i in np.argwhere(~np.isfinite(tt))[0]),))
+    xdim = np.shape(params['C'])[1]
+    sess, trial_idx = _session.session_for(experiment, xdim)
+    if sess.comm_ready:
+        raise NotImplementedError('posteriorAt does not support sharded sessions: every rank holds the posterior of its own trials only')
+    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
+    if idx.size == 0:
+        raise ValueError('empty trial list')
+    if tt.ndim == 2 and tt.shape[0] != idx.size:
+        raise ValueError('times: one grid per listed trial expected, (%d, S), got %s' % (idx.size, tt.shape))
+    labels, group = (None, None) if conditions is None else _condition_groups(conditions, idx.size)
+    if not want and labels is None:
+        raise ValueError('nothing asked for: want is empty and there are no conditions')
+    if infRes is None:
+        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
+    else:
+        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
+            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
+        covered = set(infRes.trial_idx.tolist())
+        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
+        if stale:
+            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
+        sess.set_params({'C': params['C'], 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+    need_var = any(k in want for k in ('var', 'lower', 'upper'))
+    need_mean = labels is not None or any(k in want for k in ('mean', 'lower', 'upper'))
+    dev = sess.ctx.posterior_at(tt, idx, want=(('mean',) if need_mean else ()) + (('var',) if need_var else ()))
+    out = {'times': tt}
+    sd = np.sqrt(dev['var']) if ('lower' in want or 'upper' in want) else None
+    made = {'mean': lambda: dev['mean'], 'var': lambda: dev['var'], 'lower': lambda: dev['mean'] - z * sd, 'upper': lambda: dev['mean'] + z * sd}
+    for k in want:
+        out[k] = made[k]()
+    if labels is not None:
+        binSize = float(experiment.binSize)
+        spans = [((sess.T if sess.lengths is None else int(sess.lengths[int(t)])) - 1) * binSize for t in idx]
+        out['condition_mean'], out['condition_count'] = _condition_means_at(dev['mean'], tt, group, len(labels), spans)
+        out['condition_labels'] = labels
+    return out
+
+
 # -- co-smoothing: held-out neurons predicted from the others -------------------------------------------------
 def coSmoothing(params, experiment, heldOut, trials=None):
     """Predict the neurons `heldOut` on the listed trials from the trials' other neurons and score the prediction: the held-out neurons are

@@ -1040,6 +1040,11 @@ int pgpfa_destroy(pgpfa_ctx* c) {
 int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   if (!c || !key) return fail("null argument");
   const std::string k(key);
+  auto chunk_trials = [&](int* field) -> int {              // the three *_chunk_trials options of the posterior queries
+    if (v < 0.0 || v != std::floor(v)) return fail("%s is a count of trials, or 0", key);
+    *field = (int)v;
+    return 0;
+  };
   if (k == "newton_xtol") c->xtol = v;
   else if (k == "newton_max_iter") c->max_iter = (int)v;
   else if (k == "use_mfma") {
@@ -1102,9 +1107,9 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "laplace_f32") { if (v != 0.0 && v != 1.0 && v != 2.0) return fail("laplace_f32 is 0, 1 or 2"); c->laplace_f32 = (int)v; }
   else if (k == "dual_masked") { if (v != 0.0 && v != 1.0) return fail("dual_masked is 0 or 1"); c->dual_masked = (int)v; }
   else if (k == "laplace_evidence") { if (v != 0.0 && v != 1.0) return fail("laplace_evidence is 0 or 1"); c->laplace_evidence = (int)v; }
-  else if (k == "sample_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("sample_chunk_trials is a count of trials, or 0"); c->sample_chunk = (int)v; }
-  else if (k == "interp_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("interp_chunk_trials is a count of trials, or 0"); c->interp_chunk = (int)v; }
-  else if (k == "rates_chunk_trials") { if (v < 0.0 || v != std::floor(v)) return fail("rates_chunk_trials is a count of trials, or 0"); c->rates_chunk = (int)v; }
+  else if (k == "sample_chunk_trials") CHK(chunk_trials(&c->sample_chunk));
+  else if (k == "interp_chunk_trials") CHK(chunk_trials(&c->interp_chunk));
+  else if (k == "rates_chunk_trials") CHK(chunk_trials(&c->rates_chunk));
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
   else if (k == "dual_gemm") c->dual_gemm = (v != 0.0);
@@ -1707,6 +1712,35 @@ int with_snapshot(pgpfa_ctx* c, int id, const std::function<int()>& fn) {
   const int rc2 = pgpfa_set_params(c, curC.data(), curd.data(), curtau.data());
   if (rc) { g_err = err; return rc; }
   return rc2;
+}
+
+int for_snapshot_groups(pgpfa_ctx* c, const std::vector<int>& trials, const std::function<int(const std::vector<int>& positions, bool dual)>& fn) {
+  std::map<std::pair<int, int>, std::vector<int>> groups;
+  for (size_t i = 0; i < trials.size(); ++i) groups[std::make_pair(c->trial_snap[trials[i]], (int)c->trial_dual[trials[i]])].push_back((int)i);
+  for (auto& kv : groups) {
+    const std::vector<int>& pos = kv.second;
+    const bool dual = kv.first.second != 0;
+    CHK(with_snapshot(c, kv.first.first, [&]() { return fn(pos, dual); }));
+  }
+  return 0;
+}
+
+int require_resident(const pgpfa_ctx* c, const std::vector<int>& trials, ResidentKind kind) {
+  for (int t : trials) {
+    if (kind == RESIDENT_BLOCKS && c->mode_serial[t] < 0 && c->trial_snap[t] < 0 && !c->vsmgp_ok[t])
+      return fail("no posterior for trial %d: neither an E-step nor pgpfa_set_posterior has written one since its counts were uploaded", t);
+    if (kind == RESIDENT_SAMPLABLE && (c->trial_snap[t] < 0 || (c->trial_dual[t] && !c->lam_keep)))
+      return fail("no posterior to sample for trial %d: no E-step has written one since its counts were uploaded (a posterior given by pgpfa_set_posterior "
+                  "cannot be sampled, only its blocks are known)", t);
+  }
+  return 0;
+}
+
+int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap) {
+  size_t chunk = cap > 0 ? std::min(n, cap) : n;
+  if (option > 0) chunk = std::min(chunk, (size_t)option);
+  else if (bytes_per_trial > 0) chunk = std::min(chunk, std::max<size_t>(1, QUERY_STAGE_BYTES / bytes_per_trial));
+  return (int)chunk;
 }
 
 int remember_trials(pgpfa_ctx* c, const std::vector<int>& v) {

@@ -756,57 +756,62 @@ int pgpfa_get_post_vsm(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {
 // Rebuild the per-trial T x T blocks of trials whose last E-step ran sum-only: covariance blocks at the resident
 // modes, under the parameters of that E-step (restored around the call when an M-step has moved on since).
 
+// The curvature of one chunk of them (ctx.h; shared with pgpfa_posterior_sample).
 // (dual: the trials' posterior is the dual-variational one - curvature blocks W_t = C^T diag(lambda_t) C from the kept lambda, with the
 // reference's jitter, instead of the Laplace curvature at the mode)
+int resident_curvature(pgpfa_ctx* c, const std::vector<int>& tos, bool dual, const char* where, const std::function<int(double diag_scale)>& finish) {
+  const int nb = (int)tos.size();
+  const size_t m = (size_t)c->q * c->T;
+  CHK(upload_list(c, c->trial_of_slot, tos));
+  HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
+  double scale = 1.0;
+  if (dual) {
+    for (int s = 0; s < nb; ++s)
+      HIPC(hipMemcpyAsync(c->lamd + (size_t)s * m, c->lam_keep + (size_t)tos[s] * m, m * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+    std::vector<double> sB, sD, vKv;
+    CHK(dual_common(c, nb, &sB, &sD, &vKv));
+    if (c->plan_lowrank) CHK(dual_jitter(c, nb));
+    else CHK(dual_dense_scale(c, nb, &scale));
+  } else {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((c->n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, c->n, c->Xc, (long long)c->ld,
+                       c->trial_of_slot, 0);
+    CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
+  }
+  CHK(finish(scale));
+  std::vector<int> info(nb);
+  CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
+  CHK(dl_flush(c));
+  for (int s = 0; s < nb; ++s)
+    if (info[s] != 0) return fail("posterior precision of trial %d is not positive definite at the resident %s", tos[s], where);
+  return 0;
+}
+
 static int materialize_impl(pgpfa_ctx* c, const std::vector<int>& need, bool dual) {
   CHK(ready_estep(c, dual ? c->dual_lowrank : true));
   if (dual) CHK(ensure_lambda(c));
   const int N = (int)need.size();
-  std::vector<int> info(c->B);
-  const size_t m = (size_t)c->q * c->T;
   for (int c0 = 0; c0 < N; c0 += c->B) {
     const int nb = std::min(c->B, N - c0);
-    std::vector<int> tos(need.begin() + c0, need.begin() + c0 + nb);
-    CHK(upload_list(c, c->trial_of_slot, tos));
-    HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
-    if (dual) {
-      for (int s = 0; s < nb; ++s)
-        HIPC(hipMemcpyAsync(c->lamd + (size_t)s * m, c->lam_keep + (size_t)tos[s] * m, m * sizeof(double), hipMemcpyDeviceToDevice, c->st));
-      std::vector<double> sB, sD, vKv;
-      CHK(dual_common(c, nb, &sB, &sD, &vKv));
-      if (c->plan_lowrank) { CHK(dual_jitter(c, nb)); CHK(posterior_blocks(c, nb, 1.0, true, false)); }
-      else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_blocks(c, nb, scale, true, false)); }
-    } else {
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((c->n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, c->n, c->Xc, (long long)c->ld,
-                         c->trial_of_slot, 0);
-      CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
-      CHK(posterior_blocks(c, nb, 1.0, true, false));
-    }
-    CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
-    CHK(dl_flush(c));
-    for (int s = 0; s < nb; ++s) {
-      if (info[s] != 0) return fail("posterior precision of trial %d is not positive definite at the resident mode", tos[s]);
-      c->vsmgp_ok[tos[s]] = 1;
-    }
+    const std::vector<int> tos(need.begin() + c0, need.begin() + c0 + nb);
+    CHK(resident_curvature(c, tos, dual, "mode", [&](double scale) { return posterior_blocks(c, nb, scale, true, false); }));
+    for (int t : tos) c->vsmgp_ok[t] = 1;
   }
   return 0;
 }
 
 int ensure_trial_vsmgp(pgpfa_ctx* c, const std::vector<int>& trials) {
-  // trials whose blocks are not resident, grouped by the E-step (parameter snapshot) that produced their posterior
-  std::map<std::pair<int, int>, std::vector<int>> need;
+  // trials whose blocks are not resident, each once, rebuilt under the E-step (parameter snapshot) that produced their posterior
+  std::vector<int> need;
   for (int t : trials) {
     if (c->vsmgp_ok[t]) continue;
     if (c->trial_snap[t] < 0) return fail("post_vsmGP of trial %d is not resident: no E-step or pgpfa_set_posterior produced it", t);
-    std::vector<int>& v = need[std::make_pair(c->trial_snap[t], (int)c->trial_dual[t])];
-    if (std::find(v.begin(), v.end(), t) == v.end()) v.push_back(t);
+    if (std::find(need.begin(), need.end(), t) == need.end()) need.push_back(t);
   }
-  for (auto& kv : need) {
-    const std::vector<int>& v = kv.second;
-    const bool dual = kv.first.second != 0;
-    CHK(with_snapshot(c, kv.first.first, [&]() { return materialize_impl(c, v, dual); }));
-  }
-  return 0;
+  return for_snapshot_groups(c, need, [&](const std::vector<int>& pos, bool dual) {
+    std::vector<int> v;
+    for (int i : pos) v.push_back(need[i]);
+    return materialize_impl(c, v, dual);
+  });
 }
 
 int pgpfa_get_post_vsmgp(pgpfa_ctx* c, int n, const int32_t* idx, double* out) {

@@ -404,6 +404,37 @@ struct Trials {
   std::vector<int> v;
 };
 
+// ---- what the posterior queries share (pgpfa_posterior_rates / _sample / _at: rates.hip, psample.hip, interp.hip) -------------------------------
+struct DevBufs {                                              // device scratch of one call of `entry`: freed on every way out
+  const char* entry;
+  std::vector<void*> v;
+  explicit DevBufs(const char* entry_point) : entry(entry_point) {}
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() { for (void* p : v) hipFree(p); }
+  template <typename T> int get(T** out, size_t count) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail("%s: hipMalloc(%zu bytes) failed: %s", entry, count * sizeof(T), hipGetErrorString(e)); }
+    v.push_back(p);
+    *out = reinterpret_cast<T*>(p);
+    return 0;
+  }
+};
+constexpr size_t QUERY_STAGE_BYTES = (size_t)256 << 20;      // bound on the device staging of one chunk of a query's trial list
+// Trials per chunk of a list of n: the query's *_chunk_trials option when set, else as many as fit that bound at bytes_per_trial of staging
+// (0 bytes: the whole list), at least one; never more than cap (0: no cap).
+int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap = 0);
+// A posterior is resident for a trial once a Laplace E-step (mode_serial), pgpfa_dual_finalize (its parameter snapshot) or pgpfa_set_posterior (which
+// marks the blocks it uploaded, or left, as the resident ones) has written it; new counts or lengths clear all three: RESIDENT_BLOCKS.  One that can
+// be sampled is one an E-step or pgpfa_dual_finalize of this context wrote - of an uploaded one only blocks are known -, with the kept lambda if it is
+// variational: RESIDENT_SAMPLABLE.  Fails naming the first listed trial that has none.
+enum ResidentKind { RESIDENT_BLOCKS, RESIDENT_SAMPLABLE };
+int require_resident(const pgpfa_ctx* c, const std::vector<int>& trials, ResidentKind kind);
+// fn(positions, dual) for the positions of `trials` that share a (parameter snapshot, Laplace / variational) pair, in the order of the pairs, under that
+// snapshot's parameters (with_snapshot): blocks rebuilt on demand and queries are those of every trial's OWN E-step
+int for_snapshot_groups(pgpfa_ctx* c, const std::vector<int>& trials, const std::function<int(const std::vector<int>& positions, bool dual)>& fn);
+
 // Leave-one-neuron-out job riding on the E-step machinery: item i is (trial tr.v[i], held-out neuron mask[i]); only the
 // mode is found (no covariance blocks, nothing written to the per-trial state), then the held-out neuron is predicted.
 struct LooJob {
@@ -493,6 +524,10 @@ int ensure_evidence_buffers(pgpfa_ctx* c);
 int post_vsm_from_mt(pgpfa_ctx* c, int nslots);        // post_vsm[t] of the first nslots slots from their dense L^-T slabs
 int ensure_trial_vsmgp(pgpfa_ctx* c, const std::vector<int>& trials);
 int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale);      // steps a - b alone (per-bin blocks, B, factor, L^-T) in FP64: pgpfa_posterior_sample
+// Curvature blocks c->W of the resident posterior of the trials `tos`, in the slots [0, tos.size()) (one chunk; the caller has been through ready_estep,
+// and ensure_lambda if dual): at the gathered modes, or from the kept lambda with the reference's jitter.  Then finish(diag_scale) - posterior_blocks or
+// posterior_factor_only - and the factor flags: a trial whose precision is not positive definite fails "... at the resident <where>".
+int resident_curvature(pgpfa_ctx* c, const std::vector<int>& tos, bool dual, const char* where, const std::function<int(double diag_scale)>& finish);
 // dual.hip
 int ensure_lambda(pgpfa_ctx* c);
 int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<double>* sD, std::vector<double>* vKv);

@@ -7,22 +7,8 @@ using namespace pgpfa;
 
 namespace {
 
-constexpr size_t INTERP_STAGE_BYTES = (size_t)256 << 20;     // bound on the device staging of one chunk (per-trial cross Grams, weights, results)
 constexpr size_t INTERP_LDS_MAX = (size_t)160 << 10;          // LDS of a CU: the row panel of interp_var_kernel has to fit
 constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
-
-struct DevBufs {                                              // scratch of one call: freed on every way out
-  std::vector<void*> v;
-  ~DevBufs() { for (void* p : v) hipFree(p); }
-  template <typename T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail("pgpfa_posterior_at: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
-    v.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-  }
-};
 
 struct MarkKeeper {                                           // the resident marks of post_vsmGP are what they were when the call returns
   pgpfa_ctx* c;
@@ -65,7 +51,7 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
   std::vector<int> tos(N);
   for (int i = 0; i < N; ++i) tos[i] = (*a.trials)[pos[i]];
 
-  DevBufs dev;
+  DevBufs dev("pgpfa_posterior_at");
   MarkKeeper keep{c, {}};
   if (a.var) {
     CHK(ensure_vsmgp_buffer(c));
@@ -89,12 +75,10 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
     }
   }
 
-  // chunks of the group: device staging per trial
+  // chunks of the group: device staging per trial (per-trial cross Grams, weights, results)
   const size_t slab = (size_t)p * T16 * Spad;
   const size_t per_trial = ((a.mean ? 1 : 0) + (a.var ? 1 : 0)) * (size_t)p * Spad * sizeof(double) + (a.per_trial ? (2 * slab + S) * sizeof(double) : 0);
-  int chunk = N;
-  if (c->interp_chunk > 0) chunk = std::min(N, c->interp_chunk);
-  else chunk = (int)std::min<size_t>((size_t)N, std::max<size_t>(1, INTERP_STAGE_BYTES / per_trial));
+  const int chunk = query_chunk((size_t)N, c->interp_chunk, per_trial);
   const int grids = a.per_trial ? chunk : 1;
 
   double *d_times = nullptr, *d_kx = nullptr, *d_A = nullptr, *d_mean = nullptr, *d_var = nullptr;
@@ -167,21 +151,12 @@ int pgpfa_posterior_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, const dou
   if (!c->have_params) return fail("set_params has not been called");
   if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
   HIPC(hipSetDevice(c->device));
-  // a posterior is resident for a trial as pgpfa_posterior_rates defines it
-  for (int t : tr.v)
-    if (c->mode_serial[t] < 0 && c->trial_snap[t] < 0 && !c->vsmgp_ok[t])
-      return fail("no posterior for trial %d: neither an E-step nor pgpfa_set_posterior has written one since its counts were uploaded", t);
+  CHK(require_resident(c, tr.v, RESIDENT_BLOCKS));
   for (int t : tr.v)
     if (c->trial_dual[t] && c->live.length(t) < c->T)
       return fail("the variational posterior of trial %d covers %d of %d bins: its jitter comes from the trial's own %d-bin Gram inverse, so the padded grid "
                   "does not carry its prior conditional; pgpfa_posterior_at refuses rather than approximates", t, c->live.length(t), c->T, c->live.length(t));
   AtArgs a{};
   a.trials = &tr.v; a.S = S; a.times = times_ms; a.per_trial = per_trial != 0; a.mean = mean; a.var = var;
-  std::map<std::pair<int, int>, std::vector<int>> groups;     // positions by (snapshot, kind of posterior), as ensure_trial_vsmgp groups its rebuilds
-  for (size_t i = 0; i < tr.v.size(); ++i) groups[std::make_pair(c->trial_snap[tr.v[i]], (int)c->trial_dual[tr.v[i]])].push_back((int)i);
-  for (auto& kv : groups) {
-    const std::vector<int>& pos = kv.second;
-    CHK(with_snapshot(c, kv.first.first, [&]() { return at_group(c, a, pos); }));
-  }
-  return 0;
+  return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool) { return at_group(c, a, pos); });
 }

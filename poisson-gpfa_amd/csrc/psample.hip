@@ -9,21 +9,7 @@ using namespace pgpfa;
 
 namespace {
 
-constexpr size_t SAMPLE_STAGE_BYTES = (size_t)256 << 20;     // bound on the device staging of one chunk (noise, U, trajectories, count planes)
 constexpr int GEMM_COL_SLACK = 128;                          // the GEMM stages whole column tiles of its second operand: columns past N are read, never used
-
-struct DevBufs {                                              // scratch of one call: freed on every way out
-  std::vector<void*> v;
-  ~DevBufs() { for (void* p : v) hipFree(p); }
-  template <typename T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail("pgpfa_posterior_sample: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
-    v.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-  }
-};
 
 struct SampleArgs {
   const std::vector<int>* trials;     // trial of every list position
@@ -49,15 +35,13 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
                 "parameters): set the parameters of that E-step before sampling it", t_first, rz, nz - n);
   const bool want_counts = a.Y || a.count_sum;
 
-  // chunks of the group: device staging per trial
+  // chunks of the group: device staging per trial (noise, U, trajectories, count planes)
   const size_t ldz = lr ? (size_t)rpad : (size_t)npad;       // leading dimension of the GEMM's noise operand (z2 panel / dense z), zero below the rows in use
   const size_t per_trial = (size_t)S * (((lr ? 2 * ldz + n : ldz) + n) * sizeof(double) + (a.Y ? (size_t)q * T * sizeof(uint16_t) : 0) + (want_counts ? (size_t)q * sizeof(int) : 0));
-  int chunk = (int)std::min<size_t>(pos.size(), (size_t)c->B);
-  if (c->sample_chunk > 0) chunk = std::min(chunk, c->sample_chunk);
-  else chunk = (int)std::min<size_t>((size_t)chunk, std::max<size_t>(1, SAMPLE_STAGE_BYTES / per_trial));
+  const int chunk = query_chunk(pos.size(), c->sample_chunk, per_trial, (size_t)c->B);
   if ((long long)chunk * S > (1LL << 30)) return fail("pgpfa_posterior_sample: %d samples of %d trials exceed one chunk's columns", S, chunk);
 
-  DevBufs dev;
+  DevBufs dev("pgpfa_posterior_sample");
   double *dX = nullptr, *dZ1 = nullptr, *dZ = nullptr, *dU = nullptr;
   uint16_t* dY = nullptr;
   int *dCs = nullptr, *dOver = nullptr;
@@ -75,31 +59,14 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
   const int zused = lr ? rz : n;                               // rows of dZ a draw fills: z2, or the dense z
   const size_t zoff = lr ? (size_t)n : 0;                      // where they sit in a draw's nz normals
 
-  std::vector<int> info(chunk), over(chunk), tos;
+  std::vector<int> over(chunk), tos;
   const size_t m = (size_t)q * T;
   for (size_t c0 = 0; c0 < pos.size(); c0 += chunk) {
     const int nb = (int)std::min<size_t>((size_t)chunk, pos.size() - c0);
     tos.assign(nb, 0);
     for (int s = 0; s < nb; ++s) tos[s] = (*a.trials)[pos[c0 + s]];
-    CHK(upload_list(c, c->trial_of_slot, tos));
-    HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
-    // curvature blocks of the slots, as materialize_impl (cov.hip) forms them, then steps a - b of the covariance pass
-    if (dual) {
-      for (int s = 0; s < nb; ++s)
-        HIPC(hipMemcpyAsync(c->lamd + (size_t)s * m, c->lam_keep + (size_t)tos[s] * m, m * sizeof(double), hipMemcpyDeviceToDevice, c->st));
-      std::vector<double> sB, sD, vKv;
-      CHK(dual_common(c, nb, &sB, &sD, &vKv));
-      if (lr) { CHK(dual_jitter(c, nb)); CHK(posterior_factor_only(c, nb, 1.0)); }
-      else { double scale = 1.0; CHK(dual_dense_scale(c, nb, &scale)); CHK(posterior_factor_only(c, nb, scale)); }
-    } else {
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, c->st, c->Xmode, n, c->Xc, (long long)c->ld, c->trial_of_slot, 0);
-      CHK(poisson(c, c->ident, nb, c->Xc, c->Gl, c->W, c->sc_f, 1));
-      CHK(posterior_factor_only(c, nb, 1.0));
-    }
-    CHK(dl_enqueue(c, info.data(), c->ws.info, sizeof(int) * nb));
-    CHK(dl_flush(c));
-    for (int s = 0; s < nb; ++s)
-      if (info[s] != 0) return fail("posterior precision of trial %d is not positive definite at the resident posterior", tos[s]);
+    // curvature blocks of the slots, as the blocks rebuilt on demand form them (cov.hip), then steps a - b of the covariance pass
+    CHK(resident_curvature(c, tos, dual, "posterior", [&](double scale) { return posterior_factor_only(c, nb, scale); }));
 
     // 1. the normals: copied in, or drawn
     if (a.noise_in) {
@@ -220,11 +187,7 @@ int pgpfa_posterior_sample(pgpfa_ctx* c, int n, const int32_t* idx, int n_sample
   HIPC(hipSetDevice(c->device));
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
-  // a posterior that can be sampled: one an E-step or pgpfa_dual_finalize of this context wrote (its parameter snapshot) - of an uploaded one only blocks are known
-  for (int t : tr.v)
-    if (c->trial_snap[t] < 0 || (c->trial_dual[t] && !c->lam_keep))
-      return fail("no posterior to sample for trial %d: no E-step has written one since its counts were uploaded (a posterior given by pgpfa_set_posterior "
-                  "cannot be sampled, only its blocks are known)", t);
+  CHK(require_resident(c, tr.v, RESIDENT_SAMPLABLE));
   SampleArgs a{};
   a.trials = &tr.v; a.S = n_samples; a.seed = seed; a.noise_in = noise_in; a.noise_out = noise_out; a.X = X; a.Y = Y; a.count_sum = count_sum;
   // engine and noise dimension under the current parameters (info key "sample_noise_dim"); variational trials follow option dual_lowrank
@@ -232,12 +195,5 @@ int pgpfa_posterior_sample(pgpfa_ctx* c, int n, const int32_t* idx, int n_sample
   for (int t : tr.v) any_laplace = any_laplace || !c->trial_dual[t];
   a.lowrank = want_lowrank(c) && (any_laplace || c->dual_lowrank);
   a.nz = c->n + (a.lowrank ? c->rtot : 0);
-  std::map<std::pair<int, int>, std::vector<int>> groups;     // positions by (snapshot, kind of posterior), as ensure_trial_vsmgp groups its rebuilds
-  for (size_t i = 0; i < tr.v.size(); ++i) groups[std::make_pair(c->trial_snap[tr.v[i]], (int)c->trial_dual[tr.v[i]])].push_back((int)i);
-  for (auto& kv : groups) {
-    const std::vector<int>& pos = kv.second;
-    const bool dual = kv.first.second != 0;
-    CHK(with_snapshot(c, kv.first.first, [&]() { return sample_group(c, a, pos, dual); }));
-  }
-  return 0;
+  return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool dual) { return sample_group(c, a, pos, dual); });
 }

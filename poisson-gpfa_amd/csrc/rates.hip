@@ -6,27 +6,12 @@ using namespace pgpfa;
 
 namespace {
 
-constexpr size_t RATES_STAGE_BYTES = (size_t)256 << 20;      // bound on the device staging of the per-trial planes of one chunk
-
 // bins per workgroup tile: the largest of 64 / 32 / 16 whose LDS image (4 KS rows of rates_row_stride(BT) doubles) stays within 64 KiB - two workgroups
 // per CU -, else 16: 70 KiB at 32 latents, one workgroup per CU
 int rates_nbt(int KS) {
   for (int nbt : {4, 2}) if ((size_t)4 * KS * rates_row_stride(16 * nbt) * sizeof(double) <= ((size_t)64 << 10)) return nbt;
   return 1;
 }
-
-struct DevBufs {                                              // scratch of one call: freed on every way out
-  std::vector<void*> v;
-  ~DevBufs() { for (void* p : v) hipFree(p); }
-  template <typename T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail("pgpfa_posterior_rates: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
-    v.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-  }
-};
 
 template <int NBT>
 int rates_launch(pgpfa_ctx* c, const RatesP& a, bool grouped, int items, size_t lds) {
@@ -69,11 +54,7 @@ int pgpfa_posterior_rates(pgpfa_ctx* c, int n, const int32_t* idx, const int32_t
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
   const int N = (int)tr.v.size(), q = c->q, p = c->p, T = c->T;
-  // a posterior is resident for a trial once a Laplace E-step (mode_serial), pgpfa_dual_finalize (its parameter snapshot) or pgpfa_set_posterior
-  // (which marks the blocks it uploaded, or left, as the resident ones) has written it; new counts or lengths clear all three
-  for (int t : tr.v)
-    if (c->mode_serial[t] < 0 && c->trial_snap[t] < 0 && !c->vsmgp_ok[t])
-      return fail("no posterior for trial %d: neither an E-step nor pgpfa_set_posterior has written one since its counts were uploaded", t);
+  CHK(require_resident(c, tr.v, RESIDENT_BLOCKS));
   if (group)
     for (int i = 0; i < N; ++i)
       if (group[i] < 0 || group[i] >= n_groups) return fail("group id %d of list entry %d (trial %d) is outside 0..%d", (int)group[i], i, tr.v[i], n_groups - 1);
@@ -105,11 +86,9 @@ int pgpfa_posterior_rates(pgpfa_ctx* c, int n, const int32_t* idx, const int32_t
   // chunks of the list: the per-trial planes of a chunk are staged on the device
   const size_t plane = (size_t)q * T * sizeof(double);
   const size_t per_trial = ((eta ? 1 : 0) + (var ? 1 : 0)) * plane + (ell ? (size_t)(nbt + 1) * q * sizeof(double) : 0);
-  int chunk = N;
-  if (c->rates_chunk > 0) chunk = std::min(N, c->rates_chunk);
-  else if (per_trial > 0) chunk = (int)std::min<size_t>((size_t)N, std::max<size_t>(1, RATES_STAGE_BYTES / per_trial));
+  const int chunk = query_chunk((size_t)N, c->rates_chunk, per_trial);
 
-  DevBufs dev;
+  DevBufs dev("pgpfa_posterior_rates");
   int *d_trial = nullptr, *d_start = nullptr, *d_pos = nullptr;
   double *d_eta = nullptr, *d_var = nullptr, *d_ellp = nullptr, *d_ell = nullptr, *d_gsum = nullptr;
   CHK(dev.get(&d_trial, (size_t)N));

@@ -123,6 +123,15 @@ def check(rc):
         raise HipBackendError(load_library().pgpfa_last_error().decode('utf-8', 'replace'))
 
 
+def _check_outputs(want, known, may_be_empty=False):
+    """the `want` of a posterior query: only known output names, and at least one"""
+    unknown = set(want) - set(known)
+    if unknown:
+        raise ValueError('unknown output(s) %s' % sorted(unknown))
+    if not want and not may_be_empty:
+        raise ValueError('no output asked for')
+
+
 def rates_group_csr(group, n_groups, first=0, last=None):
     """(start[n_groups + 1], pos[last - first]): the list positions first..last-1 of every group, in list order (pgpfa_rates_group_csr; host only)."""
     gg = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
@@ -364,9 +373,7 @@ class Context:
         want: any of 'eta' [n][q][T], 'var' [n][q][T], 'ell' [n][q], 'group_sum' [n_groups][q][T], 'group_count' [n_groups][T] (int32); group: one
         id in 0..n_groups-1 per listed trial.  Returns a dict of exactly the arrays asked for; nothing else is computed or moved."""
         n, ii = self._n_idx(idx)
-        unknown = set(want) - {'eta', 'var', 'ell', 'group_sum', 'group_count'}
-        if unknown:
-            raise ValueError('unknown output(s) %s' % sorted(unknown))
+        _check_outputs(want, ('eta', 'var', 'ell', 'group_sum', 'group_count'), may_be_empty=True)      # (the library refuses an empty request itself)
         gg = None
         if group is not None:
             gg = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
@@ -387,14 +394,10 @@ class Context:
         standard normals that were used, nz = info('sample_noise_dim').  noise: those normals given by the caller ([n][S][nz]) instead of drawn on the
         device from `seed`.  Returns a dict of exactly the arrays asked for."""
         n, ii = self._n_idx(idx)
-        unknown = set(want) - {'x', 'y', 'count_sum', 'noise'}
-        if unknown:
-            raise ValueError('unknown output(s) %s' % sorted(unknown))
         S = int(n_samples)
+        _check_outputs(want, ('x', 'y', 'count_sum', 'noise'), may_be_empty=S < 1)
         if S < 1:
             raise ValueError('n_samples = %d: at least one draw per trial is needed' % S)
-        if not want:
-            raise ValueError('no output asked for')
         zin = None
         nz = None
         if noise is not None or 'noise' in want:
@@ -417,11 +420,7 @@ class Context:
         (include/pgpfa.h: pgpfa_posterior_at).  times: (S,) - one grid for all listed trials - or (n, S), one grid per list entry.  want: 'mean'
         and / or 'var', each [n][p][S].  Returns a dict of exactly the arrays asked for."""
         n, ii = self._n_idx(idx)
-        unknown = set(want) - {'mean', 'var'}
-        if unknown:
-            raise ValueError('unknown output(s) %s' % sorted(unknown))
-        if not want:
-            raise ValueError('no output asked for')
+        _check_outputs(want, ('mean', 'var'))
         tt = as_f64(times)
         if tt.ndim == 1:
             per_trial = 0

@@ -151,6 +151,33 @@ def _cut_planes(sess, idx, arr, forecast):
     return np.stack(out) if len(set(lens)) == 1 else out
 
 
+def _resident_posterior(what, params, experiment, infRes, trials, set_params):
+    """The front end of the queries on a resident posterior (posteriorRates, posteriorSamples, posteriorAt = `what`): the experiment's session and the
+    session's indices of the listed trials (positions in experiment.data; None: all; repeats allowed), once a posterior is resident for them.
+    infRes None: one Laplace E-step at `params` over the experiment.  A DeviceInfRes of this session whose entries are still the resident ones: that
+    posterior, with `params` set as the current parameters if `set_params`.  Anything else raises ValueError; a sharded session NotImplementedError."""
+    from . import _session, inference
+    sess, trial_idx = _session.session_for(experiment, np.shape(params['C'])[1])
+    if sess.comm_ready:
+        raise NotImplementedError('%s does not support sharded sessions: every rank holds the posterior of its own trials only' % what)
+    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
+    if idx.size == 0:
+        raise ValueError('empty trial list')
+    if infRes is None:
+        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
+        return sess, idx
+    if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
+        raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
+    covered = set(infRes.trial_idx.tolist())
+    stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
+    if stale:
+        raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
+    if set_params:
+        sess.set_params({'C': params['C'], 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+    return sess, idx
+
+
 def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None, level=0.95, forecast=False, want=('rate', 'lower', 'upper')):
     """Denoised single-trial firing rates lambda_n(t) = exp(d_n + c_n . x_t) under the posterior of the latents, with a credible band, and
     their averages over the trials of every experimental condition.  The reference stops at the latent posterior; its only rate-like
@@ -171,33 +198,16 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     'condition_labels' [G]; with want=() only these come back and no per-trial plane leaves the device.
     Under a per-bin table (experiment.data[r]['observedBins']) the planes and the condition averages cover every entry - an entry that was not
     recorded gets the model's prediction - and 'ell' raises ValueError: the resident counts at such entries are placeholders."""
-    from . import _session, inference
+    from . import _session
     want = tuple(want)
     unknown = [k for k in want if k not in _RATE_KEYS]
     if unknown:
         raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_RATE_KEYS)))
     z = _band_z(level)
-    xdim = np.shape(params['C'])[1]
-    sess, trial_idx = _session.session_for(experiment, xdim)
-    if 'ell' in want and getattr(sess, 'observed_bins', None) is not None:
+    if 'ell' in want and getattr(_session.session_for(experiment, np.shape(params['C'])[1])[0], 'observed_bins', None) is not None:
         raise ValueError("want: 'ell' is not available under a per-bin table ('observedBins'): the resident counts at entries that were not "
                          'recorded are placeholders')
-    if sess.comm_ready:
-        raise NotImplementedError('posteriorRates does not support sharded sessions yet: every rank holds the posterior of its own trials only')
-    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
-    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
-    if idx.size == 0:
-        raise ValueError('empty trial list')
-    if infRes is None:
-        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
-    else:
-        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
-            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
-        covered = set(infRes.trial_idx.tolist())
-        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
-        if stale:
-            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
-        sess.set_params({'C': params['C'], 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+    sess, idx = _resident_posterior('posteriorRates', params, experiment, infRes, trials, set_params=True)
     planes = any(k in want for k in ('rate', 'lower', 'upper', 'median', 'eta', 'var'))
     ask = (['eta', 'var'] if planes else []) + (['ell'] if 'ell' in want else [])
     group, labels = None, None
@@ -247,7 +257,6 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
     want: any of 'x' [n][nSamples][xdim][T], 'y' [n][nSamples][ydim][T] (uint16: y ~ Poisson(exp(d + C x)) per bin), 'count_sum'
     [n][nSamples][ydim] (the counts of a draw summed over the trial's bins) and 'noise' (the standard normals used).  With trials of unequal
     length 'x' and 'y' are lists of arrays cut to each trial's own T_r bins.  Draw s of a trial is a pure function of (seed, trial, s)."""
-    from . import _session, inference
     want = tuple(want)
     unknown = [k for k in want if k not in _SAMPLE_KEYS]
     if unknown:
@@ -256,23 +265,7 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
         raise ValueError('nothing asked for: want is empty')
     if int(nSamples) != nSamples or int(nSamples) < 1:
         raise ValueError('nSamples = %r: a count of draws per trial, at least 1' % (nSamples,))
-    xdim = np.shape(params['C'])[1]
-    sess, trial_idx = _session.session_for(experiment, xdim)
-    if sess.comm_ready:
-        raise NotImplementedError('posteriorSamples does not support sharded sessions: every rank holds the posterior of its own trials only')
-    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
-    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
-    if idx.size == 0:
-        raise ValueError('empty trial list')
-    if infRes is None:
-        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
-    else:
-        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
-            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
-        covered = set(infRes.trial_idx.tolist())
-        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
-        if stale:
-            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
+    sess, idx = _resident_posterior('posteriorSamples', params, experiment, infRes, trials, set_params=False)
     dev = sess.ctx.posterior_sample(idx, n_samples=int(nSamples), seed=int(seed), want=want)
     out = {}
     for k in want:
@@ -332,29 +325,12 @@ def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=
         raise ValueError('times: shape (S,) or (n, S) with S >= 1 expected, got %s' % (tt.shape,))
     if not np.all(np.isfinite(tt)):                    # (before the session is touched: nothing reaches the device)
         raise ValueError('times: entry %s is not finite' % (tuple(int(i) for i in np.argwhere(~np.isfinite(tt))[0]),))
-    xdim = np.shape(params['C'])[1]
-    sess, trial_idx = _session.session_for(experiment, xdim)
-    if sess.comm_ready:
-        raise NotImplementedError('posteriorAt does not support sharded sessions: every rank holds the posterior of its own trials only')
-    pos = np.arange(len(trial_idx)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
-    idx = np.ascontiguousarray(trial_idx[pos], dtype=np.int32)
-    if idx.size == 0:
-        raise ValueError('empty trial list')
+    sess, idx = _resident_posterior('posteriorAt', params, experiment, infRes, trials, set_params=True)
     if tt.ndim == 2 and tt.shape[0] != idx.size:
         raise ValueError('times: one grid per listed trial expected, (%d, S), got %s' % (idx.size, tt.shape))
     labels, group = (None, None) if conditions is None else _condition_groups(conditions, idx.size)
     if not want and labels is None:
         raise ValueError('nothing asked for: want is empty and there are no conditions')
-    if infRes is None:
-        inference.laplace(experiment, copy.copy(params), returnOptimRes=False)
-    else:
-        if not isinstance(infRes, _session.DeviceInfRes) or infRes.session is not sess:
-            raise ValueError("infRes is not a device-backed result of this experiment's session: pass infRes=None to run an E-step")
-        covered = set(infRes.trial_idx.tolist())
-        stale = [int(t) for t in idx if sess.trial_stamp[int(t)] != infRes.stamp or int(t) not in covered]
-        if stale:
-            raise ValueError('infRes is superseded (or never covered) for trial %d: a later E-step has overwritten its posterior on the device' % stale[0])
-        sess.set_params({'C': params['C'], 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
     need_var = any(k in want for k in ('var', 'lower', 'upper'))
     need_mean = labels is not None or any(k in want for k in ('mean', 'lower', 'upper'))
     dev = sess.ctx.posterior_at(tt, idx, want=(('mean',) if need_mean else ()) + (('var',) if need_var else ()))
@@ -421,29 +397,40 @@ def coSmoothing(params, experiment, heldOut, trials=None):
     Yt[:n] = Y[pos]
     Yt[:n, held] = 0
     len_t = np.concatenate([np.asarray(lengths, dtype=np.int32)[pos], [Y.shape[2]]]).astype(np.int32)
-    if bins_t is not None:                               # (checked before the context exists; None: every entry inside the other two tables is live)
-        bins_t = _session.compose_observed_bins(bins_t, len_t, masked, n + 1, ydim, Y.shape[2])
-    sess = _session.Session(Yt, xdim, float(experiment.binSize), len_t, masked)
-    try:
-        sess._install_observed_bins(bins_t)
-        sess.set_params({'C': C, 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
-        idx = np.arange(n, dtype=np.int32)
-        _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
-        if np.any(status > 1):
-            raise _hip.HipBackendError('coSmoothing: the Laplace mode search failed for %d trial(s)' % int(np.sum(status > 1)))
-        dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
-        lam = np.exp(dev['eta'][:, held] + 0.5 * dev['var'][:, held])          # predicted counts per bin [n][held][T]
-    finally:
-        sess.ctx.close()
+    lam = _predicted_without_hidden('coSmoothing', params, experiment, Yt, len_t, masked, bins_t, held)      # [n] of (held, T_r)
     per_s = 1000.0 / float(experiment.binSize)
-    rates = [lam[i, :, :int(len_t[i])] * per_s for i in range(n)]
+    rates = [lm * per_s for lm in lam]
     # the score, on the host: the caller's true counts at the entries the experiment itself recorded
-    lam = [lam[i, :, :int(len_t[i])] for i in range(n)]
     scored = [np.broadcast_to(own[int(r)][held][:, None], lm.shape) if own_bins is None else own[int(r)][held][:, None] & own_bins[int(r)][held][:, :lm.shape[1]]
               for r, lm in zip(pos, lam)]
     truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64)[held] for r in pos]
     total, per_neuron, _ = _score_entries(truth, lam, scored)
     return {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+
+
+def _predicted_without_hidden(what, params, experiment, Yt, len_t, masked, bins_t, rows=slice(None)):
+    """The prediction step of the hold-out scores (coSmoothing, binHoldout = `what`, the prefix of a failure): a context of its own over the n listed
+    trials plus one silent, fully observed trial - counts Yt (n + 1, ydim, T) with the hidden entries zeroed, lengths len_t, observation table
+    masked (n + 1, ydim), per-bin table bins_t (n + 1, ydim, T) or None (checked against the other two before the context exists) -, ONE cold Laplace
+    E-step over the n trials and the posterior mean count per bin exp(eta + var / 2) of the neurons `rows`.  The context is closed on every way
+    out.  Returns one (rows, T_r) array per listed trial."""
+    from . import _session
+    n, ydim, T = Yt.shape[0] - 1, Yt.shape[1], Yt.shape[2]
+    if bins_t is not None:
+        bins_t = _session.compose_observed_bins(bins_t, len_t, masked, n + 1, ydim, T)
+    sess = _session.Session(Yt, np.shape(params['C'])[1], float(experiment.binSize), len_t, masked)
+    try:
+        sess._install_observed_bins(bins_t)
+        sess.set_params({'C': np.asarray(params['C'], dtype=np.float64), 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
+        idx = np.arange(n, dtype=np.int32)
+        _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
+        if np.any(status > 1):
+            raise _hip.HipBackendError('%s: the Laplace mode search failed for %d trial(s)' % (what, int(np.sum(status > 1))))
+        dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
+        lam = np.exp(dev['eta'][:, rows] + 0.5 * dev['var'][:, rows])
+    finally:
+        sess.ctx.close()
+    return [lam[i, :, :int(len_t[i])] for i in range(n)]
 
 
 def _score_entries(truth, lam, scored):
@@ -526,21 +513,8 @@ def binHoldout(params, experiment, heldOut, trials=None):
     Yt = np.zeros((n + 1,) + Y.shape[1:], dtype=Y.dtype)
     Yt[:n] = np.where(bins_t[:n], Y[pos], 0)
     len_t = np.concatenate([lengths[pos], [T]]).astype(np.int32)
-    live_t = _session.compose_observed_bins(bins_t, len_t, masked, n + 1, ydim, T)      # (checked before the context exists; None: nothing is hidden)
-    sess = _session.Session(Yt, xdim, float(experiment.binSize), len_t, masked)
-    try:
-        sess._install_observed_bins(live_t)
-        sess.set_params({'C': C, 'd': params['d'], 'tau': np.ndarray.flatten(np.asarray(params['tau'], dtype=np.float64))})
-        idx = np.arange(n, dtype=np.int32)
-        _, _, status = sess.ctx.estep_laplace(idx, warm_start=False)
-        if np.any(status > 1):
-            raise _hip.HipBackendError('binHoldout: the Laplace mode search failed for %d trial(s)' % int(np.sum(status > 1)))
-        dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
-        lam = np.exp(dev['eta'] + 0.5 * dev['var'])                             # predicted counts per bin [n][ydim][T]
-    finally:
-        sess.ctx.close()
+    lam = _predicted_without_hidden('binHoldout', params, experiment, Yt, len_t, masked, bins_t)      # [n] of (ydim, T_r)
     per_s = 1000.0 / float(experiment.binSize)
-    lam = [lam[i, :, :int(len_t[i])] for i in range(n)]
     scored = [(hide[i] & own_live[i])[:, :int(len_t[i])] for i in range(n)]
     truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64) for r in pos]
     total, per_neuron, n_scored = _score_entries(truth, lam, scored)

@@ -308,6 +308,44 @@ def test_the_estep_timescales_are_used_and_no_state_is_touched(config):
     assert all(same)
 
 
+@pytest.mark.parametrize('config', CONFIGS, ids=CONFIG_IDS)
+def test_a_list_across_two_parameter_snapshots_gives_the_bits_of_one_call_per_trial(config):
+    """four trials, {0, 1} through an E-step at parameters A and {2, 3} through one at B (C, d and every timescale differ): one call over
+    [3, 0, 2, 1, 0] walks two snapshot groups and scatters by list position"""
+    from funs import _hip
+    shape = SHAPES[4]                                    # (the smallest)
+    q, p, T = shape
+    par, Y, _ = problem(shape, R=4)
+    mixed = np.array([3, 0, 2, 1, 0], dtype=np.int32)
+    s = np.array([0.0, 3.7, 10.0, T - 1.0, T + 2.5]) * BIN_MS      # on the grid, off it, beyond the last bin
+    ctx = _hip.Context(q, p, T, 4, BIN_MS)
+    try:
+        ctx.upload_counts(Y.astype(np.uint16 if Y.max() > 255 else np.uint8))
+        ctx.set_option('cov_mode', config[0])
+        ctx.set_option('keep_trial_vsmgp', config[1])
+        ctx.set_params(par['C'], par['d'], par['tau'])
+        _, _, status = ctx.estep_laplace(np.array([0, 1], dtype=np.int32))
+        assert np.all(status == 0), status
+        ctx.set_params(par['C'] * 1.05 + 0.01, par['d'] + 0.1, par['tau'] * np.linspace(0.85, 0.95, p))
+        _, _, status = ctx.estep_laplace(np.array([2, 3], dtype=np.int32))
+        assert np.all(status == 0), status
+        assert ctx.info('plan_lowrank') == float(config[0] == 2)
+        before = [ctx.post_mean(), ctx.post_vsm(), ctx.gram()]
+        one = ctx.posterior_at(s, mixed)
+        after = [ctx.post_mean(), ctx.post_vsm(), ctx.gram()]
+        same = []
+        for i in range(mixed.size):
+            single = ctx.posterior_at(s, mixed[i:i + 1])
+            same.append(bool(np.array_equal(one['mean'][i], single['mean'][0]) and np.array_equal(one['var'][i], single['var'][0])))
+        kept = [bool(np.array_equal(a, b)) for a, b in zip(before, after)]
+        print('%s: list %s against one call per entry %s; post_mean, post_vsm, Gram unchanged %s' % (CONFIG_IDS[CONFIGS.index(config)], mixed.tolist(), same, kept))
+        assert all(same)
+        assert np.array_equal(one['mean'][1], one['mean'][4]) and np.array_equal(one['var'][1], one['var'][4])
+        assert all(kept)
+    finally:
+        ctx.close()
+
+
 # ---- 8. variational and uploaded posteriors --------------------------------------------------------------------------------------------------------
 def _var_problem(which):
     if which == 'var_toy':

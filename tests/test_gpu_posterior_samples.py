@@ -310,6 +310,39 @@ def test_sampling_leaves_the_resident_state_alone(engine):
         ctx.close()
 
 
+@pytest.mark.parametrize('engine', ENGINES, ids=ENGINE_IDS)
+def test_a_list_across_two_parameter_snapshots_gives_the_bits_of_one_call_per_trial(engine):
+    """four trials, {0, 1} through an E-step at parameters A and {2, 3} through one at B (C, d and every timescale differ): one call over
+    [3, 0, 2, 1, 0] walks two snapshot groups and scatters by list position"""
+    from funs import _hip
+    shape = SHAPES[0]
+    q, p, T = shape
+    par, Y, _ = problem(shape, R=4)
+    mixed = np.array([3, 0, 2, 1, 0], dtype=np.int32)
+    ctx = _hip.Context(q, p, T, 4, BIN_MS)
+    try:
+        ctx.upload_counts(Y.astype(np.uint16 if Y.max() > 255 else np.uint8))
+        ctx.set_option('cov_mode', engine)
+        ctx.set_params(par['C'], par['d'], par['tau'])
+        _, _, status = ctx.estep_laplace(np.array([0, 1], dtype=np.int32))
+        assert np.all(status == 0), status
+        ctx.set_params(par['C'] * 1.05 + 0.01, par['d'] + 0.1, par['tau'] * np.linspace(0.85, 0.95, p))
+        _, _, status = ctx.estep_laplace(np.array([2, 3], dtype=np.int32))
+        assert np.all(status == 0), status
+        assert ctx.info('plan_lowrank') == float(engine == 2)
+        before = [ctx.post_mean(), ctx.post_vsm(), ctx.gram()]
+        one = ctx.posterior_sample(mixed, n_samples=4, seed=11, want=('x',))['x']
+        after = [ctx.post_mean(), ctx.post_vsm(), ctx.gram()]
+        same = [bool(np.array_equal(one[i], ctx.posterior_sample(mixed[i:i + 1], n_samples=4, seed=11, want=('x',))['x'][0])) for i in range(mixed.size)]
+        kept = [bool(np.array_equal(a, b)) for a, b in zip(before, after)]
+        print('engine %d: list %s against one call per entry %s; post_mean, post_vsm, Gram unchanged %s' % (engine, mixed.tolist(), same, kept))
+        assert all(same)
+        assert np.array_equal(one[1], one[4])
+        assert all(kept)
+    finally:
+        ctx.close()
+
+
 # ---- 10. errors --------------------------------------------------------------------------------------------------------------------------------------------
 def raw_call(ctx, n_samples=2, want_x=True, want_y=False, idx=LIST):
     """the C entry point without the binding's own checks -> (return code, message)"""

@@ -174,7 +174,9 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * "sample_chunk_trials" (0 - the default: pgpfa_posterior_sample walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
  * "interp_chunk_trials" (0 - the default: pgpfa_posterior_at walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
- * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that). */
+ * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
+ * "counts_chunk_trials" (0 - the default; the same for pgpfa_posterior_counts), "counts_nodes" (32: nodes of the Gauss-Hermite rule of
+ * pgpfa_count_probabilities / pgpfa_posterior_counts, 8 .. 64; the rule's error falls with it and the cost grows in proportion). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
 /* Options that pgpfa_set_params builds from - "eps_noise" (Gram matrices, their inverses, the low-rank factors), "lowrank_tol" (the low-rank
  * factors), "rank_gran", "thin_products" and "use_mfma" (the rank tables: compact offsets need both) - re-run it with the stored parameters
@@ -376,6 +378,43 @@ int pgpfa_posterior_sample(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
 int pgpfa_posterior_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
                        int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
                        double* mean /* [n][p][S] or NULL */, double* var /* [n][p][S] or NULL */);
+
+/* Posterior-predictive spike counts from the two moments of the log rate.  The reference has no counterpart: it stops at the latent posterior, and
+ * its only count-like outputs are exp(C x + d) at a held-out mode (util.py:289-334).  With eta ~ N(m, v) the count of an entry is the
+ * Poisson-lognormal mixture
+ *   P(y = k) = int Poisson(k; e^eta) N(eta; m, v) d eta          (no closed form; mean mu = exp(m + v / 2), variance mu + mu^2 (e^v - 1))
+ * evaluated in FP64 by a Gauss-Hermite rule of "counts_nodes" nodes (option; 32, allowed 8 .. 64; nodes and weights are computed on the host and
+ * uploaded once per context and node count) centred on the mode of the integrand and scaled by its curvature there - found by Newton from m, at
+ * most 40 steps, warm-started from the mode of k - 1 when k is walked - and written in (eta - m) / v throughout, so that v = 0 is an ordinary input
+ * (the Poisson pmf at e^m) and v -> 0 approaches it smoothly (csrc/counts.h).  Per entry i, every output optional:
+ *   logp[i]     = log P(y = counts[i]), counts in 0 .. 65535
+ *   pmf[i][k]   = P(y = k), k = 0 .. K - 1 (k fastest), 1 <= K <= 1024
+ *   lower[i], upper[i] = the smallest k with CDF(k) >= (1 - level) / 2 and with CDF(k) >= (1 + level) / 2, 0 < level < 1; the walk over k stops at
+ *                 k_cap (0 .. 65535): an entry whose upper quantile lies beyond gets k_cap (lower too if it lies beyond), and the number of such
+ *                 entries of the LAST call is info "counts_saturated"
+ *   pmean[i], pvar[i]  = mu and mu + mu^2 expm1(v), counts per bin
+ * An entry whose moments are not finite or whose v is negative gets NaN (lower, upper: -1).  An entry's outputs are functions of its own inputs and
+ * of K, level, k_cap and the node count alone, bit for bit: not of its position, of the other entries, of how the entries are cut into chunks, or
+ * of which other outputs are asked for.  No atomics.  Needs a context for its device and stream only: no counts, parameters or posterior.
+ * Fails, naming what is wrong: every output NULL; K, level or k_cap outside their ranges (each checked only when an output reads it); logp
+ * without counts; a count outside 0 .. 65535. */
+int pgpfa_count_probabilities(pgpfa_ctx* ctx, long long n_entries, const double* m /* [n_entries] */, const double* v /* [n_entries] */,
+                              const int32_t* counts /* [n_entries], or NULL without logp */, int K, double level, int k_cap,
+                              double* logp /* [n_entries] */, double* pmf /* [n_entries][K] */, int32_t* lower, int32_t* upper /* [n_entries] */,
+                              double* pmean, double* pvar /* [n_entries] */);
+/* The same per (trial, neuron, bin) of the listed trials under their resident posterior (the reference has no counterpart): m = eta and v = var of
+ * pgpfa_posterior_rates, staged on the device per chunk of the list by that entry point's kernel and never copied to the host, then the kernel of
+ * pgpfa_count_probabilities on the staged planes.  Every output is [n][q][T] (pmf [n][q][T][K]).  counts: a host array [n][q][T] (0 .. 65535), or
+ * NULL for the resident counts, both byte planes.  Entries behind a trial's T_r (pgpfa_set_trial_lengths) are written as NaN (lower, upper: -1) and
+ * are not counted in "counts_saturated"; an unobserved neuron (pgpfa_set_observed) or entry (pgpfa_set_observed_bins) has a posterior of its log
+ * rate like any other and gets the model's prediction.  A trial's result does not depend on its position in the list, on the other trials, on the
+ * chunking (option "counts_chunk_trials", as "rates_chunk_trials") or on the outputs asked for, bit for bit; a trial listed twice gives the same
+ * numbers twice.  Fails as pgpfa_posterior_rates does and in its order - set_params not called, the trial list, a trial without a posterior -, and
+ * before those: logp with counts NULL while no counts are uploaded, or while a per-bin table is set (the resident counts at entries that were not
+ * recorded are placeholders: pass the counts).  Touches no E-step or M-step state, as pgpfa_posterior_rates. */
+int pgpfa_posterior_counts(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                           const int32_t* counts /* [n][q][T] or NULL: the resident counts */, int K, double level, int k_cap,
+                           double* logp, double* pmf, int32_t* lower, int32_t* upper, double* pmean, double* pvar);
 
 /* ---- M-step ----------------------------------------------------------------------- */
 /* MStepObservationCost(_grad) (learning.py:20-91) over the trials of the last E-step /

@@ -1040,7 +1040,7 @@ int pgpfa_destroy(pgpfa_ctx* c) {
 int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   if (!c || !key) return fail("null argument");
   const std::string k(key);
-  auto chunk_trials = [&](int* field) -> int {              // the three *_chunk_trials options of the posterior queries
+  auto chunk_trials = [&](int* field) -> int {              // the *_chunk_trials options of the posterior queries
     if (v < 0.0 || v != std::floor(v)) return fail("%s is a count of trials, or 0", key);
     *field = (int)v;
     return 0;
@@ -1110,6 +1110,8 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "sample_chunk_trials") CHK(chunk_trials(&c->sample_chunk));
   else if (k == "interp_chunk_trials") CHK(chunk_trials(&c->interp_chunk));
   else if (k == "rates_chunk_trials") CHK(chunk_trials(&c->rates_chunk));
+  else if (k == "counts_chunk_trials") CHK(chunk_trials(&c->counts_chunk));
+  else if (k == "counts_nodes") { if (v < 8.0 || v > 64.0 || v != std::floor(v)) return fail("counts_nodes is a node count in 8 .. 64"); c->counts_Q = (int)v; }
   else if (k == "slab_row_align") c->slab_row_align = (v != 0.0);
   else if (k == "vsm_mfma") c->vsm_mfma = (v != 0.0);
   else if (k == "dual_gemm") c->dual_gemm = (v != 0.0);

@@ -325,6 +325,11 @@ struct pgpfa_ctx {
   int rates_chunk = 0;                            // trials per chunk of a call (0: from the 256 MiB bound on the staging of the per-trial planes)
   int sample_chunk = 0;                           // option sample_chunk_trials: the same for pgpfa_posterior_sample (psample.hip); no output depends on it
   int interp_chunk = 0;                           // option interp_chunk_trials: the same for pgpfa_posterior_at (interp.hip); no output depends on it
+  // predictive counts (pgpfa_count_probabilities / pgpfa_posterior_counts, rates.hip): the Gauss-Hermite nodes and log weights of the rule, computed on
+  // the host and uploaded on first use and again when option counts_nodes has changed (counts_nodes_Q: the node count the device copy holds)
+  int counts_chunk = 0;                           // option counts_chunk_trials: the same for pgpfa_posterior_counts; no output depends on it
+  int counts_Q = 32;                              // option counts_nodes: nodes of the rule, 8 .. 64
+  double* counts_nodes = nullptr; int counts_nodes_Q = 0;     // device [2][64]: x_q | log w_q
 };
 
 template <typename T>

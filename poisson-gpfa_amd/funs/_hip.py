@@ -48,6 +48,10 @@ _SIGNATURES = {
     'pgpfa_posterior_rates': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p],
     'pgpfa_posterior_sample': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p, ct.POINTER(ct.c_uint16), c_int32_p],
     'pgpfa_posterior_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p],
+    'pgpfa_count_probabilities': [ct.c_void_p, ct.c_longlong, c_double_p, c_double_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p,
+                                  c_int32_p, c_double_p, c_double_p],
+    'pgpfa_posterior_counts': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p,
+                               c_double_p, c_double_p],
     'pgpfa_rates_group_csr': [ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_int, c_int32_p, c_int32_p],
     'pgpfa_mstep_cd_costgrad': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p],
     'pgpfa_mstep_cd_newton_pass': [ct.c_void_p, c_double_p, c_double_p, ct.c_double, c_double_p, c_double_p, c_double_p],
@@ -130,6 +134,9 @@ def _check_outputs(want, known, may_be_empty=False):
         raise ValueError('unknown output(s) %s' % sorted(unknown))
     if not want and not may_be_empty:
         raise ValueError('no output asked for')
+
+
+COUNT_OUTPUTS = ('logp', 'pmf', 'lower', 'upper', 'pmean', 'pvar')      # of count_probabilities / posterior_counts, in the order of the C prototypes
 
 
 def rates_group_csr(group, n_groups, first=0, last=None):
@@ -432,6 +439,41 @@ class Context:
         out = {k: np.empty((n, self.p, S)) for k in ('mean', 'var') if k in want}
         check(self.lib.pgpfa_posterior_at(self.h, n, iptr(ii), S, dptr(tt), per_trial, dptr(out['mean']) if 'mean' in out else None,
                                           dptr(out['var']) if 'var' in out else None))
+        return out
+
+    def _count_outputs(self, shape, counts, K, level, k_cap, want):
+        """The output arrays of the two predictive-count calls and their pointers in the order of the C prototypes (None where not asked for)."""
+        _check_outputs(want, COUNT_OUTPUTS)
+        cc = None
+        if counts is not None:
+            cc = np.ascontiguousarray(counts, dtype=np.int32)
+            if cc.shape != shape:
+                raise ValueError('counts must have shape %s, got %s' % (shape, cc.shape))
+        kinds = {'logp': (shape, np.float64), 'pmf': (shape + (int(K),), np.float64), 'lower': (shape, np.int32), 'upper': (shape, np.int32),
+                 'pmean': (shape, np.float64), 'pvar': (shape, np.float64)}
+        out = {k: np.empty(kinds[k][0], dtype=kinds[k][1]) for k in COUNT_OUTPUTS if k in want}
+        ptrs = [None if k not in out else (iptr(out[k]) if k in ('lower', 'upper') else dptr(out[k])) for k in COUNT_OUTPUTS]
+        return cc, out, (iptr(cc), int(K), float(level), int(k_cap)) + tuple(ptrs)
+
+    def count_probabilities(self, m, v, counts=None, K=1, level=0.95, k_cap=65535, want=('logp',)):
+        """Posterior-predictive count probabilities of entries with log-rate moments m, v (any shape, the same for both; include/pgpfa.h:
+        pgpfa_count_probabilities).  want: any of 'logp' (needs counts, int32 of m's shape), 'pmf' (m's shape + (K,)), 'lower' / 'upper' (int32, the
+        central `level` interval, walked up to k_cap; info('counts_saturated') counts the entries it cut), 'pmean', 'pvar'.  Returns a dict of exactly
+        the arrays asked for."""
+        mm, vv = as_f64(m), as_f64(v)
+        if mm.shape != vv.shape:
+            raise ValueError('m and v must have the same shape, got %s and %s' % (mm.shape, vv.shape))
+        cc, out, args = self._count_outputs(mm.shape, counts, K, level, k_cap, want)
+        check(self.lib.pgpfa_count_probabilities(self.h, mm.size, dptr(mm), dptr(vv), *args))
+        return out
+
+    def posterior_counts(self, idx=None, counts=None, K=1, level=0.95, k_cap=65535, want=('logp',)):
+        """The same per (trial, neuron, bin) of the listed trials (repeats allowed) under their resident posterior (include/pgpfa.h:
+        pgpfa_posterior_counts): every output [n][q][T], 'pmf' [n][q][T][K].  counts: int32 [n][q][T], or None for the resident counts.  Bins behind
+        a trial's own length come back as NaN (lower, upper: -1)."""
+        n, ii = self._n_idx(idx)
+        cc, out, args = self._count_outputs((n, self.q, self.T), counts, K, level, k_cap, want)
+        check(self.lib.pgpfa_posterior_counts(self.h, n, iptr(ii), *args))
         return out
 
     # -- dual variational ---------------------------------------------------------------------

@@ -316,6 +316,14 @@ class PPGPFAfit():
         self.samples = util.posteriorSamples(self.optimParams, self.experiment, **kw)
         return self.samples
 
+    def posteriorCounts(self, **kw):
+        """util.posteriorCounts at the fitted parameters -> self.counts (a dict; keywords as there: infRes, trials, counts, maxCount, level,
+        forecast, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.counts = util.posteriorCounts(self.optimParams, self.experiment, **kw)
+        return self.counts
+
     def posteriorAt(self, **kw):
         """util.posteriorAt at the fitted parameters -> self.trajectoriesAt (a dict; keywords as there: times, infRes, trials, conditions,
         level, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""

@@ -241,6 +241,130 @@ def posteriorRates(params, experiment, infRes=None, trials=None, conditions=None
     return out
 
 
+# -- posterior-predictive spike counts -------------------------------------------------------------------------
+_COUNT_KEYS = ('logp', 'pmf', 'lower', 'upper', 'mean', 'var', 'saturated')
+_COUNT_DEVICE = {'logp': 'logp', 'pmf': 'pmf', 'lower': 'lower', 'upper': 'upper', 'mean': 'pmean', 'var': 'pvar', 'saturated': 'upper'}
+MAX_COUNT = 65535                                          # largest count a bin can hold on the device (two byte planes)
+
+
+def _listed_counts(counts, experiment, pos, ydim, T):
+    """The caller's counts - one (ydim, T_r) array per listed trial - as one int32 (n, ydim, T) array, zeros behind T_r.  Shapes and values are
+    checked against the experiment: no device is touched."""
+    if len(counts) != len(pos):
+        raise ValueError('counts: one (ydim, T_r) array per listed trial expected (%d trials, %d arrays)' % (len(pos), len(counts)))
+    out = np.zeros((len(pos), ydim, T), dtype=np.int32)
+    for i, (r, y) in enumerate(zip(pos, counts)):
+        y = np.asarray(y)
+        L = int(np.shape(experiment.data[int(r)]['Y'])[1])
+        if y.shape != (ydim, L):
+            raise ValueError('counts[%d] must have shape (ydim, T_r) = (%d, %d), got %s' % (i, ydim, L, y.shape))
+        if not np.all((y >= 0) & (y <= MAX_COUNT) & (y == np.floor(y))):
+            raise ValueError('counts[%d]: integers in 0..%d expected' % (i, MAX_COUNT))
+        out[i, :, :L] = y
+    return out
+
+
+def posteriorCounts(params, experiment, infRes=None, trials=None, counts=None, maxCount=None, level=0.95, forecast=False, want=('logp',)):
+    """What the fitted model predicts for the spike COUNT of every (trial, neuron, bin): with the log rate eta ~ N(eta, var) of posteriorRates the
+    count is the Poisson-lognormal mixture P(y = k) = int Poisson(k; e^eta) N(eta; m, v) d eta - over-dispersed, variance mu + mu^2 (e^v - 1), and
+    far from Poisson(mu) where the posterior is wide: held-out neurons, hidden entries, forecast bins.  The reference has no counterpart.  Computed
+    on the device from the resident posterior (pgpfa_posterior_counts: a mode-centred Gauss-Hermite rule in FP64; eta and var never come to the host).
+
+    infRes, trials: as posteriorRates.  counts: one (ydim, T_r) array of integers per listed trial - the counts 'logp' is taken at -, or None for
+    the experiment's own.  maxCount: 'pmf' covers k = 0..maxCount (needed for 'pmf', at most 1023), and the walk of the band stops there (None:
+    at 65535).  want: any of
+      'logp'   log P(y) at the count of every entry; NaN where the experiment did not observe the neuron on the trial and counts is None,
+      'pmf'    [n][ydim][T][maxCount + 1],
+      'lower', 'upper'   the central `level` predictive interval in counts (integers): the smallest k with CDF(k) >= (1 -+ level) / 2; an entry
+               whose upper quantile lies beyond maxCount gets maxCount,
+      'saturated'   how many entries that happened to (an int; computes 'upper'),
+      'mean', 'var'   mu = exp(eta + var / 2) and mu + mu^2 (e^var - 1): counts per BIN, not per second.
+    Per-trial entries are [n][ydim][T]; with trials of unequal length each is cut to its T_r bins - a list - unless forecast=True, which keeps all T
+    bins: behind T_r they carry the prediction from the trial's own bins, and 'logp' is NaN there.  Under a per-bin table ('observedBins') every
+    entry gets a prediction; 'logp' with counts=None raises ValueError there (the resident counts at entries that were not recorded are placeholders)."""
+    from . import _session
+    want = tuple(want)
+    unknown = [k for k in want if k not in _COUNT_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_COUNT_KEYS)))
+    if not want:
+        raise ValueError('nothing asked for: want is empty')
+    _band_z(level)                                       # (its check of level)
+    if maxCount is not None and (int(maxCount) != maxCount or not 0 <= int(maxCount) <= MAX_COUNT):
+        raise ValueError('maxCount must be an integer in 0..%d, got %r' % (MAX_COUNT, maxCount))
+    if 'pmf' in want and (maxCount is None or int(maxCount) > 1023):
+        raise ValueError("want: 'pmf' needs maxCount (at most 1023): it covers k = 0..maxCount")
+    ydim = np.shape(params['C'])[0]
+    pos = np.arange(len(experiment.data)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    T_all = max(int(np.shape(tr['Y'])[1]) for tr in experiment.data)
+    given = None if counts is None else _listed_counts(counts, experiment, pos, ydim, T_all)      # (checked before any device call)
+    if 'logp' in want and counts is None and getattr(_session.session_for(experiment, np.shape(params['C'])[1])[0], 'observed_bins', None) is not None:
+        raise ValueError("want: 'logp' needs counts= under a per-bin table ('observedBins'): the resident counts at entries that were not "
+                         'recorded are placeholders')
+    sess, idx = _resident_posterior('posteriorCounts', params, experiment, infRes, trials, set_params=True)
+    if given is not None and given.shape[2] != sess.T:
+        given = _listed_counts(counts, experiment, pos, ydim, sess.T)
+    ask = sorted({_COUNT_DEVICE[k] for k in want})
+    K = 1 if maxCount is None else int(maxCount) + 1
+    k_cap = MAX_COUNT if maxCount is None else int(maxCount)
+    ragged = sess.lengths is not None
+    if forecast and ragged:
+        # behind T_r the library writes padding: the forecast goes through the moments, which cover all T bins
+        mv = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
+        at = given
+        if 'logp' in want and at is None:
+            at = _listed_counts([experiment.data[int(r)]['Y'] for r in pos], experiment, pos, ydim, sess.T)
+        dev = sess.ctx.count_probabilities(mv['eta'], mv['var'], counts=at if 'logp' in want else None, K=K, level=level, k_cap=k_cap, want=ask)
+        if 'logp' in dev:
+            beyond = np.arange(sess.T)[None, :] >= sess.lengths[idx][:, None]
+            dev['logp'] = np.where(beyond[:, None, :], np.nan, dev['logp'])
+    else:
+        dev = sess.ctx.posterior_counts(idx, counts=given if 'logp' in want else None, K=K, level=level, k_cap=k_cap, want=ask)
+    saturated = int(sess.ctx.info('counts_saturated')) if 'upper' in ask else 0
+    if 'logp' in dev and counts is None:
+        observed = getattr(sess, 'observed', None)
+        if observed is not None:                           # no counts, nothing to take the probability of
+            dev['logp'] = np.where(observed[idx][:, :, None], dev['logp'], np.nan)
+    out = {}
+    for k in want:
+        out[k] = saturated if k == 'saturated' else _cut_planes(sess, idx, dev[_COUNT_DEVICE[k]], forecast)
+    return out
+
+
+def _score_predictive(truth, logp, scored):
+    """Bits per spike of the predictive distribution over single entries: truth, logp (log P(y) of the model at the true count) and scored are lists
+    of (rows, T_r) arrays, one per trial.  Per row n: sum over its scored entries of log P(y) - log Poisson(y; lbar_n), lbar_n the mean count of row n
+    over its scored entries as in _score_entries, both terms WITH - log y!; divided by log 2 times the spikes scored.  Returns (total, per row -
+    NaN for a row without a scored spike)."""
+    from math import lgamma
+    rows = truth[0].shape[0]
+    tot_y, tot_n = np.zeros(rows), np.zeros(rows)
+    for y, sc in zip(truth, scored):
+        tot_y += np.where(sc, y, 0.0).sum(axis=1)
+        tot_n += sc.sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        lbar = np.where(tot_n > 0, tot_y / tot_n, 0.0)
+    lfact = np.vectorize(lambda k: lgamma(k + 1.0), otypes=[np.float64])
+    ll, spikes = np.zeros(rows), np.zeros(rows)
+    for y, lp, sc in zip(truth, logp, scored):
+        y = np.where(sc, y, 0.0)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            null = np.where(y > 0, y * np.log(lbar)[:, None], 0.0) - lbar[:, None] - lfact(y)
+        ll += np.where(sc, np.where(sc, lp, 0.0) - null, 0.0).sum(axis=1)
+        spikes += y.sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        per_row = np.where(spikes > 0, ll / (np.log(2.0) * spikes), np.nan)
+        total = float(ll.sum() / (np.log(2.0) * spikes.sum())) if spikes.sum() > 0 else float('nan')
+    return total, per_row
+
+
+def _predictive_keys(truth, logp, scored):
+    """The keys predictive=True adds to the dict of coSmoothing / binHoldout"""
+    total, per_row = _score_predictive(truth, logp, scored)
+    return {'logPredictive': [np.where(sc, lp, np.nan) for lp, sc in zip(logp, scored)], 'bitsPerSpikePredictive': total,
+            'bitsPerSpikePredictivePerNeuron': per_row}
+
+
 _SAMPLE_KEYS = ('x', 'y', 'count_sum', 'noise')
 
 
@@ -348,7 +472,7 @@ def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=
 
 
 # -- co-smoothing: held-out neurons predicted from the others -------------------------------------------------
-def coSmoothing(params, experiment, heldOut, trials=None):
+def coSmoothing(params, experiment, heldOut, trials=None, predictive=False):
     """Predict the neurons `heldOut` on the listed trials from the trials' other neurons and score the prediction: the held-out neurons are
     marked unobserved on those trials (on top of experiment.data[r]['observed']), ONE Laplace E-step gives the posterior of the latents
     without them, and their rate is the posterior mean rate exp(eta + var / 2) that posteriorRates documents.  No ydim mode searches per
@@ -362,7 +486,10 @@ def coSmoothing(params, experiment, heldOut, trials=None):
     spikes per second; 'bitsPerSpike' - sum over the scored (trial, neuron, bin) of [y log lam - lam] - [y log lbar_n - lbar_n], divided by
     log 2 times the spikes scored, lam the predicted count per bin, lbar_n the mean count per bin of neuron n over its scored bins;
     'bitsPerSpikePerNeuron' [len(heldOut)] (NaN for a neuron without a scored spike).  A (trial, neuron) pair is scored when the experiment
-    itself observed the neuron on that trial: the score is computed on the host from the rate plane and the caller's true counts."""
+    itself observed the neuron on that trial: the score is computed on the host from the rate plane and the caller's true counts.
+    predictive=True adds the proper score: 'logPredictive' - one (len(heldOut), T_r) array per trial, log P(y) of the true count under the
+    predictive distribution of posteriorCounts, NaN where the entry is not scored -, 'bitsPerSpikePredictive' - sum over the scored entries of
+    log P(y) - log Poisson(y; lbar_n), both with - log y!, divided by log 2 times the spikes scored - and 'bitsPerSpikePredictivePerNeuron'."""
     from . import _session
     C = np.asarray(params['C'], dtype=np.float64)
     ydim, xdim = C.shape
@@ -397,7 +524,12 @@ def coSmoothing(params, experiment, heldOut, trials=None):
     Yt[:n] = Y[pos]
     Yt[:n, held] = 0
     len_t = np.concatenate([np.asarray(lengths, dtype=np.int32)[pos], [Y.shape[2]]]).astype(np.int32)
-    lam = _predicted_without_hidden('coSmoothing', params, experiment, Yt, len_t, masked, bins_t, held)      # [n] of (held, T_r)
+    at = None
+    if predictive:                                       # the true counts of the held-out neurons where they are scored, 0 elsewhere
+        at = np.zeros(Yt.shape, dtype=np.int32)
+        keep = own[pos][:, held][:, :, None] if own_bins is None else own[pos][:, held][:, :, None] & own_bins[pos][:, held]
+        at[:n, held] = np.where(keep, Y[pos][:, held], 0)
+    lam, logp = _predicted_without_hidden('coSmoothing', params, experiment, Yt, len_t, masked, bins_t, held, at)      # [n] of (held, T_r)
     per_s = 1000.0 / float(experiment.binSize)
     rates = [lm * per_s for lm in lam]
     # the score, on the host: the caller's true counts at the entries the experiment itself recorded
@@ -405,15 +537,20 @@ def coSmoothing(params, experiment, heldOut, trials=None):
               for r, lm in zip(pos, lam)]
     truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64)[held] for r in pos]
     total, per_neuron, _ = _score_entries(truth, lam, scored)
-    return {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+    out = {'rate': rates, 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'heldOut': held}
+    if predictive:
+        out.update(_predictive_keys(truth, logp, scored))
+    return out
 
 
-def _predicted_without_hidden(what, params, experiment, Yt, len_t, masked, bins_t, rows=slice(None)):
+def _predicted_without_hidden(what, params, experiment, Yt, len_t, masked, bins_t, rows=slice(None), counts_at=None):
     """The prediction step of the hold-out scores (coSmoothing, binHoldout = `what`, the prefix of a failure): a context of its own over the n listed
     trials plus one silent, fully observed trial - counts Yt (n + 1, ydim, T) with the hidden entries zeroed, lengths len_t, observation table
     masked (n + 1, ydim), per-bin table bins_t (n + 1, ydim, T) or None (checked against the other two before the context exists) -, ONE cold Laplace
     E-step over the n trials and the posterior mean count per bin exp(eta + var / 2) of the neurons `rows`.  The context is closed on every way
-    out.  Returns one (rows, T_r) array per listed trial."""
+    out.  counts_at (n + 1, ydim, T) int32 or None: the counts at which the predictive log probability of every entry is also taken (the private
+    context holds zeros at the hidden entries, so the query is given the caller's).  Returns (one (rows, T_r) array per listed trial, the same of
+    log P or None)."""
     from . import _session
     n, ydim, T = Yt.shape[0] - 1, Yt.shape[1], Yt.shape[2]
     if bins_t is not None:
@@ -428,9 +565,13 @@ def _predicted_without_hidden(what, params, experiment, Yt, len_t, masked, bins_
             raise _hip.HipBackendError('%s: the Laplace mode search failed for %d trial(s)' % (what, int(np.sum(status > 1))))
         dev = sess.ctx.posterior_rates(idx, group=None, n_groups=0, want=['eta', 'var'])
         lam = np.exp(dev['eta'][:, rows] + 0.5 * dev['var'][:, rows])
+        logp = None
+        if counts_at is not None:
+            logp = sess.ctx.posterior_counts(idx, counts=counts_at[:n], want=['logp'])['logp'][:, rows]
     finally:
         sess.ctx.close()
-    return [lam[i, :, :int(len_t[i])] for i in range(n)]
+    cut = lambda a: [a[i, :, :int(len_t[i])] for i in range(n)]
+    return cut(lam), (None if logp is None else cut(logp))
 
 
 def _score_entries(truth, lam, scored):
@@ -458,7 +599,7 @@ def _score_entries(truth, lam, scored):
     return total, per_row, int(tot_n.sum())
 
 
-def binHoldout(params, experiment, heldOut, trials=None):
+def binHoldout(params, experiment, heldOut, trials=None, predictive=False):
     """Predict single (neuron, bin) entries of the listed trials from everything else and score the prediction: the per-entry sibling of
     coSmoothing ("speckled" hold-out).  heldOut: one boolean (ydim, T_r) array per listed trial, True = hide and score.  The hidden entries are
     marked as not recorded (on top of the experiment's own lengths, 'observed' and 'observedBins'), ONE Laplace E-step gives the posterior of
@@ -469,7 +610,8 @@ def binHoldout(params, experiment, heldOut, trials=None):
 
     trials: positions in experiment.data (None: all).  Returns a dict: 'rate' - one (ydim, T_r) array per listed trial, spikes per second,
     every entry; 'bitsPerSpike' and 'bitsPerSpikePerNeuron' [ydim] as coSmoothing defines them, over the entries that are held out AND were
-    live in the experiment (the null model is each neuron's mean count over its scored entries); 'nScored' - how many those are."""
+    live in the experiment (the null model is each neuron's mean count over its scored entries); 'nScored' - how many those are.
+    predictive=True adds 'logPredictive', 'bitsPerSpikePredictive' and 'bitsPerSpikePredictivePerNeuron' as coSmoothing defines them."""
     from . import _session
     C = np.asarray(params['C'], dtype=np.float64)
     ydim, xdim = C.shape
@@ -513,12 +655,19 @@ def binHoldout(params, experiment, heldOut, trials=None):
     Yt = np.zeros((n + 1,) + Y.shape[1:], dtype=Y.dtype)
     Yt[:n] = np.where(bins_t[:n], Y[pos], 0)
     len_t = np.concatenate([lengths[pos], [T]]).astype(np.int32)
-    lam = _predicted_without_hidden('binHoldout', params, experiment, Yt, len_t, masked, bins_t)      # [n] of (ydim, T_r)
+    at = None
+    if predictive:                                       # the true counts at the scored entries, 0 elsewhere
+        at = np.zeros(Yt.shape, dtype=np.int32)
+        at[:n] = np.where(hide & own_live, Y[pos], 0)
+    lam, logp = _predicted_without_hidden('binHoldout', params, experiment, Yt, len_t, masked, bins_t, counts_at=at)      # [n] of (ydim, T_r)
     per_s = 1000.0 / float(experiment.binSize)
     scored = [(hide[i] & own_live[i])[:, :int(len_t[i])] for i in range(n)]
     truth = [np.asarray(experiment.data[int(r)]['Y'], dtype=np.float64) for r in pos]
     total, per_neuron, n_scored = _score_entries(truth, lam, scored)
-    return {'rate': [lm * per_s for lm in lam], 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'nScored': n_scored}
+    out = {'rate': [lm * per_s for lm in lam], 'bitsPerSpike': total, 'bitsPerSpikePerNeuron': per_neuron, 'nScored': n_scored}
+    if predictive:
+        out.update(_predictive_keys(truth, logp, scored))
+    return out
 
 
 def speckledHoldout(experiment, holdoutFraction=0.1, seed=0):
@@ -604,10 +753,11 @@ class crossValidation:
     better, so optimXdim stays the arg-min).  It also takes test trials of unequal length, which the leave-one-out score refuses.
     score='speckled' (an addition; Laplace only) hides a seeded random subset of the TRAINING trials' live entries (speckledHoldout: each with
     probability holdoutFraction, numpy.random.default_rng(seed), the same subset for every width), fits on the rest and scores the fit by
-    binHoldout at the hidden entries: errs[i] = - bitsPerSpike (lower is better); the test split is not used."""
+    binHoldout at the hidden entries: errs[i] = - bitsPerSpike (lower is better); the test split is not used.  predictive=True (with
+    score='speckled') scores by the predictive distribution of the counts instead: errs[i] = - bitsPerSpikePredictive."""
 
     def __init__(self, experiment, numTrainingTrials=10, numTestTrials=2, maxXdim=6, maxEMiter=3, batchSize=5,
-                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo', holdoutFraction=0.1, seed=0):
+                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo', holdoutFraction=0.1, seed=0, predictive=False):
         from . import engine
         if learningMethod not in ('batch', 'diag', 'hess', 'grad'):
             raise ValueError("learningMethod must be 'batch', 'diag', 'hess' or 'grad'")
@@ -617,6 +767,8 @@ class crossValidation:
             raise ValueError("score='evidence' is the Laplace log evidence: it needs inferenceMethod='laplace'")
         if score == 'speckled' and inferenceMethod != 'laplace':
             raise ValueError("score='speckled' fits and scores under a per-bin table: it needs inferenceMethod='laplace'")
+        if predictive and score != 'speckled':
+            raise ValueError("predictive=True is the predictive score of binHoldout: it needs score='speckled'")
         trainingSet, testSet = splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials)
         if score == 'speckled':
             scoredSet = trainingSet                       # (the hidden entries are scored against the training trials' true counts)
@@ -633,7 +785,7 @@ class crossValidation:
                                        EMmode='Online', onlineParamUpdateMethod=learningMethod, maxEMiter=maxEMiter,
                                        batchSize=batchSize, quiet=quiet)
             if score == 'speckled':
-                predErr = -binHoldout(fit.optimParams, scoredSet, self.heldOut)['bitsPerSpike']
+                predErr = -binHoldout(fit.optimParams, scoredSet, self.heldOut, predictive=predictive)['bitsPerSpikePredictive' if predictive else 'bitsPerSpike']
             elif score == 'evidence':
                 predErr = negLogEvidencePerBin(fit.optimParams, testSet)
             else:

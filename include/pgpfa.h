@@ -561,6 +561,39 @@ int pgpfa_test_split_syrk(pgpfa_ctx* ctx, int nslots, int T, int p, int ract, in
  * the segmented-K GEMM (option "cross_kernel").  Groups as in the E-step: X in groups of sps slots (0: its rule, as above), S in at most 256 groups. */
 int pgpfa_test_split_latent_sums(pgpfa_ctx* ctx, int nslots, int rk, int kw, int T, int lda, long long sM, int row_off, int ldd, long long sD, int sps,
                                  int cross_kernel, const double* A, const float* D, double* Ssum, double* Xsum);
+/* pgpfa_test_thin: the three block-diagonal products of the low-rank preconditioner y = F Sb F^T t (csrc/thin.h) on caller data, through the table builder
+ * of the rank tables (thin_tables) and the launch code of the inner solve (thin_launch_ft / _s / _f); device buffers of its own, the context only lends its
+ * stream.  kind: PGPFA_THIN_FT u = F^T t, PGPFA_THIN_S v = Sb u, PGPFA_THIN_F y = F v, PGPFA_THIN_APPLY the three in that order through two intermediates.
+ * Geometry by the rule of the rank tables: rr_l = round_up(ranks[l], gran) (gran 4, 8 or 16), rk_l = round_up(rr_l, 16), roff_l = sum of rr before l,
+ * rtot = roff_p, rpad = round_up(max(rtot, max_l roff_l + rk_l), 128); they come back in geom = [rr (p), rk (p), roff (p + 1), rtot, rpad], the work tables in
+ * tab_ft / tab_f / tab_s (four ints per entry, at most tab_cap ints each) and their entry counts in ntab[3].
+ * F: slabs [p][Tf][Tf], element (t, j) of latent l at l Tf Tf + j Tf + t; columns [ranks[l], rk_l) must hold zeros, rows t >= T may hold anything.  The
+ *   transposed copy FT (ld rpad) is built from F by build_fbig_kernel, as the rank tables' owner builds it, over a buffer that holds `fill` where production
+ *   has zeros (outside every latent's own rr rows).  Sb: [rpad][rpad], element (m, k) at k rpad + m, read for m, k < rtot.
+ * n-vectors (input of FT, output of F): one column per slot, latent l at rows l Tx + (0..T), Tx >= T; doubles, or floats with vec_f32 (FT, F, APPLY).
+ * rank-space vectors (output of FT, both of S, input of F): doubles, rows [0, rtot) of a column that holds at least rpad.
+ * X: input [nslots][ldx], Y: output [nslots][ldy] (elements of their storage type), uploaded before the launch - what no kernel stores comes back as it
+ *   went in - with a band of 1024 doubles behind it, and behind the intermediates of APPLY (leading dimension max(ldx, ldy), prefilled with `fill`); the
+ *   call fails if a band changed.  Every input has 128 elements of `fill` behind it.
+ * cols (may be NULL: identity): ncols slot numbers; live: device-side count of the leading list entries in use (-1: none); stop: value of the device
+ *   stop flag (-1: no flag).
+ * Impossible geometry is refused before anything is allocated or launched, with a code of its own (the text is in pgpfa_last_error). */
+enum {
+  PGPFA_THIN_FT = 0, PGPFA_THIN_S = 1, PGPFA_THIN_F = 2, PGPFA_THIN_APPLY = 3
+};
+enum {
+  PGPFA_THIN_BAD_ARG = 100,       /* null pointer, unknown kind or granularity, sizes below 1, Tf below T or no multiple of 4 */
+  PGPFA_THIN_REFUSED_T = 101,     /* T < 4 */
+  PGPFA_THIN_REFUSED_RANK = 102,  /* a rank or the rank total no multiple of 4, rk above Tf */
+  PGPFA_THIN_REFUSED_TX = 103,    /* Tx < T, or Tx % 4 where T % 4 == 0 */
+  PGPFA_THIN_REFUSED_LD = 104,    /* ldx / ldy below the rows read or written, or no multiple of 4 */
+  PGPFA_THIN_REFUSED_RPAD = 105,  /* rpad above the leading dimension of a rank-space vector */
+  PGPFA_THIN_REFUSED_COLS = 106,  /* list entry outside the slots, or a slot twice; without a list, more columns than slots */
+  PGPFA_THIN_REFUSED_LIVE = 107   /* live count above ncols */
+};
+int pgpfa_test_thin(pgpfa_ctx* ctx, int kind, int p, int T, int Tf, const int32_t* ranks, int gran, long long ldx, long long ldy, int Tx, int vec_f32,
+                    int nslots, int ncols, const int32_t* cols, int live, int stop, double fill, const double* F, const double* Sb, const void* X, void* Y,
+                    int32_t* geom /* [3 p + 3] */, int tab_cap, int32_t* tab_ft, int32_t* tab_f, int32_t* tab_s, int32_t* ntab /* [3] */);
 /* Times `reps` launches of the dominant kernel (batched trailing SYRK update, K=512) with HIP
  * events on the context stream; returns average ms per launch and the flops of one launch. */
 int pgpfa_bench_syrk(pgpfa_ctx* ctx, int batch, int n, int k, int reps, double* ms_per_launch,

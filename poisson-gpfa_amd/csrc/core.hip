@@ -2,6 +2,8 @@
 #include "ctx.h"
 #include "model.h"
 #include "dual.h"
+#include "thin.h"
+#include "hook.h"
 
 using namespace pgpfa;
 
@@ -734,6 +736,28 @@ int launch_pivchol(pgpfa_ctx* c, hipStream_t st) {
   return 0;
 }
 
+// Work tables of thin.h's kernels from the rank tables (rr: rank rows a latent owns, rk = round_up(rr, 16): the size its products are issued with,
+// roff: where its rows start, rtot = roff[p]).
+ThinTables thin_tables(int p, int T, const int* rr, const int* rk, const int* roff, int rtot) {
+  ThinTables tt;
+  std::vector<int>&hft = tt.ft, &hf = tt.f, &hs = tt.s;
+  for (int k = 0; k < p; ++k) {
+    // (row groups of a latent of equal size up to one 4-row run, multiples of 4 up to 64: 80 rank rows are 40 + 40, not 64 + 16, and 136 are
+    //  48 + 44 + 44, not 48 + 48 + 40 - the remainder is dealt out in runs of 4 to the first groups; rr is a multiple of 4)
+    // (rr, not rk: these rows are WRITTEN - past the latent's own they are the next latent's)
+    const int ngr = (rr[k] + 63) / 64, runs = rr[k] / 4;
+    for (int g = 0, m0 = 0; g < ngr; ++g) {
+      const int rows = 4 * (runs / ngr + (g < runs % ngr ? 1 : 0));
+      hft.push_back(k); hft.push_back(m0); hft.push_back(rows); hft.push_back(roff[k]);
+      m0 += rows;
+    }
+    for (int t0 = 0; t0 < T; t0 += 256) { hf.push_back(k); hf.push_back(t0); hf.push_back(rk[k]); hf.push_back(roff[k]); }
+  }
+  // Sb u with the same kernel as F^T t: one "latent" of rtot rows and rtot "bins", 64 rows per workgroup
+  for (int m0 = 0; m0 < rtot; m0 += 64) { hs.push_back(0); hs.push_back(m0); hs.push_back(std::min(64, rtot - m0)); hs.push_back(0); }
+  return tt;
+}
+
 // (pivchol_launched: the kernel is already running on the side stream and c->ev_join marks its end)
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   const int p = c->p, T = c->T, Tp = c->Tp;
@@ -814,18 +838,9 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
     if (tft.size() > c->tab_cap || tf.size() > c->tab_cap) return fail("internal: row-tile table overflow");
     CHK(upload_list(c, c->d_kr_ft, tft));
     CHK(upload_list(c, c->d_kr_f, tf));
-    // thin.h: F^T t by (latent, 64 rank rows), F v by (latent, 512 bins)
-    std::vector<int> hft, hf;
-    for (int k = 0; k < p; ++k) {
-      // (row groups of a latent of equal size, a multiple of 4 up to 64: 80 rank rows are 40 + 40, not 64 + 16)
-      // (rr, not rk: these rows are WRITTEN - past the latent's own they are the next latent's)
-      const int ngr = (c->rr[k] + 63) / 64, per = round_up((c->rr[k] + ngr - 1) / ngr, 4);
-      for (int m0 = 0; m0 < c->rr[k]; m0 += per) { hft.push_back(k); hft.push_back(m0); hft.push_back(std::min(per, c->rr[k] - m0)); hft.push_back(c->roff[k]); }
-      for (int t0 = 0; t0 < T; t0 += 256) { hf.push_back(k); hf.push_back(t0); hf.push_back(c->rk[k]); hf.push_back(c->roff[k]); }
-    }
-    // Sb u with the same kernel as F^T t: one "latent" of rtot rows and rtot "bins", 64 rows per workgroup
-    std::vector<int> hs;
-    for (int m0 = 0; m0 < c->rtot; m0 += 64) { hs.push_back(0); hs.push_back(m0); hs.push_back(std::min(64, c->rtot - m0)); hs.push_back(0); }
+    // thin.h: F^T t by (latent, 64 rank rows), F v by (latent, 256 bins), Sb u by 64 rows
+    const ThinTables tt = thin_tables(p, T, c->rr.data(), c->rk.data(), c->roff.data(), c->rtot);
+    const std::vector<int>&hft = tt.ft, &hf = tt.f, &hs = tt.s;
     c->nthin_s = (int)hs.size() / 4;
     if (hs.size() > c->tab_cap) return fail("internal: thin-product table overflow");
     CHK(upload_list(c, c->d_thin_s, hs));
@@ -847,6 +862,174 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   c->info["lowrank_compact"] = c->rank_compact ? 1.0 : 0.0;
   c->flr32_valid = false;
   return 0;
+}
+
+// ---- test hook: the three thin products of the low-rank preconditioner on caller data, through thin_tables and the launches of shared_solve ---------
+namespace {
+int thin_refuse(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  (void)fail("pgpfa_test_thin refuses: %s", buf);
+  return code;
+}
+}  // namespace
+
+int pgpfa_test_thin(pgpfa_ctx* c, int kind, int p, int T, int Tf, const int32_t* ranks, int gran, long long ldx, long long ldy, int Tx, int vec_f32, int nslots,
+                    int ncols, const int32_t* cols, int live, int stop, double fill, const double* F, const double* Sb, const void* X, void* Y, int32_t* geom,
+                    int tab_cap, int32_t* tab_ft, int32_t* tab_f, int32_t* tab_s, int32_t* ntab) {
+  using namespace hook;
+  if (!c || !ranks || !X || !Y || !geom || !tab_ft || !tab_f || !tab_s || !ntab) return thin_refuse(PGPFA_THIN_BAD_ARG, "null argument");
+  if (kind < PGPFA_THIN_FT || kind > PGPFA_THIN_APPLY) return thin_refuse(PGPFA_THIN_BAD_ARG, "kind %d", kind);
+  const bool use_f = kind != PGPFA_THIN_S, use_s = kind == PGPFA_THIN_S || kind == PGPFA_THIN_APPLY;
+  if ((use_f && !F) || (use_s && !Sb)) return thin_refuse(PGPFA_THIN_BAD_ARG, "null argument");
+  if (p < 1 || nslots < 1 || ncols < 1 || tab_cap < 4) return thin_refuse(PGPFA_THIN_BAD_ARG, "invalid sizes");
+  if (gran != 4 && gran != 8 && gran != 16) return thin_refuse(PGPFA_THIN_BAD_ARG, "rank granularity %d (4, 8 or 16)", gran);
+  if (vec_f32 && kind == PGPFA_THIN_S) return thin_refuse(PGPFA_THIN_BAD_ARG, "Sb u has no single-precision vectors");
+  if (T < 4) return thin_refuse(PGPFA_THIN_REFUSED_T, "T = %d below 4 (the 4-bin runs of the vector loads are clamped to T - 4)", T);
+  if (Tf < T || Tf % 4 != 0) return thin_refuse(PGPFA_THIN_BAD_ARG, "slab size Tf = %d below T = %d or no multiple of 4", Tf, T);
+  // rank tables by the rule of build_lowrank
+  std::vector<int> rr(p), rk(p), roff(p + 1, 0);
+  int extent = 0;
+  for (int k = 0; k < p; ++k) {
+    if (ranks[k] < 1 || ranks[k] % 4 != 0) return thin_refuse(PGPFA_THIN_REFUSED_RANK, "rank %d of latent %d is no positive multiple of 4", ranks[k], k);
+    rr[k] = round_up(std::max(ranks[k], 1), gran);
+    rk[k] = round_up(rr[k], 16);
+    if (rk[k] > Tf) return thin_refuse(PGPFA_THIN_REFUSED_RANK, "latent %d: %d rank columns do not fit a slab of %d", k, rk[k], Tf);
+    roff[k + 1] = roff[k] + rr[k];
+    extent = std::max(extent, roff[k] + rk[k]);
+  }
+  const int rtot = roff[p];
+  if (rtot % 4 != 0) return thin_refuse(PGPFA_THIN_REFUSED_RANK, "rank total %d is no multiple of 4", rtot);
+  const int rpad = round_up(std::max(rtot, extent), NB);
+  const bool vec4 = T % 4 == 0;
+  if (use_f) {
+    if (Tx < T) return thin_refuse(PGPFA_THIN_REFUSED_TX, "latent stride Tx = %d below T = %d", Tx, T);
+    if (vec4 && Tx % 4 != 0) return thin_refuse(PGPFA_THIN_REFUSED_TX, "latent stride Tx = %d is no multiple of 4 where T is one (vector loads)", Tx);
+  } else {
+    Tx = T;
+  }
+  // leading dimensions: an n-vector holds (p - 1) Tx + T rows, a rank-space vector rtot written rows inside rpad
+  const long long nrows = (long long)(p - 1) * Tx + T;
+  const long long need_x = kind == PGPFA_THIN_FT || kind == PGPFA_THIN_APPLY ? nrows : rtot;
+  const long long need_y = kind == PGPFA_THIN_F || kind == PGPFA_THIN_APPLY ? nrows : rtot;
+  if (ldx < need_x || ldy < need_y) return thin_refuse(PGPFA_THIN_REFUSED_LD, "ldx = %lld, ldy = %lld below the rows read / written (%lld, %lld)", ldx, ldy, need_x, need_y);
+  if (ldx % 4 != 0 || ldy % 4 != 0) return thin_refuse(PGPFA_THIN_REFUSED_LD, "ldx = %lld, ldy = %lld: no multiples of 4 (vector loads and stores)", ldx, ldy);
+  if (ldx > (1ll << 24) || ldy > (1ll << 24)) return thin_refuse(PGPFA_THIN_REFUSED_LD, "leading dimension too large for a test");
+  const long long ldr = std::max(ldx, ldy);          // apply: leading dimension of the two rank-space intermediates
+  const long long ld_rank = kind == PGPFA_THIN_FT ? ldy : kind == PGPFA_THIN_F ? ldx : kind == PGPFA_THIN_S ? std::min(ldx, ldy) : ldr;
+  if (rpad > ld_rank) return thin_refuse(PGPFA_THIN_REFUSED_RPAD, "rpad = %d above the leading dimension %lld of the rank-space vectors", rpad, ld_rank);
+  if (cols) {
+    std::vector<char> seen(nslots, 0);
+    for (int i = 0; i < ncols; ++i) {
+      if (cols[i] < 0 || cols[i] >= nslots) return thin_refuse(PGPFA_THIN_REFUSED_COLS, "column list entry %d = %d outside the %d slots", i, cols[i], nslots);
+      if (seen[cols[i]]) return thin_refuse(PGPFA_THIN_REFUSED_COLS, "column list names slot %d twice", cols[i]);
+      seen[cols[i]] = 1;
+    }
+  } else if (ncols > nslots) {
+    return thin_refuse(PGPFA_THIN_REFUSED_COLS, "%d columns of %d slots", ncols, nslots);
+  }
+  if (live < -1 || live > ncols) return thin_refuse(PGPFA_THIN_REFUSED_LIVE, "live count %d outside 0..%d", live, ncols);
+  if (!c->mfma) return fail("the thin products run on the matrix cores (use_mfma = 1)");
+  const ThinTables tt = thin_tables(p, T, rr.data(), rk.data(), roff.data(), rtot);
+  if ((int)tt.ft.size() > tab_cap || (int)tt.f.size() > tab_cap || (int)tt.s.size() > tab_cap) return thin_refuse(PGPFA_THIN_BAD_ARG, "tables exceed tab_cap = %d", tab_cap);
+  for (int k = 0; k < p; ++k) { geom[k] = rr[k]; geom[p + k] = rk[k]; }
+  for (int k = 0; k <= p; ++k) geom[2 * p + k] = roff[k];
+  geom[3 * p + 1] = rtot; geom[3 * p + 2] = rpad;
+  std::copy(tt.ft.begin(), tt.ft.end(), tab_ft); std::copy(tt.f.begin(), tt.f.end(), tab_f); std::copy(tt.s.begin(), tt.s.end(), tab_s);
+  ntab[0] = (int)tt.ft.size() / 4; ntab[1] = (int)tt.f.size() / 4; ntab[2] = (int)tt.s.size() / 4;
+
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  // Inputs: the caller's array with SLACK more elements behind it, holding `fill`.  The kernels read whole 64-row tiles: up to 63 rows past the last
+  // group of FT and past bin T of the last slab column - values that are never stored.
+  constexpr size_t SLACK = 128;
+  auto filled = [&](double** dev, size_t count) -> int {
+    CHK(hb.get(dev, count + SLACK, 0));
+    const std::vector<double> h(count + SLACK, fill);
+    HIPC(hipMemcpy(*dev, h.data(), (count + SLACK) * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto input = [&](double** dev, const double* host, size_t count) -> int {
+    CHK(filled(dev, count));
+    HIPC(hipMemcpy(*dev, host, count * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto ints = [&](int** dev, const int* host, size_t count) -> int {
+    CHK(hb.get(dev, count, 0));
+    HIPC(hipMemcpy(*dev, host, count * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+  };
+  double *dF = nullptr, *dFT = nullptr, *dFbig = nullptr, *dSb = nullptr, *dX = nullptr;
+  int *d_ft = nullptr, *d_f = nullptr, *d_s = nullptr, *d_roff = nullptr, *d_cols = nullptr, *d_live = nullptr, *d_stop = nullptr;
+  CHK(ints(&d_ft, tt.ft.data(), tt.ft.size()));
+  CHK(ints(&d_f, tt.f.data(), tt.f.size()));
+  CHK(ints(&d_s, tt.s.data(), tt.s.size()));
+  CHK(ints(&d_roff, roff.data(), roff.size()));
+  if (cols) CHK(ints(&d_cols, cols, ncols));
+  if (live >= 0) CHK(ints(&d_live, &live, 1));
+  if (stop >= 0) CHK(ints(&d_stop, &stop, 1));
+  const bool x_f32 = vec_f32 && (kind == PGPFA_THIN_FT || kind == PGPFA_THIN_APPLY), y_f32 = vec_f32 && (kind == PGPFA_THIN_F || kind == PGPFA_THIN_APPLY);
+  {
+    // (floats: ldx is a multiple of 4, two to a double)
+    const size_t xd = x_f32 ? (size_t)nslots * ldx / 2 : (size_t)nslots * ldx;
+    CHK(input(&dX, static_cast<const double*>(X), xd));
+  }
+  if (use_f) {
+    // slabs, and FT built from them as build_lowrank does - over `fill` where production has zeros: outside the blocks
+    CHK(input(&dF, F, (size_t)p * Tf * Tf));
+    CHK(filled(&dFT, (size_t)p * T * rpad));
+    CHK(hb.get(&dFbig, (size_t)rtot * p * T, 0));
+    int rkmax = 0;
+    for (int k = 0; k < p; ++k) rkmax = std::max(rkmax, rk[k]);
+    HIPC(hipDeviceSynchronize());
+    hipLaunchKernelGGL(build_fbig_kernel, dim3(rkmax, p), dim3(128), 0, c->st, dF, Tf, T, d_roff, dFbig, p * T, dFT, rpad);
+    HIPC(hipGetLastError());
+  }
+  if (use_s) CHK(input(&dSb, Sb, (size_t)rpad * rpad));
+  void* dY = nullptr;
+  const size_t ybytes = (size_t)nslots * ldy * (y_f32 ? sizeof(float) : sizeof(double));
+  CHK(hook_output_bytes(hb, &dY, Y, ybytes));
+  double *dU = nullptr, *dV = nullptr;
+  const size_t mid = (size_t)nslots * ldr;
+  if (kind == PGPFA_THIN_APPLY) {
+    // the intermediates F^T t and Sb F^T t: `fill` everywhere (rows [rtot, rpad) "may hold anything"), a band behind each
+    const std::vector<double> h(mid, fill);
+    CHK(hook_output(hb, &dU, h.data(), mid));
+    CHK(hook_output(hb, &dV, h.data(), mid));
+  }
+  HIPC(hipDeviceSynchronize());
+  ThinP tp{};
+  tp.F = dF; tp.Tf = Tf; tp.T = T; tp.Tx = Tx; tp.FT = dFT; tp.ldft = rpad;
+  tp.cols = d_cols; tp.n_dev = d_live; tp.ncols = ncols; tp.skip = d_stop;
+  auto run_ft = [&](const double* x, long long lx, double* y, long long ly) {
+    tp.tab = d_ft; tp.X = x; tp.ldx = lx; tp.Y = y; tp.ldy = ly;
+    thin_launch_ft(tp, ntab[0], ncols, x_f32, c->st);
+  };
+  auto run_s = [&](const double* x, long long lx, double* y, long long ly) {
+    ThinP ts = tp;
+    ts.FT = dSb; ts.ldft = rpad; ts.T = rtot; ts.tab = d_s; ts.X = x; ts.ldx = lx; ts.Y = y; ts.ldy = ly;
+    thin_launch_s(ts, ntab[2], ncols, c->st);
+  };
+  auto run_f = [&](const double* x, long long lx, double* y, long long ly) {
+    tp.tab = d_f; tp.X = x; tp.ldx = lx; tp.Y = y; tp.ldy = ly;
+    thin_launch_f(tp, ntab[1], ncols, y_f32, c->st);
+  };
+  double* y = static_cast<double*>(dY);
+  if (kind == PGPFA_THIN_FT) run_ft(dX, ldx, y, ldy);
+  else if (kind == PGPFA_THIN_S) run_s(dX, ldx, y, ldy);
+  else if (kind == PGPFA_THIN_F) run_f(dX, ldx, y, ldy);
+  else { run_ft(dX, ldx, dU, ldr); run_s(dU, ldr, dV, ldr); run_f(dV, ldr, y, ldy); }
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  if (kind == PGPFA_THIN_APPLY) {
+    CHK(hook_collect("pgpfa_test_thin (F^T t)", dU, nullptr, mid));
+    CHK(hook_collect("pgpfa_test_thin (Sb u)", dV, nullptr, mid));
+  }
+  return hook_collect_bytes("pgpfa_test_thin", dY, Y, ybytes);
 }
 
 

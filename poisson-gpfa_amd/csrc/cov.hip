@@ -3,6 +3,7 @@
 #include "model.h"
 #include "split.h"
 #include "ytmix.h"
+#include "hook.h"
 
 using namespace pgpfa;
 
@@ -896,43 +897,8 @@ int pgpfa_set_posterior(pgpfa_ctx* c, int n, const int32_t* idx, const double* p
 
 
 // ---- test hooks: steps 2 and 3 of the split covariance sum on caller data, through the launch code above ------------------------------
-namespace {
-constexpr size_t HOOK_BAND = 1024;                      // doubles behind every output buffer of a hook that no kernel may touch
-constexpr double HOOK_BAND_VALUE = -12345.6789;
-
-struct HookBuffers {                                    // device allocations of one hook call, freed when it returns
-  std::vector<void*> ptrs;
-  ~HookBuffers() { for (void* q : ptrs) (void)hipFree(q); }
-  // `count` elements + `slack` zeroed ones behind them (the general GEMM reads whole 64-row tiles: rows past M of the last column of the last slot)
-  template <typename T>
-  int get(T** out, size_t count, size_t slack) {
-    void* q = nullptr;
-    const size_t bytes = (count + slack) * sizeof(T);
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return fail("out of device memory in a test hook (%zu bytes)", bytes); }
-    ptrs.push_back(q);
-    if (hipMemset(q, 0, bytes) != hipSuccess) return fail("hipMemset failed in a test hook");
-    *out = reinterpret_cast<T*>(q);
-    return 0;
-  }
-};
-
-// output buffer of `count` doubles holding the caller's prefill, with the band behind it
-int hook_output(HookBuffers& hb, double** dev, const double* host, size_t count) {
-  CHK(hb.get(dev, count + HOOK_BAND, 0));
-  HIPC(hipMemcpy(*dev, host, count * sizeof(double), hipMemcpyHostToDevice));
-  const std::vector<double> band(HOOK_BAND, HOOK_BAND_VALUE);
-  HIPC(hipMemcpy(*dev + count, band.data(), HOOK_BAND * sizeof(double), hipMemcpyHostToDevice));
-  return 0;
-}
-int hook_collect(const char* what, const double* dev, double* host, size_t count) {
-  std::vector<double> band(HOOK_BAND);
-  HIPC(hipMemcpy(host, dev, count * sizeof(double), hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(band.data(), dev + count, HOOK_BAND * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < HOOK_BAND; ++i)
-    if (band[i] != HOOK_BAND_VALUE) return fail("%s: a kernel wrote %zu doubles past the end of its output", what, i + 1);
-  return 0;
-}
-}  // namespace
+// (device buffers, prefilled outputs and the band behind them: hook.h)
+using namespace hook;
 
 int pgpfa_test_split_syrk(pgpfa_ctx* c, int nslots, int T, int p, int ract, int ldd, int ts, int sps, int tile, const float* D, double* part, int* tile_used,
                           int* ngroups) {

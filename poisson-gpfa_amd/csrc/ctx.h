@@ -26,6 +26,7 @@
 #include "types.h"
 #include "live.h"
 
+namespace pgpfa { struct ThinP; }                // thin.h
 using namespace pgpfa;
 
 
@@ -493,6 +494,10 @@ int upload_nosync(pgpfa_ctx* c, void* dev, const void* host, size_t bytes);
 int build_kinv(pgpfa_ctx* c);
 int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
+// work tables of thin.h's kernels, four ints per entry: ft (latent, first rank row, rank rows, rank offset), f (latent, first bin, rk, rank offset),
+// s (0, first row, rows, 0) - a function of the rank tables alone (build_lowrank uploads them; pgpfa_test_thin returns them)
+struct ThinTables { std::vector<int> ft, f, s; };
+ThinTables thin_tables(int p, int T, const int* rr, const int* rk, const int* roff, int rtot);
 int resolve_trials(pgpfa_ctx* c, int n, const int32_t* idx, Trials* out, bool distinct = false);
 void counts_changed(pgpfa_ctx* c, const std::vector<int>* trials);
 // Fails while a table is set that the entry point does not know.  allowed: the tables (TBL_*) it understands; with_dual_masked: those it understands
@@ -517,6 +522,10 @@ int prior_mv_all(pgpfa_ctx* c, int nb, const double* in, double* out, const doub
                  const int* cols = nullptr, int ncols = 0);
 int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale = 1.0);
 int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* Wt, long long sO, int nslots, double* ldet);
+// the launches of the preconditioner's three thin products (thin.h), shared by shared_solve and pgpfa_test_thin
+void thin_launch_ft(const pgpfa::ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream_t st);
+void thin_launch_s(const pgpfa::ThinP& ts, int ntab, int ncols, hipStream_t st);
+void thin_launch_f(const pgpfa::ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream_t st);
 int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, double* obj_sum, int32_t* iters, int32_t* status,
                const LooJob* loo = nullptr, const VarJob* var = nullptr);
 // cov.hip: posterior covariance blocks (dense and low-rank engines), blocks rebuilt on demand

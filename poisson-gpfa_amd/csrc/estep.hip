@@ -169,6 +169,28 @@ int pgpfa_laplace_hessian(pgpfa_ctx* c, int trial, const double* X, double* H) {
 }
 
 
+// The three launches of the low-rank preconditioner application (thin.h), as shared_solve issues them and as pgpfa_test_thin (core.hip) issues them on
+// caller data.  tp: the kernel's arguments, ntab: entries of tp.tab, ncols: the host's bound on the columns (tp.ncols), vec_f32: the n-vectors are floats.
+// VEC4 where the 4-bin runs of the n-vectors start on 32-byte boundaries: tp.T % 4 == 0.
+void thin_launch_ft(const ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream_t st) {
+  if (vec_f32) {
+    if (tp.T % 4 == 0) hipLaunchKernelGGL((thin_ft_kernel<true, float>), dim3(ntab, (ncols + 15) / 16), dim3(512), 0, st, tp);
+    else hipLaunchKernelGGL((thin_ft_kernel<false, float>), dim3(ntab, (ncols + 15) / 16), dim3(512), 0, st, tp);
+  } else if (tp.T % 4 == 0) hipLaunchKernelGGL(thin_ft_kernel<true>, dim3(ntab, (ncols + 15) / 16), dim3(512), 0, st, tp);
+  else hipLaunchKernelGGL(thin_ft_kernel<false>, dim3(ntab, (ncols + 15) / 16), dim3(512), 0, st, tp);
+}
+// Sb u: ts.FT = Sb, ts.T = rtot (a multiple of 4), one "latent"; always double vectors
+void thin_launch_s(const ThinP& ts, int ntab, int ncols, hipStream_t st) {
+  hipLaunchKernelGGL(thin_ft_kernel<true>, dim3(ntab, (ncols + 15) / 16), dim3(512), 0, st, ts);
+}
+void thin_launch_f(const ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream_t st) {
+  if (vec_f32) {
+    if (tp.T % 4 == 0) hipLaunchKernelGGL((thin_f_kernel<true, float>), dim3(ntab, (ncols + 15) / 16), dim3(256), 0, st, tp);
+    else hipLaunchKernelGGL((thin_f_kernel<false, float>), dim3(ntab, (ncols + 15) / 16), dim3(256), 0, st, tp);
+  } else if (tp.T % 4 == 0) hipLaunchKernelGGL(thin_f_kernel<true>, dim3(ntab, (ncols + 15) / 16), dim3(256), 0, st, tp);
+  else hipLaunchKernelGGL(thin_f_kernel<false>, dim3(ntab, (ncols + 15) / 16), dim3(256), 0, st, tp);
+}
+
 // Z <- P^-1 R for the nb slot vectors at once.  Dense plan: the shared preconditioner is ONE matrix, its explicit
 // inverse is formed once per chunk and applied with a single multi-RHS GEMM.  Low-rank plan: the same matrix in
 // Woodbury form, P^-1 v = Gb (eps v + F Sb F^T Gb v), with Gb the per-bin blocks of the mean curvature and Sb the
@@ -225,11 +247,7 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
     if (thin) {
       tp.tab = c->d_thin_ft; tp.X = c->Xt; tp.ldx = c->ld; tp.Y = c->Glt; tp.ldy = c->ld;
       thin_prof("F^T t");
-      if (vec_f32) {
-        if (c->T % 4 == 0) hipLaunchKernelGGL((thin_ft_kernel<true, float>), dim3(c->nthin_ft, (ng + 15) / 16), dim3(512), 0, c->st, tp);
-        else hipLaunchKernelGGL((thin_ft_kernel<false, float>), dim3(c->nthin_ft, (ng + 15) / 16), dim3(512), 0, c->st, tp);
-      } else if (c->T % 4 == 0) hipLaunchKernelGGL(thin_ft_kernel<true>, dim3(c->nthin_ft, (ng + 15) / 16), dim3(512), 0, c->st, tp);
-      else hipLaunchKernelGGL(thin_ft_kernel<false>, dim3(c->nthin_ft, (ng + 15) / 16), dim3(512), 0, c->st, tp);
+      thin_launch_ft(tp, c->nthin_ft, ng, vec_f32, c->st);
       prof_end(c);
     } else {
       CHK(gemm(c, true, y));
@@ -246,7 +264,7 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
       ThinP ts = tp;
       ts.FT = c->sU; ts.ldft = rpad; ts.T = c->rtot; ts.tab = c->d_thin_s; ts.X = c->Glt; ts.ldx = c->ld; ts.Y = c->KD; ts.ldy = c->ld;
       prof_begin(c, TAG_SOLVE, tp.n_dev ? 0.0 : 2.0 * (double)c->rtot * c->rtot * ng);
-      hipLaunchKernelGGL(thin_ft_kernel<true>, dim3(c->nthin_s, (ng + 15) / 16), dim3(512), 0, c->st, ts);
+      thin_launch_s(ts, c->nthin_s, ng, c->st);
       prof_end(c);
     } else {
       CHK(gemm(c, true, z));
@@ -259,11 +277,7 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
     if (thin) {
       tp.tab = c->d_thin_f; tp.X = c->KD; tp.ldx = c->ld; tp.Y = c->Xt; tp.ldy = c->ld;
       thin_prof("F v");
-      if (vec_f32) {
-        if (c->T % 4 == 0) hipLaunchKernelGGL((thin_f_kernel<true, float>), dim3(c->nthin_f, (ng + 15) / 16), dim3(256), 0, c->st, tp);
-        else hipLaunchKernelGGL((thin_f_kernel<false, float>), dim3(c->nthin_f, (ng + 15) / 16), dim3(256), 0, c->st, tp);
-      } else if (c->T % 4 == 0) hipLaunchKernelGGL(thin_f_kernel<true>, dim3(c->nthin_f, (ng + 15) / 16), dim3(256), 0, c->st, tp);
-      else hipLaunchKernelGGL(thin_f_kernel<false>, dim3(c->nthin_f, (ng + 15) / 16), dim3(256), 0, c->st, tp);
+      thin_launch_f(tp, c->nthin_f, ng, vec_f32, c->st);
       prof_end(c);
     } else {
       CHK(gemm(c, true, q));

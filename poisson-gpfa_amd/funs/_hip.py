@@ -88,6 +88,9 @@ _SIGNATURES = {
                               ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)],
     'pgpfa_test_split_latent_sums': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_longlong, ct.c_int, ct.c_int, ct.c_longlong, ct.c_int, ct.c_int,
                                      c_double_p, ct.POINTER(ct.c_float), c_double_p, c_double_p],
+    'pgpfa_test_thin': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_int32_p, ct.c_int, ct.c_longlong, ct.c_longlong, ct.c_int, ct.c_int, ct.c_int,
+                        ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_double, c_double_p, c_double_p, ct.c_void_p, ct.c_void_p, c_int32_p, ct.c_int,
+                        c_int32_p, c_int32_p, c_int32_p, c_int32_p],
     'pgpfa_bench_syrk': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_double_p, c_double_p],
     'pgpfa_bench_potrf_diag': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, c_double_p],
     'pgpfa_gemm_shape_report': [ct.c_void_p, ct.c_char_p, ct.c_int],
@@ -709,6 +712,59 @@ class Context:
         check(self.lib.pgpfa_test_split_latent_sums(self.h, nslots, int(rk), int(kw), int(T), int(lda), A.shape[1], int(row_off), int(ldd), D.shape[1], int(sps),
                                                     int(cross_kernel), dptr(A), D.ctypes.data_as(ct.POINTER(ct.c_float)), dptr(S), dptr(X)))
         return S[:rk * rk].reshape(rk, rk), X[:rk * T].reshape(T, rk), (S[rk * rk:], X[rk * T:])
+
+    THIN_KINDS = {'ft': 0, 's': 1, 'f': 2, 'apply': 3}
+    THIN_REFUSALS = {100: 'bad_arg', 101: 'T', 102: 'rank', 103: 'Tx', 104: 'ld', 105: 'rpad', 106: 'cols', 107: 'live'}      # PGPFA_THIN_* of pgpfa.h
+
+    def test_thin(self, kind, T, Tf, ranks, gran, X, Y, Tx=None, F=None, Sb=None, f32=False, cols=None, ncols=None, live=None, stop=None, fill=0.0):
+        """The thin products of the low-rank preconditioner (pgpfa_test_thin) on caller data: kind 'ft' (u = F^T t), 's' (v = Sb u), 'f' (y = F v) or
+        'apply' (the three in a row).  X (nslots, ldx) input and Y (nslots, ldy) output buffer with the caller's prefill, one row per slot; n-vectors
+        (input of 'ft' / 'apply', output of 'f' / 'apply') are float32 with f32, everything else float64.  F (p, Tf, Tf) indexed [latent, column, bin],
+        Sb (rpad, rpad) indexed [k, m].  cols: slot list (None: identity over ncols slots), live: device-side live count, stop: stop flag value.
+        Returns (Y as the device left it, info): info holds rr, rk, roff, rtot, rpad and the tables ft, f, s as (entries, 4) arrays.
+        A refused geometry raises HipBackendError with .rc (the return code) and .refusal (its name in THIN_REFUSALS)."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int32)
+        p = len(ranks)
+        k = self.THIN_KINDS[kind]
+        xt = np.float32 if f32 and kind in ('ft', 'apply') else np.float64
+        yt = np.float32 if f32 and kind in ('f', 'apply') else np.float64
+        X = np.ascontiguousarray(X, dtype=xt)
+        out = np.array(Y, dtype=yt, order='C', copy=True)
+        assert X.ndim == 2 and out.ndim == 2 and X.shape[0] == out.shape[0]
+        nslots = X.shape[0]
+        cl = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        nc = int(ncols) if ncols is not None else (nslots if cl is None else len(cl))
+        assert cl is None or len(cl) == nc
+        Fp = None
+        if F is not None:
+            F = as_f64(F)
+            assert F.shape == (p, int(Tf), int(Tf))
+            Fp = dptr(F)
+        geom = np.zeros(3 * p + 3, dtype=np.int32)
+        cap = 4 * (p * (16 + (max(int(T), 1) + 255) // 256) + 1024)
+        tabs = [np.zeros(cap, dtype=np.int32) for _ in range(3)]
+        ntab = np.zeros(3, dtype=np.int32)
+        Sp = None
+        if Sb is not None:
+            Sb = as_f64(Sb)
+            if int(gran) in (4, 8, 16) and np.all(ranks >= 1):                 # (else the hook refuses before it reads anything)
+                rr = (ranks + int(gran) - 1) // int(gran) * int(gran)
+                roff = np.concatenate([[0], np.cumsum(rr)])
+                rpad = (max(int(roff[-1]), int(np.max(roff[:-1] + (rr + 15) // 16 * 16))) + 127) // 128 * 128
+                assert Sb.shape == (rpad, rpad), (Sb.shape, rpad)
+            Sp = dptr(Sb)
+        rc = self.lib.pgpfa_test_thin(self.h, k, p, int(T), int(Tf), iptr(ranks), int(gran), X.shape[1], out.shape[1], int(T if Tx is None else Tx), int(bool(f32)),
+                                      nslots, nc, iptr(cl), -1 if live is None else int(live), -1 if stop is None else int(stop), float(fill), Fp, Sp,
+                                      X.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p), iptr(geom), cap, iptr(tabs[0]), iptr(tabs[1]), iptr(tabs[2]),
+                                      iptr(ntab))
+        if rc != 0:
+            err = HipBackendError(self.lib.pgpfa_last_error().decode('utf-8', 'replace'))
+            err.rc = rc
+            err.refusal = self.THIN_REFUSALS.get(rc)
+            raise err
+        info = dict(rr=geom[:p].copy(), rk=geom[p:2 * p].copy(), roff=geom[2 * p:3 * p + 1].copy(), rtot=int(geom[3 * p + 1]), rpad=int(geom[3 * p + 2]),
+                    ft=tabs[0][:4 * ntab[0]].reshape(-1, 4).copy(), f=tabs[1][:4 * ntab[1]].reshape(-1, 4).copy(), s=tabs[2][:4 * ntab[2]].reshape(-1, 4).copy())
+        return out, info
 
     def bench_mfma_peak(self, iters=20000):
         tf = ct.c_double(0.0)

@@ -775,7 +775,7 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   // computed on 16-blocks that never straddle a latent (assemble_b, in the PADDED index space roff16 / blk_lat / blk_col) and stored at its
   // compact place (cmap), and the panel of L^-T that yt_mix stages keeps padded rows (gathered through the same map).
   // (compact offsets need the preconditioner's three products as thin.h's kernels: the general GEMM's row-tile tables start tiles on multiples of 16)
-  const bool thin_all = c->thin_products >= 2 && c->mfma && T >= 4;
+  const bool thin_all = thin_possible(c) && c->thin_products >= 2;
   const int G = ((c->rank_gran == 4 || c->rank_gran == 8) && thin_all) ? c->rank_gran : 16;
   c->rk.assign(p, 0);
   c->roff.assign(p + 1, 0);
@@ -862,6 +862,13 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   c->info["lowrank_compact"] = c->rank_compact ? 1.0 : 0.0;
   c->flr32_valid = false;
   return 0;
+}
+
+// what the kernels that know the compact offsets are told of the tables above (ctx.h)
+BLayout b_layout(const pgpfa_ctx* c) {
+  const int n64 = round_up(c->rtot16, 64) / 64, d64 = c->rpad / 64;
+  return c->rank_compact ? BLayout{n64, n64 * (n64 + 1) / 2, c->d_cmap, c->d_roff16, c->d_nrtab, round_up(c->rtot16, (int)NB)}
+                         : BLayout{d64, d64 * (d64 + 1) / 2, nullptr, c->d_roff, nullptr, 0};
 }
 
 // ---- test hook: the three thin products of the low-rank preconditioner on caller data, through thin_tables and the launches of shared_solve ---------

@@ -231,15 +231,117 @@ static int split_latent_sums(pgpfa_ctx* c, const double* A0, long long sM, int l
   return 0;
 }
 
-// Sum-only covariance output by the exact split form (split.h): Pacc[k] += sum over the chunk's slots of Y~_k Y~_k^T + eps diag(G_t[k][k])
-// from L^-T (lw.Mt), Yt (lw.H) and the per-bin blocks G (c->Gbin), without the full-width FP64 product.  Also writes post_vsm.
-static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, int Ts, bool skip_zero_cols, int ctile, bool fused) {
-  const int T = c->T, p = c->p, Tp = c->Tp, rpad = c->rpad;
-  const long long sW = (long long)T * p * p;
+// B = I + F^T Wt F (ctx.h).  The shared preconditioner's one slot gives the grid (npairs, (1 + AB_SLOTS - 1) / AB_SLOTS) = (npairs, 1) it has always had.
+template <typename TB>
+int assemble_rxr(pgpfa_ctx* c, const CholWS& view, int nb, const TB* F, const double* Wt, long long sW, const int* slots) {
+  const int rpad = c->rpad;
+  const BLayout L = b_layout(c);
+  TB* Bm = reinterpret_cast<TB*>(view.H);                  // (a single-precision view carries its strides in floats)
+  hipLaunchKernelGGL(assemble_b_kernel_t<TB>, dim3(L.npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, Bm, view.sH, rpad, L.nblk64, F, c->Tp, c->T, c->p,
+                     c->d_blk_lat, c->d_blk_col, Wt, sW, slots, nb, L.cmap);
+  if (L.cmap && rpad > c->rtot)
+    hipLaunchKernelGGL(pad_identity_kernel<TB>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, Bm, view.sH, rpad, c->rtot, rpad, view.nact, (int)NB, slots);
+  HIPC(hipGetLastError());
+  return 0;
+}
+template int assemble_rxr<double>(pgpfa_ctx*, const CholWS&, int, const double*, const double*, long long, const int*);
+template int assemble_rxr<float>(pgpfa_ctx*, const CholWS&, int, const float*, const double*, long long, const int*);
+
+namespace {
+
+// Clear the L^-T slabs of `w` (T = float: the slabs viewed as floats), then L^-T.  The slab holds whatever its last use left - another rank layout, the
+// factor of a dense pass -: all of it is cleared, or, with lower_ctile > 0 (FP64; every consumer starts at the latent's own columns), only the strictly
+// lower entries of the p rectangles they read.
+template <typename T>
+int clear_and_invert(pgpfa_ctx* c, const CholWS& w, int nb, int lower_ctile = 0) {
+  const int rpad = c->rpad;
+  constexpr bool f32 = sizeof(T) == 4;
+  if constexpr (f32)
+    hipLaunchKernelGGL(fill_slabs_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, reinterpret_cast<float*>(w.Mt), w.sM,
+                       (size_t)rpad * rpad, 0.0f);
+  else if (lower_ctile > 0)
+    hipLaunchKernelGGL(clear_lower_reads_kernel, dim3(c->p, nb), dim3(256), 0, c->st, w.Mt, w.sM, rpad, c->d_roff, lower_ctile, c->ident);
+  else
+    hipLaunchKernelGGL(fill_slabs_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, w.Mt, w.sM, (size_t)rpad * rpad, 0.0);
+  return inverse_t(c, w, c->ident, nb, f32);
+}
+
+// What one low-rank covariance pass derives from its arguments, the options and the plan, once per call.
+struct CovPass {
+  int nb;
+  bool want_vsmgp, accumulate;
+  int ract;                        // columns of Yt that are not identically zero (rpad rounds to 128 for the factor)
+  long long sW;
+  // sum-only accumulation by the split form (split.h)?  Decided by the relative size of the mixing correction of this chunk, max_t eps ||Wt_t||_inf,
+  // measured with the per-bin blocks and read back just before the mixing pass (info key "last_eps_wt_norm")
+  // (want_vsmgp passes run the FP64 engine whatever dual_f32 says - it only concerns the dual's evaluations - and under laplace_f32 everything the
+  //  split form touches is FP64 as well, so the split form does not ask)
+  bool split_candidate;
+  unsigned* norm_bits;             // (scratch word: the inner solves are over)
+  // Mixed precision (option dual_f32, dual-variational evaluations only): B, its Cholesky factor, L^-T and Yt = F L^-T - the O(T r^2) and
+  // O(r^3) parts - run on the FP32 matrix cores (twice the FP64 rate, half the bytes); log det and the per-bin covariance blocks are
+  // accumulated in FP64 from the single-precision factors.  (dual_f32 = 2: B is still assembled in FP64 and rounded once.)
+  // Option laplace_f32 (want_vsmgp passes: the Laplace E-step and the blocks rebuilt on demand): the same single-precision B, factor and L^-T; L^-T is then
+  // widened into the FP64 slab (widen_upper_f64_kernel) and everything from Yt on is the FP64 path, unchanged.  A chunk with a non-positive pivot in
+  // the single-precision factorisation is redone in FP64.
+  int f32_mode;
+  bool f32, lap32;
+  // Yt = F L^-T: L^-T is upper triangular, so the rows of Yt that belong to latent k vanish left of column roff[k].  When the consumer knows
+  // the same offsets and takes those entries as zeros without reading them (the mixing pass up to 16 latents, the matrix-core post_vsm
+  // beyond 10) the product skips the whole 128-column tiles left of it: ~45 % of the flops and stores.
+  bool skip_zero_cols;
+  // granularity of that skipping: the mixing passes take any multiple of 16 (the ranks are padded to 16, so exactly the zero columns are left
+  // out: 128-column tiles kept 64 of them per latent on average - 18 % of the product and of the pass at config 3), the matrix-core post_vsm whole
+  // 128-column tiles
+  int ctile;
+  // rows (k, t) of the Yt slab sit at k * Ts + t with Ts = T rounded up to 16 when the slab is tall enough: the 64-bin runs of the mixing pass and
+  // the product's stores then start on 128-byte lines (at T = 500 every run straddled one: 1.4x the bytes fetched, PMC)
+  int Ts;
+  CholWS lw;                       // the dense engine's slabs as scratch, ld = rpad: B / L, then Yt in the H slabs, L^-T in the Mt slabs
+  CholWS lwf;                      // single-precision views: B / L in the Mt slabs, L^-T and Yt in the H slabs
+  float* Ytf;                      // Yt (float, n x ract, ld = c->ld) behind L^-T in the same slab
+};
+
+CovPass cov_pass(const pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, bool allow_lap32) {
+  const int T = c->T, p = c->p;
+  CovPass P{};
+  P.nb = nb; P.want_vsmgp = want_vsmgp; P.accumulate = accumulate;
+  P.ract = round_up(c->rtot, 16);
+  P.sW = (long long)T * p * p;
+  P.split_candidate = want_vsmgp && accumulate && c->split_cov && c->mfma && (p <= 16 || (p <= 20 && c->mix_wide));
+  P.norm_bits = reinterpret_cast<unsigned*>(c->pcg_ratio);
+  P.f32_mode = want_vsmgp ? (allow_lap32 ? c->laplace_f32 : 0) : c->dual_f32;
+  P.f32 = P.f32_mode != 0;
+  P.lap32 = P.f32 && want_vsmgp;
+  P.skip_zero_cols = want_vsmgp ? p <= 16 : (p > 10 && c->vsm_mfma);
+  P.ctile = (want_vsmgp && p <= 16) ? 16 : (int)GBN;
+  P.Ts = (c->slab_row_align && p * round_up(T, 16) <= c->ld) ? round_up(T, 16) : T;
+  P.lw = lowrank_view(c, c->ws);
+  P.lwf = P.lw;
+  if (P.f32) {
+    P.lwf.H = P.lw.Mt; P.lwf.sH = 2 * P.lw.sM;
+    P.lwf.Mt = P.lw.H; P.lwf.sM = 2 * P.lw.sH;
+    P.lwf.sD = 2 * P.lw.sD; P.lwf.sP = 2 * P.lw.sP;
+    P.Ytf = reinterpret_cast<float*>(P.lw.H) + (size_t)c->rpad * c->rpad;
+  }
+  return P;
+}
+
+// ---- the split form of the sum-only output (split.h): Pacc[k] += sum over the chunk's slots of Y~_k Y~_k^T + eps diag(G_t[k][k]) from L^-T (lw.Mt),
+// Yt (lw.H) and the per-bin blocks G (c->Gbin), without the full-width FP64 product.  Also writes post_vsm.
+
+// scratch: S parts [NS][r_k^2] | X parts [NG][r_k T] | Ssum | Xsum | Z | T1 [p][T^2] | Xfull [p][T^2]; a latent's padded rank r_k can reach
+// T rounded up to 16, so the first five are laid out in units of tq = round_up(T, 16)^2
+struct SplitScratch {
+  double *Spart, *Xpart, *Ssum, *Xsum, *Zb, *T1, *Xfull;
+  float* D;                        // the correction eps Wt Yt, behind Yt in every slot's slab
+  long long sD;                    // slab stride in floats
+  int ldd;
+};
+
+int split_scratch(pgpfa_ctx* c, const CholWS& lw, SplitScratch* s) {
+  const int T = c->T, p = c->p;
   const size_t tt = (size_t)T * T;
-  (void)skip_zero_cols;
-  // scratch: S parts [NS][r_k^2] | X parts [NG][r_k T] | Ssum | Xsum | Z | T1 [p][T^2] | Xfull [p][T^2]; a latent's padded rank r_k can reach
-  // T rounded up to 16, so the first five are laid out in units of tq = round_up(T, 16)^2
   constexpr int NS = SPLIT_NS, NG = PACC_SPLITS + 1;
   const size_t tq = (size_t)round_up(T, 16) * round_up(T, 16);
   if (!c->split_buf) {
@@ -247,18 +349,27 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
     if (hipMalloc((void**)&c->split_buf, len * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); c->split_buf = nullptr; return fail("out of device memory for the split accumulation (%zu bytes)", len * sizeof(double)); }
     c->bytes += len * sizeof(double);
   }
-  double* Spart = c->split_buf;
-  double* Xpart = Spart + (size_t)NS * tq;
-  double* Ssum = Xpart + (size_t)NG * tq;
-  double* Xsum = Ssum + tq;
-  double* Zb = Xsum + tq;
-  double* T1 = Zb + tq;
-  double* Xfull = T1 + (size_t)p * tt;
-  float* D = reinterpret_cast<float*>(lw.H + (size_t)c->ld * rpad);          // behind Yt in every slot's slab
-  const long long sD = 2 * (long long)lw.sH;                                   // slab stride in floats
-  const int ldd = c->ld;
-  // 1. mixing pass: post_vsm and the correction D = eps Wt Yt (single precision); Yt itself stays
-  int mix_form = 0;                                        // info key "last_mix_form": which of the kernels below ran
+  s->Spart = c->split_buf;
+  s->Xpart = s->Spart + (size_t)NS * tq;
+  s->Ssum = s->Xpart + (size_t)NG * tq;
+  s->Xsum = s->Ssum + tq;
+  s->Zb = s->Xsum + tq;
+  s->T1 = s->Zb + tq;
+  s->Xfull = s->T1 + (size_t)p * tt;
+  s->D = reinterpret_cast<float*>(lw.H + (size_t)c->ld * c->rpad);
+  s->sD = 2 * (long long)lw.sH;
+  s->ldd = c->ld;
+  return 0;
+}
+
+// 1. mixing pass: post_vsm and the correction D = eps Wt Yt (single precision); Yt itself stays.  Returns the info key "last_mix_form": which of the
+// kernels ran (4: with the product, ytmix.h - Yt was not formed; 5: mix_vsm_wide2; 3 / 2 / 1: mix_slot3 / 2 / 1; 0: mix_vsm_split).
+int mix_split(pgpfa_ctx* c, const CovPass& P, const SplitScratch& s, bool fused) {
+  const int T = c->T, p = c->p, Tp = c->Tp, rpad = c->rpad, nb = P.nb, ract = P.ract, Ts = P.Ts, ctile = P.ctile, ldd = s.ldd;
+  const long long sW = P.sW, sD = s.sD;
+  const CholWS& lw = P.lw;
+  float* D = s.D;
+  int mix_form = 0;
   double mix_cols = 0.0;                                   // columns of Yt a latent's rows really hold: left of its first column tile nothing was written
   for (int k = 0; k < p; ++k) mix_cols += std::max(0, ract - (ctile > 0 ? (c->roff[k] / ctile) * ctile : 0));
   // (bytes: the columns of Yt that hold something read once in FP64; D - dense, the mixing couples the latents - written once in FP32)
@@ -275,8 +386,9 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
         a.D = D; a.sD = sD; a.ldd = ldd; a.G = c->Gbin; a.sG = sW;
         a.T = T; a.p = p; a.ract = ract; a.nbx = (T + YTM_BINS - 1) / YTM_BINS; a.nslots = nb; a.eps = c->eps;
         a.vsm = c->vsm; a.slots = c->ident; a.trial_of_slot = c->trial_of_slot; a.ts = Ts; a.dbg = c->yt_mix_dbg;
-        a.roff = c->rank_compact ? c->d_roff16 : c->d_roff; a.cmap = c->rank_compact ? c->d_cmap : nullptr; a.nrtab = c->rank_compact ? c->d_nrtab : nullptr;
-        a.ncmap = c->rank_compact ? round_up(c->rtot16, (int)NB) : 0;
+        const BLayout L = b_layout(c);
+        a.roff = L.roff_padded; a.cmap = L.cmap; a.nrtab = L.nrtab;
+        a.ncmap = L.ncmap_rows;
         if (ytmix_lds(PW) + (size_t)a.ncmap * sizeof(int) > (size_t)160 * 1024) a.ncmap = 0;     // (the kernel then reads the map from memory)
         const size_t lds = ytmix_lds(PW) + (size_t)a.ncmap * sizeof(int);
         a.zero16 = c->zero16;
@@ -329,14 +441,18 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
   });
   prof_end(c);
   }
-  c->info["last_mix_form"] = (double)mix_form;
-  // 2. the full-width term on the FP16 matrix cores: partial sums per (latent, group of slots) into c->ppart
-  int sps = 0, ngroups = 0, tile_used = 0;
-  CHK(split_syrk_launch(c, D, sD, ldd, Ts, T, p, ract, nb, 0, c->syrk_tile, c->ppart, &tile_used, &sps, &ngroups));
-  c->info["last_syrk_tile"] = (double)tile_used;
-  c->info["last_split_sps"] = (double)sps;
-  // 3. per latent: S_k = sum_r A A^T (r_k x r_k), X_k = sum_r A D_k^T (r_k x T) with A = rows of latent k of L^-T right of column
-  //    roff_k (it is upper triangular), both as segmented-K products over groups of slots (split_latent_sums); then T1 = F S F^T and Xfull = F X
+  return mix_form;
+}
+
+// 3. per latent: S_k = sum_r A A^T (r_k x r_k), X_k = sum_r A D_k^T (r_k x T) with A = rows of latent k of L^-T right of column
+//    roff_k (it is upper triangular), both as segmented-K products over groups of slots (split_latent_sums); then T1 = F S F^T and Xfull = F X
+int split_latent_terms(pgpfa_ctx* c, const CovPass& P, const SplitScratch& s, int sps, bool* cross_ran_out) {
+  const int T = c->T, p = c->p, Tp = c->Tp, rpad = c->rpad, nb = P.nb, ract = P.ract, Ts = P.Ts, ldd = s.ldd;
+  const size_t tt = (size_t)T * T;
+  const long long sD = s.sD;
+  const CholWS& lw = P.lw;
+  float* D = s.D;
+  double *Spart = s.Spart, *Xpart = s.Xpart, *Ssum = s.Ssum, *Xsum = s.Xsum, *Zb = s.Zb, *T1 = s.T1, *Xfull = s.Xfull;
   bool cross_ran = false;
   for (int k = 0; k < p; ++k) {
     // (compact rank offsets: the rk rows taken from r0 on end in the next latent's first rows - they meet zero columns of F_k in T1 and Xfull
@@ -367,122 +483,91 @@ static int accumulate_split(pgpfa_ctx* c, const CholWS& lw, int nb, int ract, in
     xf.B = Xsum; xf.ldb = rk; xf.C = Xfull + (size_t)k * tt; xf.ldc = T; xf.N = T;
     CHK(gemm(c, true, xf));
   }
+  *cross_ran_out = cross_ran;
+  return 0;
+}
+
+int accumulate_split(pgpfa_ctx* c, const CovPass& P, bool fused) {
+  const int T = c->T, p = c->p;
+  SplitScratch s{};
+  CHK(split_scratch(c, P.lw, &s));
+  c->info["last_mix_form"] = (double)mix_split(c, P, s, fused);
+  // 2. the full-width term on the FP16 matrix cores: partial sums per (latent, group of slots) into c->ppart
+  int sps = 0, ngroups = 0, tile_used = 0;
+  CHK(split_syrk_launch(c, s.D, s.sD, s.ldd, P.Ts, T, p, P.ract, P.nb, 0, c->syrk_tile, c->ppart, &tile_used, &sps, &ngroups));
+  c->info["last_syrk_tile"] = (double)tile_used;
+  c->info["last_split_sps"] = (double)sps;
+  bool cross_ran = false;
+  CHK(split_latent_terms(c, P, s, sps, &cross_ran));
   c->info["last_cross_kernel"] = cross_ran ? 1.0 : 0.0;
   // 4. Pacc += eps diag + T1 - Xfull - Xfull^T + sum of the FP16 partial sums
-  {
-    const int nt64 = (T + PACC_TS - 1) / PACC_TS;
-    hipLaunchKernelGGL(pacc_split_reduce_kernel, dim3(nt64 * (nt64 + 1) / 2, p), dim3(256), 0, c->st, T1, Xfull, c->ppart, ngroups, c->Gbin, sW, nb, c->eps, T, Tp,
-                       p, c->Pacc);
-  }
+  const int nt64 = (T + PACC_TS - 1) / PACC_TS;
+  hipLaunchKernelGGL(pacc_split_reduce_kernel, dim3(nt64 * (nt64 + 1) / 2, p), dim3(256), 0, c->st, s.T1, s.Xfull, c->ppart, ngroups, c->Gbin, P.sW, P.nb, c->eps, T, c->Tp,
+                     p, c->Pacc);
   HIPC(hipGetLastError());
   c->pacc_used = true;
   return 0;
 }
 
-// Covariance blocks through the low-rank form of the prior (see model.h): per slot an r x r SPD system
-// B = I + F^T Wt F instead of the n x n Hessian.  Uses the dense engine's slabs as scratch (ld = rpad views).
-// logdet_out (optional, host, nb entries): log det of the posterior precision K^-1 + scatter(W) of every slot,
-//   = -sum_k log det K_k + sum_t log det(I + eps W_t) + log det(I + F^T Wt F)   (Sylvester; K_k = eps I + F_k F_k^T)
-// (allow_lap32 = false: the FP64 pass that redoes a chunk whose single-precision factorisation failed under option laplace_f32)
-// ld_dev (optional, device, nb entries; the Laplace log evidence): log det of the posterior precision + sum_k log det K_k = the last two terms above,
-//   reduced per slot by one kernel behind the factorisation; nothing is read back here.  FP64 factor only: the E-step refuses it under laplace_f32.
-static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, bool allow_lap32, double* ld_dev) {
-  const int T = c->T, p = c->p, Tp = c->Tp, pp = p * p;
-  const int rpad = c->rpad;
-  const int ract = round_up(c->rtot, 16);          // columns of Yt that are not identically zero (rpad rounds to 128 for the factor)
-  const long long sW = (long long)T * pp;
-  c->last_cov_lowrank = true;
-  // a. per-bin blocks G = (I + eps W)^-1, Wt = W G
-  CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, (logdet_out || ld_dev) ? c->ldet_buf : nullptr));
-  // sum-only accumulation by the split form (split.h)?  Decided by the relative size of the mixing correction of this chunk,
-  // max_t eps ||Wt_t||_inf, measured here and read back just before the mixing pass (info key "last_eps_wt_norm")
-  // (want_vsmgp passes run the FP64 engine whatever dual_f32 says - it only concerns the dual's evaluations - and under laplace_f32 everything the
-  //  split form touches is FP64 as well, so the split form does not ask)
-  const bool split_candidate = want_vsmgp && accumulate && c->split_cov && c->mfma && (p <= 16 || (p <= 20 && c->mix_wide));
-  unsigned* norm_bits = reinterpret_cast<unsigned*>(c->pcg_ratio);         // (scratch word: the inner solves are over)
-  if (split_candidate || c->measure_mix) {
-    HIPC(hipMemsetAsync(norm_bits, 0, 4 * sizeof(unsigned), c->st));
-    const long long nblk = (long long)nb * T;
-    hipLaunchKernelGGL(block_norm_max_kernel, dim3((unsigned)std::min<long long>((nblk * p + 255) / 256, 2048)), dim3(256), 0, c->st, c->Wt, nblk, p, c->eps, norm_bits,
-                       reinterpret_cast<double*>(norm_bits + 2));
+// ---- the phases of the low-rank covariance pass, in the order posterior_blocks_lowrank_impl calls them ---------------------------------------------
+
+// a. per-bin blocks G = (I + eps W)^-1, Wt = W G [, their log-dets]; and what the split form's verdict will need, max and mean square over the chunk's
+//    bins of eps ||Wt_t||_inf
+int blocks_and_norm(pgpfa_ctx* c, const CovPass& P, double* ldet) {
+  CHK(bin_blocks(c, c->W, P.sW, c->Gbin, c->Wt, P.sW, P.nb, ldet));
+  if (P.split_candidate || c->measure_mix) {
+    HIPC(hipMemsetAsync(P.norm_bits, 0, 4 * sizeof(unsigned), c->st));
+    const long long nblk = (long long)P.nb * c->T;
+    hipLaunchKernelGGL(block_norm_max_kernel, dim3((unsigned)std::min<long long>((nblk * c->p + 255) / 256, 2048)), dim3(256), 0, c->st, c->Wt, nblk, c->p, c->eps,
+                       P.norm_bits, reinterpret_cast<double*>(P.norm_bits + 2));
   }
-  // b. B = I + F^T Wt F into the factor slabs viewed with ld = rpad; factor; L^-T
-  CholWS lw = c->ws;
-  lw.ld = rpad; lw.npad = rpad; lw.nact = round_up(c->rtot, 64);
-  // (compact rank offsets: the tiles of B are walked in the padded index space - rtot16 rows - and stored through cmap; build_lowrank)
-  const int nblk64 = c->rank_compact ? round_up(c->rtot16, 64) / 64 : rpad / 64, npairs = nblk64 * (nblk64 + 1) / 2;
-  const int* cmap = c->rank_compact ? c->d_cmap : nullptr;
-  // Mixed precision (option dual_f32, dual-variational evaluations only): B, its Cholesky factor, L^-T and Yt = F L^-T - the O(T r^2) and
-  // O(r^3) parts - run on the FP32 matrix cores (twice the FP64 rate, half the bytes); log det and the per-bin covariance blocks are
-  // accumulated in FP64 from the single-precision factors.  (dual_f32 = 2: B is still assembled in FP64 and rounded once.)
-  // Option laplace_f32 (want_vsmgp passes: the Laplace E-step and the blocks rebuilt on demand): the same single-precision B, factor and L^-T; L^-T is then
-  // widened into the FP64 slab (widen_upper_f64_kernel) and everything from Yt on is the FP64 path below, unchanged.  A chunk with a non-positive pivot in
-  // the single-precision factorisation is redone in FP64.
-  const int f32_mode = want_vsmgp ? (allow_lap32 ? c->laplace_f32 : 0) : c->dual_f32;
-  const bool f32 = f32_mode != 0;
-  const bool lap32 = f32 && want_vsmgp;
-  c->info["last_cov_f32"] = lap32 ? 1.0 : 0.0;
-  // Yt = F L^-T: L^-T is upper triangular, so the rows of Yt that belong to latent k vanish left of column roff[k].  When the consumer knows
-  // the same offsets and takes those entries as zeros without reading them (the mixing pass up to 16 latents, the matrix-core post_vsm
-  // beyond 10) the product skips the whole 128-column tiles left of it: ~45 % of the flops and stores.
-  const bool skip_zero_cols = want_vsmgp ? p <= 16 : (p > 10 && c->vsm_mfma);
-  // granularity of that skipping: the mixing passes take any multiple of 16 (the ranks are padded to 16, so exactly the zero columns are left
-  // out: 128-column tiles kept 64 of them per latent on average - 18 % of the product and of the pass at config 3), the matrix-core post_vsm whole
-  // 128-column tiles
-  const int ctile = (want_vsmgp && p <= 16) ? 16 : (int)GBN;
-  // rows (k, t) of the Yt slab sit at k * Ts + t with Ts = T rounded up to 16 when the slab is tall enough: the 64-bin runs of the mixing pass and
-  // the product's stores then start on 128-byte lines (at T = 500 every run straddled one: 1.4x the bytes fetched, PMC)
-  const int Ts = (c->slab_row_align && p * round_up(T, 16) <= c->ld) ? round_up(T, 16) : T;
-  CholWS lwf = lw;                                         // single-precision views: B / L in the Mt slabs, L^-T and Yt in the H slabs
-  float* Ytf = nullptr;
-  if (f32) {
-    lwf.H = lw.Mt; lwf.sH = 2 * lw.sM;
-    lwf.Mt = lw.H; lwf.sM = 2 * lw.sH;
-    lwf.sD = 2 * lw.sD; lwf.sP = 2 * lw.sP;
-    Ytf = reinterpret_cast<float*>(lw.H) + (size_t)rpad * rpad;
-    if (!c->Flr32) {
-      if (hipMalloc((void**)&c->Flr32, ((size_t)Tp * Tp * p + 256 * (size_t)Tp) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail("out of device memory for the single-precision factors"); }
-      c->flr32_valid = false;
-    }
-    if (!c->flr32_valid) {
-      const size_t nf = (size_t)Tp * Tp * p;
-      hipLaunchKernelGGL(cvt_f32_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->st, c->Flr, c->Flr32, nf);
-      c->flr32_valid = true;
-    }
+  return 0;
+}
+
+// the single-precision copy of the low-rank factors, allocated on first use and converted again after every build_lowrank
+int ensure_f32_factors(pgpfa_ctx* c) {
+  const size_t nf = (size_t)c->Tp * c->Tp * c->p;
+  if (!c->Flr32) {
+    if (hipMalloc((void**)&c->Flr32, (nf + 256 * (size_t)c->Tp) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail("out of device memory for the single-precision factors"); }
+    c->flr32_valid = false;
   }
+  if (!c->flr32_valid) {
+    hipLaunchKernelGGL(cvt_f32_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->st, c->Flr, c->Flr32, nf);
+    c->flr32_valid = true;
+  }
+  return 0;
+}
+
+// b. B = I + F^T Wt F into the factor slabs viewed with ld = rpad - in FP64, in FP32 (f32_mode 1), or in FP64 and rounded once (2) - and its factor
+// (compact rank offsets: the tiles of B are walked in the padded index space - rtot16 rows - and stored through cmap; build_lowrank)
+int assemble_and_factor(pgpfa_ctx* c, const CovPass& P) {
+  const int rpad = c->rpad, nb = P.nb;
   HIPC(hipMemsetAsync(c->ws.info, 0, sizeof(int) * nb, c->st));
-  if (f32 && f32_mode == 1) {
-    hipLaunchKernelGGL(assemble_b_kernel_t<float>, dim3(npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, reinterpret_cast<float*>(lwf.H),
-                       (long long)lwf.sH, rpad, nblk64, (const float*)c->Flr32, Tp, T, p, c->d_blk_lat, c->d_blk_col, c->Wt, sW, c->ident, nb, cmap);
-    if (cmap && rpad > c->rtot)
-      hipLaunchKernelGGL(pad_identity_kernel<float>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<float*>(lwf.H), (long long)lwf.sH, rpad, c->rtot, rpad, lw.nact, (int)NB, c->ident);
-  } else {
-    hipLaunchKernelGGL(assemble_b_kernel_t<double>, dim3(npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad,
-                       nblk64, (const double*)c->Flr, Tp, T, p, c->d_blk_lat, c->d_blk_col, c->Wt, sW, c->ident, nb, cmap);
-    if (cmap && rpad > c->rtot)
-      hipLaunchKernelGGL(pad_identity_kernel<double>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad, c->rtot, rpad, lw.nact, (int)NB, c->ident);
-  }
-  HIPC(hipGetLastError());
-  if (f32) {
-    if (f32_mode != 1)
-      hipLaunchKernelGGL(cvt_lower_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH,
-                         reinterpret_cast<float*>(lwf.H), (long long)lwf.sH, rpad);
-    c->mt_dirty = true;
-    // (laplace_f32: the diagonal blocks of the factorisation in FP64 registers over the single-precision slab - their 127 rank-1 steps in float cost
-    //  6 x the error of the rest, and the kernel is latency-bound either way; the dual's dual_f32 keeps its arithmetic)
-    CHK(factor(c, lwf, c->ident, nb, true, lap32));
-  } else {
-    CHK(factor(c, lw, c->ident, nb));
-  }
+  if (P.f32_mode == 1) CHK(assemble_rxr<float>(c, P.lwf, nb, c->Flr32, c->Wt, P.sW, c->ident));
+  else CHK(assemble_rxr<double>(c, P.lw, nb, c->Flr, c->Wt, P.sW, c->ident));
+  if (!P.f32) return factor(c, P.lw, c->ident, nb);
+  if (P.f32_mode != 1)
+    hipLaunchKernelGGL(cvt_lower_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, P.lw.H, P.lw.sH,
+                       reinterpret_cast<float*>(P.lwf.H), P.lwf.sH, rpad);
+  c->mt_dirty = true;
+  // (laplace_f32: the diagonal blocks of the factorisation in FP64 registers over the single-precision slab - their 127 rank-1 steps in float cost
+  //  6 x the error of the rest, and the kernel is latency-bound either way; the dual's dual_f32 keeps its arithmetic)
+  return factor(c, P.lwf, c->ident, nb, true, P.lap32);
+}
+
+// log-determinants from the factor, before anything reuses its slab: ld_dev on the device, logdet_out through two read-backs (see the pass below)
+int log_determinants(pgpfa_ctx* c, const CovPass& P, double* logdet_out, double* ld_dev) {
+  const int T = c->T, rpad = c->rpad, nb = P.nb;
+  const CholWS &lw = P.lw, &lwf = P.lwf;
   if (ld_dev) {
-    if (f32) return fail("internal: log evidence requested from a single-precision factor");
+    if (P.f32) return fail("internal: log evidence requested from a single-precision factor");
     hipLaunchKernelGGL(evidence_logdet_kernel, dim3(nb), dim3(256), 0, c->st, (const double*)c->ldet_buf, T, lw.H, (long long)lw.sH, rpad, rpad, 0.0, ld_dev);
   }
   if (logdet_out) {
     std::vector<double> a(nb), b2(nb);
     hipLaunchKernelGGL(sum_rows_kernel, dim3(nb), dim3(256), 0, c->st, c->ldet_buf, T, c->sc_f);
     CHK(download(c, a.data(), c->sc_f, nb));
-    if (f32)
+    if (P.f32)
       hipLaunchKernelGGL(logdet_batch_f32_kernel, dim3(nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.H), (long long)lwf.sH, rpad, rpad,
                          c->sc_f);
     else
@@ -492,200 +577,225 @@ static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, 
     for (double v : c->logdetK) ldk += v;
     for (int s2 = 0; s2 < nb; ++s2) logdet_out[s2] = -ldk + a[s2] + b2[s2];
   }
-  c->mt_dirty = true;
-  if (f32 && !lap32) {
-    hipLaunchKernelGGL(fill_slabs_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st,
-                       reinterpret_cast<float*>(lwf.Mt), (long long)lwf.sM, (size_t)rpad * rpad, 0.0f);
-    CHK(inverse_t(c, lwf, c->ident, nb, true));
-    // Yt (float, n x ract, ld = c->ld) behind L^-T in the same slab
-    for (int k = 0; k < p; ++k) {
-      const int c0 = skip_zero_cols ? (c->roff[k] / ctile) * ctile : 0;      // (see the FP64 product below)
-      if (c0 >= ract) continue;
-      GemmP g{};
-      g.A = reinterpret_cast<const double*>(c->Flr32 + (size_t)k * Tp * Tp); g.sA = 0; g.lda = Tp;
-      g.B = reinterpret_cast<const double*>(reinterpret_cast<float*>(lwf.Mt) + c->roff[k] + (size_t)c0 * rpad); g.sB = lwf.sM; g.ldb = rpad;
-      g.C = reinterpret_cast<double*>(Ytf + (size_t)k * Ts + (size_t)c0 * c->ld); g.sC = lwf.sM; g.ldc = c->ld;
-      g.M = T; g.N = ract - c0; g.K = c->rk[k]; g.alpha = 1.0; g.beta = 0.0;
-      g.slots = c->ident; g.nbatch = nb; g.mode = GEMM_FULL; g.kflags = 0;
-      CHK(gemm(c, true, g, true));
-    }
-    if (p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, p);
-    prof_begin(c, TAG_VSM, (double)nb * c->n * rpad * p);
-    launch_post_vsm(c, (const float*)Ytf, (long long)lwf.sM, ract, nb, 1, skip_zero_cols ? c->d_roff : nullptr, Ts);
-    prof_end(c);
-    dispatch_pw(p, [&](auto pw) {
-      constexpr int PW = decltype(pw)::value;
-      if constexpr (PW <= 16) {
-        constexpr int BT = 256 / PW;
-        hipLaunchKernelGGL(vsm_finish_kernel<PW>, dim3((T + BT - 1) / BT, nb), dim3(256), 0, c->st, c->vsm, c->Gbin, sW, T, p, c->eps, c->ident,
-                           c->trial_of_slot);
-      } else {
-        const int bins = wide_bins(p) / 2;
-        hipLaunchKernelGGL(vsm_finish_wide_kernel, dim3((T + bins - 1) / bins, nb), dim3(bins * 32), wide_lds_bytes(p, bins, 2), c->st, c->vsm,
-                           c->Gbin, sW, T, p, c->eps, c->ident, c->trial_of_slot, bins);
-      }
-    });
-    HIPC(hipGetLastError());
-    return 0;
+  return 0;
+}
+
+// c. Yt = F L^-T per latent (T x ract, ld = c->ld, rows (k, .) at k * Ts), in the element type of its three operands; column tiles left of roff[k]
+// skipped under skip_zero_cols.  FP64: from the Mt slabs into the factor slab (the factor itself is dead now).
+template <typename T>
+int yt_product(pgpfa_ctx* c, const CovPass& P, const T* F, const T* Linv, long long sL, T* Yt, long long sY) {
+  const int Tp = c->Tp, rpad = c->rpad;
+  for (int k = 0; k < c->p; ++k) {
+    const int c0 = P.skip_zero_cols ? (c->roff[k] / P.ctile) * P.ctile : 0;
+    if (c0 >= P.ract) continue;
+    GemmP g{};
+    g.A = reinterpret_cast<const double*>(F + (size_t)k * Tp * Tp); g.sA = 0; g.lda = Tp;
+    g.B = reinterpret_cast<const double*>(Linv + c->roff[k] + (size_t)c0 * rpad); g.sB = sL; g.ldb = rpad;     // rows roff[k].. of L^-T, K x N column-major
+    g.C = reinterpret_cast<double*>(Yt + (size_t)k * P.Ts + (size_t)c0 * c->ld); g.sC = sY; g.ldc = c->ld;
+    g.M = c->T; g.N = P.ract - c0; g.K = c->rk[k]; g.alpha = 1.0; g.beta = 0.0;
+    g.slots = c->ident; g.nbatch = P.nb; g.mode = GEMM_FULL; g.kflags = 0;
+    CHK(gemm(c, true, g, sizeof(T) == 4));
   }
-  if (lap32) {
-    // L^-T in single precision into the H slabs (float view, cleared first as for the dual), then widened into the Mt slabs - the single-precision factor
-    // there is dead - before anything writes Yt or D into the H slabs.  The widening writes the zeros the two clears below would have left.
-    hipLaunchKernelGGL(fill_slabs_f32_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st,
-                       reinterpret_cast<float*>(lwf.Mt), (long long)lwf.sM, (size_t)rpad * rpad, 0.0f);
-    CHK(inverse_t(c, lwf, c->ident, nb, true));
-    const int full = (skip_zero_cols && c->mt_fill) ? 0 : 1;
-    const bool vec = lw.sM % 2 == 0 && lw.sH % 2 == 0 && (reinterpret_cast<uintptr_t>(lw.Mt) & 15) == 0 && (reinterpret_cast<uintptr_t>(lw.H) & 15) == 0;
-    prof_begin(c, TAG_MIX, (double)nb * rpad * lw.nact * 6.0);          // (bytes, roughly: the upper triangle read in FP32 and written in FP64)
-    if (vec)
-      hipLaunchKernelGGL(widen_upper_f64_kernel<true>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
-                         lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
-    else
-      hipLaunchKernelGGL(widen_upper_f64_kernel<false>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
-                         lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
-    prof_end(c);
-    HIPC(hipGetLastError());
-    // B >= I in exact arithmetic, so a bad pivot needs cond(B) r 6e-8 of order one; the chunk is then redone through the FP64 path as a whole.  (The
-    // host waits for the factorisation here; where the fused pass runs it would wait for the split form's verdict a few lines on anyway.)
-    std::vector<int> pivot(nb, 0);
-    CHK(dl_enqueue(c, pivot.data(), c->ws.info, sizeof(int) * nb));
-    CHK(dl_flush(c));
-    if (std::any_of(pivot.begin(), pivot.end(), [](int v) { return v != 0; })) {
-      c->info["last_cov_f32_fallbacks"] += 1.0;
-      return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, false, ld_dev);
+  return 0;
+}
+
+// d. post_vsm[t] = eps G_t + G_t (Y_t^T Y_t) G_t from the Yt panel
+template <typename TY>
+int vsm_from_yt(pgpfa_ctx* c, const CovPass& P, const TY* Yt, long long sY) {
+  const int T = c->T, p = c->p, nb = P.nb;
+  const long long sW = P.sW;
+  prof_begin(c, TAG_VSM, (double)nb * c->n * c->rpad * p);
+  launch_post_vsm(c, Yt, sY, P.ract, nb, 1, P.skip_zero_cols ? c->d_roff : nullptr, P.Ts);
+  prof_end(c);
+  dispatch_pw(p, [&](auto pw) {
+    constexpr int PW = decltype(pw)::value;
+    if constexpr (PW <= 16) {
+      constexpr int BT = 256 / PW;
+      hipLaunchKernelGGL(vsm_finish_kernel<PW>, dim3((T + BT - 1) / BT, nb), dim3(256), 0, c->st, c->vsm, c->Gbin, sW, T, p, c->eps, c->ident,
+                         c->trial_of_slot);
+    } else {
+      const int bins = wide_bins(p) / 2;                 // two staged blocks per bin
+      hipLaunchKernelGGL(vsm_finish_wide_kernel, dim3((T + bins - 1) / bins, nb), dim3(bins * 32), wide_lds_bytes(p, bins, 2), c->st, c->vsm,
+                         c->Gbin, sW, T, p, c->eps, c->ident, c->trial_of_slot, bins);
     }
-  } else {
-  // L^-T's slab holds whatever the last use left (another rank layout, the factor of a dense pass): clear what will be read and not written - all of it,
-  // or, when every consumer starts at the latent's own columns (skip_zero_cols), the strictly lower entries of the p rectangles they read
-  if (skip_zero_cols && c->mt_fill)
-    hipLaunchKernelGGL(clear_lower_reads_kernel, dim3(p, nb), dim3(256), 0, c->st, lw.Mt, (long long)lw.sM, rpad, c->d_roff, ctile, c->ident);
+  });
+  return 0;
+}
+
+// The rest of a dual evaluation under dual_f32: L^-T, Yt and post_vsm from the single-precision factor.
+int dual_f32_tail(pgpfa_ctx* c, const CovPass& P) {
+  CHK(clear_and_invert<float>(c, P.lwf, P.nb));
+  CHK(yt_product<float>(c, P, c->Flr32, reinterpret_cast<const float*>(P.lwf.Mt), P.lwf.sM, P.Ytf, P.lwf.sM));
+  if (c->p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, c->p);
+  CHK(vsm_from_yt<float>(c, P, P.Ytf, P.lwf.sM));
+  HIPC(hipGetLastError());
+  return 0;
+}
+
+// L^-T under laplace_f32: in single precision into the H slabs (float view, cleared first as for the dual), then widened into the Mt slabs - the
+// single-precision factor there is dead - before anything writes Yt or D into the H slabs.  The widening writes the zeros the FP64 path's clears would have
+// left.  *redo: a pivot of the single-precision factorisation was not positive.
+int lap32_inverse(pgpfa_ctx* c, const CovPass& P, bool* redo) {
+  const int p = c->p, rpad = c->rpad, nb = P.nb, ctile = P.ctile;
+  const CholWS &lw = P.lw, &lwf = P.lwf;
+  CHK(clear_and_invert<float>(c, lwf, nb));
+  const int full = (P.skip_zero_cols && c->mt_fill) ? 0 : 1;
+  const bool vec = lw.sM % 2 == 0 && lw.sH % 2 == 0 && (reinterpret_cast<uintptr_t>(lw.Mt) & 15) == 0 && (reinterpret_cast<uintptr_t>(lw.H) & 15) == 0;
+  prof_begin(c, TAG_MIX, (double)nb * rpad * lw.nact * 6.0);          // (bytes, roughly: the upper triangle read in FP32 and written in FP64)
+  if (vec)
+    hipLaunchKernelGGL(widen_upper_f64_kernel<true>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
+                       lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
   else
-    hipLaunchKernelGGL(fill_slabs_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.Mt, lw.sM,
-                       (size_t)rpad * rpad, 0.0);
-  CHK(inverse_t(c, lw, c->ident, nb));
-  }
-  if (p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, p);
-  // the split form's verdict: the relative size of the mixing correction, measured when the chunk's blocks were formed
-  bool split = false, decided = false;
-  auto decide_split = [&]() -> int {
-    decided = true;
-    if (!(split_candidate || c->measure_mix)) return 0;
-    unsigned hw[4] = {0u, 0u, 0u, 0u};
-    CHK(dl_enqueue(c, hw, norm_bits, 4 * sizeof(unsigned)));
-    CHK(dl_flush(c));
-    float hv;
-    double hsq;
-    std::memcpy(&hv, &hw[0], sizeof(float));
-    std::memcpy(&hsq, &hw[2], sizeof(double));
-    const double rms = std::sqrt(hsq / std::max(1.0, (double)nb * T));
-    c->info["last_eps_wt_norm"] = std::max(c->info["last_eps_wt_norm"], (double)hv);
-    c->info["last_eps_wt_rms"] = std::max(c->info["last_eps_wt_rms"], rms);
-    // (the precision of the split form follows the root mean square of the correction; the maximum only has to stay a contraction)
-    split = split_candidate && std::isfinite(hv) && std::isfinite(rms) && rms <= c->split_max_norm && (double)hv <= 0.9;
-    return 0;
+    hipLaunchKernelGGL(widen_upper_f64_kernel<false>, dim3((lw.nact + 3) / 4, nb), dim3(256), 0, c->st, reinterpret_cast<const float*>(lwf.Mt), (long long)lwf.sM,
+                       lw.Mt, (long long)lw.sM, rpad, lw.nact, c->d_roff, p, ctile, full);
+  prof_end(c);
+  HIPC(hipGetLastError());
+  // B >= I in exact arithmetic, so a bad pivot needs cond(B) r 6e-8 of order one; the chunk is then redone through the FP64 path as a whole.  (The
+  // host waits for the factorisation here; where the fused pass runs it would wait for the split form's verdict a few lines on anyway.)
+  std::vector<int> pivot(nb, 0);
+  CHK(dl_enqueue(c, pivot.data(), c->ws.info, sizeof(int) * nb));
+  CHK(dl_flush(c));
+  *redo = std::any_of(pivot.begin(), pivot.end(), [](int v) { return v != 0; });
+  if (*redo) c->info["last_cov_f32_fallbacks"] += 1.0;
+  return 0;
+}
+
+// The split form's verdict: the relative size of the mixing correction, measured when the chunk's blocks were formed.  The host waits for it.
+int split_verdict(pgpfa_ctx* c, const CovPass& P, bool* split) {
+  *split = false;
+  if (!(P.split_candidate || c->measure_mix)) return 0;
+  unsigned hw[4] = {0u, 0u, 0u, 0u};
+  CHK(dl_enqueue(c, hw, P.norm_bits, 4 * sizeof(unsigned)));
+  CHK(dl_flush(c));
+  float hv;
+  double hsq;
+  std::memcpy(&hv, &hw[0], sizeof(float));
+  std::memcpy(&hsq, &hw[2], sizeof(double));
+  const double rms = std::sqrt(hsq / std::max(1.0, (double)P.nb * c->T));
+  c->info["last_eps_wt_norm"] = std::max(c->info["last_eps_wt_norm"], (double)hv);
+  c->info["last_eps_wt_rms"] = std::max(c->info["last_eps_wt_rms"], rms);
+  // (the precision of the split form follows the root mean square of the correction; the maximum only has to stay a contraction)
+  *split = P.split_candidate && std::isfinite(hv) && std::isfinite(rms) && rms <= c->split_max_norm && (double)hv <= 0.9;
+  return 0;
+}
+
+// d+e. one pass over Yt: post_vsm[t] = eps G_t + sum_b (G_t y_b)(G_t y_b)^T, and Yt is mixed in place (y <- G_t y) so that
+//      rows (k,.) of the slab become Ymix_k, the GEMM operand of post_vsmGP_k = eps diag(G_t[k][k]) + Ymix_k Ymix_k^T
+int mix_in_place(pgpfa_ctx* c, const CovPass& P) {
+  const int T = c->T, p = c->p, nb = P.nb, ract = P.ract, ctile = P.ctile, Ts = P.Ts;
+  const long long sW = P.sW;
+  const CholWS& lw = P.lw;
+  prof_begin(c, TAG_MIX, (double)nb * c->n * ract * 16.0);           // (bytes: Yt read and written in place)
+  dispatch_pw(p, [&](auto pw) {
+    constexpr int PW = decltype(pw)::value;
+    if constexpr (PW <= 16) {
+      hipLaunchKernelGGL(mix_vsm_kernel<PW>, dim3((T + 63) / 64, nb), dim3(256), 0, c->st, lw.H, lw.sH, c->ld, c->Gbin, sW, T, p, ract, c->eps,
+                         c->vsm, c->ident, c->trial_of_slot, c->d_roff, ctile, Ts);
+    } else if (c->mix_wide && p <= 20) {
+      hipLaunchKernelGGL((mix_vsm_wide2_kernel<20, false>), dim3((T + 63) / 64, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, c->ld, c->Gbin, sW, T, p, ract, c->eps,
+                         c->vsm, c->ident, c->trial_of_slot, Ts, c->sink, (float*)nullptr, 0LL, 0);
+    } else {
+      const int bins = wide_bins(p);
+      hipLaunchKernelGGL(mix_vsm_wide_kernel, dim3((T + bins - 1) / bins, nb), dim3(bins * 32), wide_lds_bytes(p, bins, 1), c->st, lw.H, lw.sH,
+                         c->ld, c->Gbin, sW, T, p, ract, c->eps, c->vsm, c->ident, c->trial_of_slot, bins, Ts);
+    }
+  });
+  prof_end(c);
+  return 0;
+}
+
+// sum-only output: Pacc[k] += sum over the chunk's slots of Ymix_k Ymix_k^T as ONE split-K product per launch -
+// batch = (latent, group of `sps` consecutive slots), the K dimension walks the rpad-wide panels of the
+// group's slabs - followed by a reduction of the partial products (+ the eps G_t[k][k] diagonals)
+int pacc_sum(pgpfa_ctx* c, const CovPass& P) {
+  const int T = c->T, p = c->p, nb = P.nb, ract = P.ract;
+  const CholWS& lw = P.lw;
+  const int sps = std::max(1, (nb + PACC_SPLITS - 1) / PACC_SPLITS);
+  const int nfull = nb / sps, rem = nb - nfull * sps, nsplit = nfull + (rem ? 1 : 0);
+  auto launch = [&](int first_slot, int slots_per, int ngroups, int part_first) -> int {
+    GemmP g{};
+    g.A = lw.H + (size_t)first_slot * lw.sH; g.sA = (long long)slots_per * lw.sH; g.lda = c->ld;
+    g.B = g.A; g.sB = g.sA; g.ldb = c->ld;
+    g.C = c->ppart + (size_t)part_first * T * T; g.sC = (long long)T * T; g.ldc = T;
+    g.M = T; g.N = T; g.K = slots_per * ract; g.alpha = 1.0; g.beta = 0.0;
+    g.slots = nullptr; g.nb_lo = ngroups; g.nbatch = ngroups * p;
+    g.sA_hi = P.Ts; g.sB_hi = P.Ts; g.sC_hi = (long long)nsplit * T * T;
+    g.kseg = ract; g.sAseg = lw.sH; g.sBseg = lw.sH;    // ract columns of each slab, slabs sH apart
+    g.mode = GEMM_LOWER; g.kflags = 0;
+    return gemm(c, false, g);
   };
-  // c. Yt = F Mts  (n x rpad, ld = c->ld) into the factor slab (the factor itself is dead now)
-  // (column tiles left of roff[k] skipped under skip_zero_cols, see above)
-  // Under the split form Yt has one consumer, the mixing pass: up to 10 latents the two run as one kernel (ytmix.h) and Yt is never written.  That
-  // needs the verdict before the product is queued instead of behind it (the host then waits for the factorisation: one launch gap per chunk).
+  if (nfull) CHK(launch(0, sps, nfull, 0));
+  if (rem) CHK(launch(nfull * sps, rem, 1, nfull));
+  hipLaunchKernelGGL(pacc_reduce_kernel, dim3(T, p), dim3(128), 0, c->st, c->ppart, nsplit, c->Gbin, P.sW, nb, c->eps, T, c->Tp, p, c->Pacc);
+  c->pacc_used = true;
+  return 0;
+}
+
+// per-trial output: post_vsmGP_k of every slot from the mixed panel, through a staging block behind Yt
+int trial_blocks(pgpfa_ctx* c, const CovPass& P) {
+  const int T = c->T, p = c->p, rpad = c->rpad, nb = P.nb;
+  const CholWS& lw = P.lw;
+  CHK(ensure_vsmgp_buffer(c));
+  const size_t off_stage = (size_t)c->ld * rpad + (size_t)c->Tp * rpad;
+  for (int k = 0; k < p; ++k) {
+    GemmP g{};
+    g.A = lw.H + (size_t)k * P.Ts; g.sA = lw.sH; g.lda = c->ld;
+    g.B = g.A; g.sB = lw.sH; g.ldb = c->ld;
+    g.C = lw.H + off_stage; g.sC = lw.sH; g.ldc = T;
+    g.M = T; g.N = T; g.K = P.ract; g.alpha = 1.0; g.beta = 0.0;
+    g.slots = c->ident; g.nbatch = nb; g.mode = GEMM_LOWER; g.kflags = 0;
+    CHK(gemm(c, false, g));
+    hipLaunchKernelGGL(scatter_vsmgp_lr_kernel, dim3((unsigned)(((size_t)T * T + 255) / 256), nb), dim3(256), 0, c->st, lw.H + off_stage, lw.sH, T,
+                       c->vsmgp, T, p, k, c->Gbin, P.sW, c->eps, c->trial_of_slot);
+  }
+  return 0;
+}
+
+}  // namespace
+
+// Covariance blocks through the low-rank form of the prior (see model.h): per slot an r x r SPD system
+// B = I + F^T Wt F instead of the n x n Hessian.  Uses the dense engine's slabs as scratch (ld = rpad views).  The phases, in DESIGN section 3's order:
+// logdet_out (optional, host, nb entries): log det of the posterior precision K^-1 + scatter(W) of every slot,
+//   = -sum_k log det K_k + sum_t log det(I + eps W_t) + log det(I + F^T Wt F)   (Sylvester; K_k = eps I + F_k F_k^T)
+// (allow_lap32 = false: the FP64 pass that redoes a chunk whose single-precision factorisation failed under option laplace_f32)
+// ld_dev (optional, device, nb entries; the Laplace log evidence): log det of the posterior precision + sum_k log det K_k = the last two terms above,
+//   reduced per slot by one kernel behind the factorisation; nothing is read back here.  FP64 factor only: the E-step refuses it under laplace_f32.
+static int posterior_blocks_lowrank_impl(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out, bool allow_lap32, double* ld_dev) {
+  c->last_cov_lowrank = true;
+  const CovPass P = cov_pass(c, nb, want_vsmgp, accumulate, allow_lap32);
+  CHK(blocks_and_norm(c, P, (logdet_out || ld_dev) ? c->ldet_buf : nullptr));                  // a.
+  c->info["last_cov_f32"] = P.lap32 ? 1.0 : 0.0;
+  if (P.f32) CHK(ensure_f32_factors(c));
+  CHK(assemble_and_factor(c, P));                                                               // b.
+  CHK(log_determinants(c, P, logdet_out, ld_dev));
+  c->mt_dirty = true;
+  if (P.f32 && !P.lap32) return dual_f32_tail(c, P);
+  if (P.lap32) {
+    bool redo = false;
+    CHK(lap32_inverse(c, P, &redo));
+    if (redo) return posterior_blocks_lowrank_impl(c, nb, want_vsmgp, accumulate, logdet_out, false, ld_dev);
+  } else {
+    CHK(clear_and_invert<double>(c, P.lw, nb, (P.skip_zero_cols && c->mt_fill) ? P.ctile : 0));
+  }
+  if (c->p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, c->p);
+  // c. Yt = F L^-T.  Under the split form Yt has one consumer, the mixing pass: up to 10 latents the two run as one kernel (ytmix.h) and Yt is never
+  // written.  That needs the verdict before the product is queued instead of behind it (the host then waits for the factorisation: one launch gap per chunk).
   // (compact offsets: the last column block of Yt is partly padding - identity columns of L^-T meeting no row of F: zeros)
-  const bool fuse_candidate = split_candidate && c->yt_mix && c->mfma && p <= 10 && (ract == c->rtot || (c->rank_compact && ract <= lw.nact));
-  if (fuse_candidate) CHK(decide_split());
+  const bool fuse_candidate = P.split_candidate && c->yt_mix && c->mfma && c->p <= 10 && (P.ract == c->rtot || (c->rank_compact && P.ract <= P.lw.nact));
+  bool split = false;
+  if (fuse_candidate) CHK(split_verdict(c, P, &split));
   const bool fused = fuse_candidate && split;
   c->info["last_yt_mix_fused"] = fused ? 1.0 : 0.0;
-  if (!fused) {
-    for (int k = 0; k < p; ++k) {
-      const int c0 = skip_zero_cols ? (c->roff[k] / ctile) * ctile : 0;
-      if (c0 >= ract) continue;
-      GemmP g{};
-      g.A = c->Flr + (size_t)k * Tp * Tp; g.sA = 0; g.lda = Tp;
-      g.B = lw.Mt + c->roff[k] + (size_t)c0 * rpad; g.sB = lw.sM; g.ldb = rpad;     // rows roff[k].. of Mts, K x N column-major
-      g.C = lw.H + (size_t)k * Ts + (size_t)c0 * c->ld; g.sC = lw.sH; g.ldc = c->ld;
-      g.M = T; g.N = ract - c0; g.K = c->rk[k]; g.alpha = 1.0; g.beta = 0.0;
-      g.slots = c->ident; g.nbatch = nb; g.mode = GEMM_FULL; g.kflags = 0;
-      CHK(gemm(c, true, g));
-    }
-  }
-  if (!decided) CHK(decide_split());
+  if (!fused) CHK(yt_product<double>(c, P, c->Flr, P.lw.Mt, P.lw.sM, P.lw.H, P.lw.sH));
+  if (!fuse_candidate) CHK(split_verdict(c, P, &split));
   c->info["last_split_cov"] = split ? 1.0 : 0.0;
   if (!split) for (const char* key : {"last_syrk_tile", "last_split_sps", "last_cross_kernel", "last_mix_form"}) c->info[key] = 0.0;
-  if (want_vsmgp && split) {
-    CHK(accumulate_split(c, lw, nb, ract, Ts, skip_zero_cols, ctile, fused));
-  } else if (want_vsmgp) {
-    // d+e. one pass over Yt: post_vsm[t] = eps G_t + sum_b (G_t y_b)(G_t y_b)^T, and Yt is mixed in place (y <- G_t y) so that
-    //      rows (k,.) of the slab become Ymix_k, the GEMM operand of post_vsmGP_k = eps diag(G_t[k][k]) + Ymix_k Ymix_k^T
-    prof_begin(c, TAG_MIX, (double)nb * c->n * ract * 16.0);           // (bytes: Yt read and written in place)
-    dispatch_pw(p, [&](auto pw) {
-      constexpr int PW = decltype(pw)::value;
-      if constexpr (PW <= 16) {
-        hipLaunchKernelGGL(mix_vsm_kernel<PW>, dim3((T + 63) / 64, nb), dim3(256), 0, c->st, lw.H, lw.sH, c->ld, c->Gbin, sW, T, p, ract, c->eps,
-                           c->vsm, c->ident, c->trial_of_slot, c->d_roff, ctile, Ts);
-      } else if (c->mix_wide && p <= 20) {
-        hipLaunchKernelGGL((mix_vsm_wide2_kernel<20, false>), dim3((T + 63) / 64, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, c->ld, c->Gbin, sW, T, p, ract, c->eps,
-                           c->vsm, c->ident, c->trial_of_slot, Ts, c->sink, (float*)nullptr, 0LL, 0);
-      } else {
-        const int bins = wide_bins(p);
-        hipLaunchKernelGGL(mix_vsm_wide_kernel, dim3((T + bins - 1) / bins, nb), dim3(bins * 32), wide_lds_bytes(p, bins, 1), c->st, lw.H, lw.sH,
-                           c->ld, c->Gbin, sW, T, p, ract, c->eps, c->vsm, c->ident, c->trial_of_slot, bins, Ts);
-      }
-    });
-    prof_end(c);
-  } else {
-    // d. post_vsm[t] = eps G_t + G_t (Y_t^T Y_t) G_t
-    prof_begin(c, TAG_VSM, (double)nb * c->n * rpad * p);
-    launch_post_vsm(c, (const double*)lw.H, (long long)lw.sH, ract, nb, 1, skip_zero_cols ? c->d_roff : nullptr, Ts);
-    prof_end(c);
-    dispatch_pw(p, [&](auto pw) {
-      constexpr int PW = decltype(pw)::value;
-      if constexpr (PW <= 16) {
-        constexpr int BT = 256 / PW;
-        hipLaunchKernelGGL(vsm_finish_kernel<PW>, dim3((T + BT - 1) / BT, nb), dim3(256), 0, c->st, c->vsm, c->Gbin, sW, T, p, c->eps, c->ident,
-                           c->trial_of_slot);
-      } else {
-        const int bins = wide_bins(p) / 2;                 // two staged blocks per bin
-        hipLaunchKernelGGL(vsm_finish_wide_kernel, dim3((T + bins - 1) / bins, nb), dim3(bins * 32), wide_lds_bytes(p, bins, 2), c->st, c->vsm,
-                           c->Gbin, sW, T, p, c->eps, c->ident, c->trial_of_slot, bins);
-      }
-    });
-  }
-  if (want_vsmgp && !split) {
-    if (accumulate) {
-      // sum-only output: Pacc[k] += sum over the chunk's slots of Ymix_k Ymix_k^T as ONE split-K product per launch -
-      // batch = (latent, group of `sps` consecutive slots), the K dimension walks the rpad-wide panels of the
-      // group's slabs - followed by a reduction of the partial products (+ the eps G_t[k][k] diagonals)
-      const int sps = std::max(1, (nb + PACC_SPLITS - 1) / PACC_SPLITS);
-      const int nfull = nb / sps, rem = nb - nfull * sps, nsplit = nfull + (rem ? 1 : 0);
-      auto launch = [&](int first_slot, int slots_per, int ngroups, int part_first) -> int {
-        GemmP g{};
-        g.A = lw.H + (size_t)first_slot * lw.sH; g.sA = (long long)slots_per * lw.sH; g.lda = c->ld;
-        g.B = g.A; g.sB = g.sA; g.ldb = c->ld;
-        g.C = c->ppart + (size_t)part_first * T * T; g.sC = (long long)T * T; g.ldc = T;
-        g.M = T; g.N = T; g.K = slots_per * ract; g.alpha = 1.0; g.beta = 0.0;
-        g.slots = nullptr; g.nb_lo = ngroups; g.nbatch = ngroups * p;
-        g.sA_hi = Ts; g.sB_hi = Ts; g.sC_hi = (long long)nsplit * T * T;
-        g.kseg = ract; g.sAseg = lw.sH; g.sBseg = lw.sH;    // ract columns of each slab, slabs sH apart
-        g.mode = GEMM_LOWER; g.kflags = 0;
-        return gemm(c, false, g);
-      };
-      if (nfull) CHK(launch(0, sps, nfull, 0));
-      if (rem) CHK(launch(nfull * sps, rem, 1, nfull));
-      hipLaunchKernelGGL(pacc_reduce_kernel, dim3(T, p), dim3(128), 0, c->st, c->ppart, nsplit, c->Gbin, sW, nb, c->eps, T, Tp, p, c->Pacc);
-      c->pacc_used = true;
-    } else {
-      CHK(ensure_vsmgp_buffer(c));
-      const size_t off_stage = (size_t)c->ld * rpad + (size_t)Tp * rpad;
-      for (int k = 0; k < p; ++k) {
-        GemmP g{};
-        g.A = lw.H + (size_t)k * Ts; g.sA = lw.sH; g.lda = c->ld;
-        g.B = g.A; g.sB = lw.sH; g.ldb = c->ld;
-        g.C = lw.H + off_stage; g.sC = lw.sH; g.ldc = T;
-        g.M = T; g.N = T; g.K = ract; g.alpha = 1.0; g.beta = 0.0;
-        g.slots = c->ident; g.nbatch = nb; g.mode = GEMM_LOWER; g.kflags = 0;
-        CHK(gemm(c, false, g));
-        hipLaunchKernelGGL(scatter_vsmgp_lr_kernel, dim3((unsigned)(((size_t)T * T + 255) / 256), nb), dim3(256), 0, c->st, lw.H + off_stage, lw.sH, T,
-                           c->vsmgp, T, p, k, c->Gbin, sW, c->eps, c->trial_of_slot);
-      }
-    }
+  // d, e. post_vsm and the T x T output: summed by the split form, or summed / per trial from the panel mixed in place; post_vsm alone for the dual
+  if (!want_vsmgp) CHK(vsm_from_yt<double>(c, P, P.lw.H, P.lw.sH));
+  else if (split) CHK(accumulate_split(c, P, fused));
+  else {
+    CHK(mix_in_place(c, P));
+    CHK(accumulate ? pacc_sum(c, P) : trial_blocks(c, P));
   }
   HIPC(hipGetLastError());
   return 0;
@@ -718,23 +828,14 @@ int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale) {
     return 0;
   }
   if (diag_scale != 1.0) return fail("internal: jittered factor requested under the low-rank workspace plan");
-  const int T = c->T, p = c->p, Tp = c->Tp, rpad = c->rpad;
-  if (p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, p);
-  const long long sW = (long long)T * p * p;
+  if (c->p > WIDE_MAX) return fail("low-rank covariance engine supports up to %d latents (p=%d)", WIDE_MAX, c->p);
+  const long long sW = (long long)c->T * c->p * c->p;
   CHK(bin_blocks(c, c->W, sW, c->Gbin, c->Wt, sW, nb, nullptr));
-  CholWS lw = c->ws;
-  lw.ld = rpad; lw.npad = rpad; lw.nact = round_up(c->rtot, 64);
-  const int nblk64 = c->rank_compact ? round_up(c->rtot16, 64) / 64 : rpad / 64, npairs = nblk64 * (nblk64 + 1) / 2;
-  const int* cmap = c->rank_compact ? c->d_cmap : nullptr;
-  hipLaunchKernelGGL(assemble_b_kernel_t<double>, dim3(npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad,
-                     nblk64, (const double*)c->Flr, Tp, T, p, c->d_blk_lat, c->d_blk_col, c->Wt, sW, c->ident, nb, cmap);
-  if (cmap && rpad > c->rtot)
-    hipLaunchKernelGGL(pad_identity_kernel<double>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad, c->rtot, rpad, lw.nact, (int)NB, c->ident);
-  HIPC(hipGetLastError());
+  const CholWS lw = lowrank_view(c, c->ws);
+  CHK(assemble_rxr<double>(c, lw, nb, c->Flr, c->Wt, sW, c->ident));
   CHK(factor(c, lw, c->ident, nb));
   c->mt_dirty = true;
-  hipLaunchKernelGGL(fill_slabs_kernel, dim3((unsigned)(((size_t)rpad * rpad + 1023) / 1024), nb), dim3(256), 0, c->st, lw.Mt, lw.sM, (size_t)rpad * rpad, 0.0);
-  CHK(inverse_t(c, lw, c->ident, nb));
+  CHK(clear_and_invert<double>(c, lw, nb));
   HIPC(hipGetLastError());
   return 0;
 }

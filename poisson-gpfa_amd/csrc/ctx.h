@@ -333,6 +333,27 @@ struct pgpfa_ctx {
   double* counts_nodes = nullptr; int counts_nodes_Q = 0;     // device [2][64]: x_q | log w_q
 };
 
+// The preconditioner's products can run as thin.h's kernels (matrix cores, at least one 4-bin step).  build_lowrank decides the compact rank offsets
+// from it, shared_solve and solve_form (estep.hip: thin_ok) the form of the inner solve: one predicate, so the three cannot disagree.
+inline bool thin_possible(const pgpfa_ctx* c) { return c->thin_products && c->mfma && c->T >= 4; }
+
+// Rank layout of the r x r system B = I + F^T Wt F (core.hip: build_lowrank): 64-blocks and lower block pairs its assembly walks - in the padded
+// index space (rtot16 rows) under compact offsets, stored through cmap -, and the tables the fused Yt / mixing kernel reads the same layout from.
+struct BLayout {
+  int nblk64, npairs;
+  const int* cmap;                               // padded index -> compact index (null: the two spaces are one)
+  const int* roff_padded;                        // offsets of the latents in the space the tiles are walked in
+  const int* nrtab;                              // padded rows per 16-column block of L^-T (null without cmap)
+  int ncmap_rows;                                // entries of cmap (0 without)
+};
+BLayout b_layout(const pgpfa_ctx* c);            // core.hip
+// the factor slabs `ws` as the r x r system sees them
+inline CholWS lowrank_view(const pgpfa_ctx* c, const CholWS& ws) {
+  CholWS lw = ws;
+  lw.ld = c->rpad; lw.npad = c->rpad; lw.nact = round_up(c->rtot, 64);
+  return lw;
+}
+
 template <typename T>
 int dmalloc(pgpfa_ctx* c, T** out, size_t count, bool zero = false) {
   void* p = nullptr;
@@ -531,6 +552,10 @@ int estep_impl(pgpfa_ctx* c, const Trials& tr, int warm_start, bool allow_lr, do
 // cov.hip: posterior covariance blocks (dense and low-rank engines), blocks rebuilt on demand
 int ensure_mt_clean(pgpfa_ctx* c);
 int ensure_vsmgp_buffer(pgpfa_ctx* c);
+// B = I + F^T Wt F of nb slots into view.H (TB = float: the slab viewed as floats), with the identity behind the last latent under compact offsets.
+// Instantiated for double and float in cov.hip.
+template <typename TB>
+int assemble_rxr(pgpfa_ctx* c, const pgpfa::CholWS& view, int nb, const TB* F, const double* Wt, long long sW, const int* slots);
 // (ld_dev, optional, device, nb entries: log det of every slot's posterior precision + sum_k log det K_k, written in stream order - no host wait)
 int posterior_blocks_lowrank(pgpfa_ctx* c, int nb, bool want_vsmgp, bool accumulate, double* logdet_out = nullptr, double* ld_dev = nullptr);
 int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, bool accumulate = false, double* ld_dev = nullptr);

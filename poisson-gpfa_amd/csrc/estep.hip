@@ -191,6 +191,9 @@ void thin_launch_f(const ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream
   else hipLaunchKernelGGL(thin_f_kernel<false>, dim3(ntab, (ncols + 15) / 16), dim3(256), 0, st, tp);
 }
 
+// the thin products run: they can (ctx.h) and the r x r operands fit the vectors' leading dimension (shared_solve, solve_form)
+static bool thin_ok(const pgpfa_ctx* c) { return thin_possible(c) && (size_t)c->rpad <= (size_t)c->ld; }
+
 // Z <- P^-1 R for the nb slot vectors at once.  Dense plan: the shared preconditioner is ONE matrix, its explicit
 // inverse is formed once per chunk and applied with a single multi-RHS GEMM.  Low-rank plan: the same matrix in
 // Woodbury form, P^-1 v = Gb (eps v + F Sb F^T Gb v), with Gb the per-bin blocks of the mean curvature and Sb the
@@ -223,7 +226,7 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
     };
     if (first_apply) apply_bin(R, nullptr, 1.0, c->Xt);
     // the two block-diagonal products as kernels of their own (thin.h) where the matrix cores are in use; the general product otherwise
-    const bool thin = c->thin_products && c->mfma && c->T >= 4 && (size_t)c->rpad <= (size_t)c->ld;
+    const bool thin = thin_ok(c);
     if ((vec_row > 0 || vec_f32) && (!thin || first_apply || final_apply)) return fail("internal: padded vector rows need the thin products and no per-bin application");
     // (the general GEMM's row-tile tables start tiles on multiples of 16: compact offsets must never reach it)
     if (c->rank_compact && !(thin && c->thin_products >= 2)) return fail("internal: compact rank offsets without the thin products (rank tables are stale)");
@@ -344,15 +347,8 @@ static int shared_factor_lowrank(pgpfa_ctx* c, int nb) {
     hipLaunchKernelGGL(pack_sym_t_kernel<double>, dim3((npk + 255) / 256), dim3(256), 0, c->st, (const double*)c->Gbar, c->GbT, T, p);
     hipLaunchKernelGGL(pack_sym_t_kernel<float>, dim3((npk + 255) / 256), dim3(256), 0, c->st, (const double*)c->Wbar, reinterpret_cast<float*>(c->WbT), T, p);
   }
-  CholWS lw = c->sws;
-  lw.ld = rpad; lw.npad = rpad; lw.nact = round_up(c->rtot, 64);
-  const int nblk64 = c->rank_compact ? round_up(c->rtot16, 64) / 64 : rpad / 64, npairs = nblk64 * (nblk64 + 1) / 2;
-  const int* cmap = c->rank_compact ? c->d_cmap : nullptr;
-  hipLaunchKernelGGL(assemble_b_kernel_t<double>, dim3(npairs, 1), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad, nblk64, (const double*)c->Flr, c->Tp, T, p, c->d_blk_lat,
-                     c->d_blk_col, c->Wtbar, 0LL, c->ident, 1, cmap);
-  if (cmap && rpad > c->rtot)
-    hipLaunchKernelGGL(pad_identity_kernel<double>, dim3((rpad + 3) / 4, 1), dim3(256), 0, c->st, lw.H, (long long)lw.sH, rpad, c->rtot, rpad, lw.nact, (int)NB, c->ident);
-  HIPC(hipGetLastError());
+  const CholWS lw = lowrank_view(c, c->sws);
+  CHK(assemble_rxr<double>(c, lw, 1, c->Flr, c->Wtbar, 0LL, c->ident));
   HIPC(hipMemsetAsync(c->sws.info, 0, sizeof(int), c->st));
   CHK(factor(c, lw, nullptr, 1));
   HIPC(hipMemsetAsync(lw.Mt, 0, (size_t)rpad * rpad * sizeof(double), c->st));
@@ -522,7 +518,7 @@ static SolveForm solve_form(const pgpfa_ctx* c, int nb) {
   SolveForm sf{};
   // (small chunks are launch-latency bound: there the extra packing / check launches of the host-free form cost more than
   // the round trips they remove - measured at config 2: 8.6 vs 8.0 ms per E-step)
-  sf.thin_ok = c->thin_products && c->mfma && T >= 4 && (size_t)c->rpad <= (size_t)c->ld;
+  sf.thin_ok = thin_ok(c);
   // (11 .. 20 latents: only the round-5 form of the host-free step exists - pcgw_*_kernel - and it needs the thin products)
   sf.wide_ok = p <= 20 && c->pcg_form >= 2 && sf.thin_ok && c->pcg_w32 && c->pcg_retire && c->pcg_blk != nullptr;
   sf.fused = c->pcg_fused && c->plan_lowrank && (p <= 16 || sf.wide_ok) && c->h_pcg != nullptr && (c->pcg_fused == 2 || (double)nb * c->n >= 1.0e6);

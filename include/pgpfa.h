@@ -175,6 +175,9 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
  * "interp_chunk_trials" (0 - the default: pgpfa_posterior_at walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
+ * "covat_chunk_trials" (0 - the default; the same for pgpfa_posterior_cov_at), "covat_block_times" (0 - the default: pgpfa_posterior_cov_at walks
+ * its query times in blocks sized so that the right-hand sides of a block stay within that bound; > 0: that many times per block, rounded up to 16.
+ * No output depends on it, bit for bit),
  * "counts_chunk_trials" (0 - the default; the same for pgpfa_posterior_counts), "counts_nodes" (32: nodes of the Gauss-Hermite rule of
  * pgpfa_count_probabilities / pgpfa_posterior_counts, 8 .. 64; the rule's error falls with it and the cost grows in proportion). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
@@ -378,6 +381,28 @@ int pgpfa_posterior_sample(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
 int pgpfa_posterior_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
                        int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
                        double* mean /* [n][p][S] or NULL */, double* var /* [n][p][S] or NULL */);
+
+/* Cross-latent posterior covariance and log-rate moments at arbitrary time points: what pgpfa_posterior_at leaves out.  With a_k(s) = K_k^-1 kx_k(s)
+ * as there and Sigma the trial's p T x p T posterior covariance (the layout of pgpfa_get_post_cov),
+ *   cov(s)[k][l] = a_k(s)^T Sigma_kl a_l(s) + delta_kl (1 - a_k(s) . kx_k(s))
+ * - at a grid time post_vsm of that bin, on the diagonal the var of pgpfa_posterior_at - and per neuron n the Gaussian log rate at s:
+ *   eta[n][s] = d_n + c_n . mean(s),   var[n][s] = c_n^T cov(s) c_n                (rate, bands: as for pgpfa_posterior_rates)
+ * Sigma is never formed: the call builds the square root pgpfa_posterior_sample draws from (dense engine: L^-T of the Hessian; low-rank engine:
+ * eps G + (G F L^-T)(G F L^-T)^T), pushes the p weight vectors of every time through it with the library's GEMM and takes their p x p Gram on the
+ * FP64 matrix cores (csrc/covat.h).  times_ms and per_trial mean what they mean for pgpfa_posterior_at; so do the parameter snapshots, trials of
+ * unequal length (times behind T_r: the forecast) and the missing-data tables.
+ * A trial's result does not depend on its position in the list, on which other trials are listed, on how the list is cut into chunks or the query
+ * times into blocks (options "covat_chunk_trials", "covat_block_times"), or on which other outputs are asked for, bit for bit; cov is symmetric to
+ * the bit, its diagonal and var are clamped at 0.  No floating-point atomics.
+ * Fails, naming what is wrong: S < 1; all four outputs NULL; times_ms NULL; a time that is not finite, naming its position (before any device
+ * call); set_params not called; an asynchronous timescale pass in flight; a trial without a posterior, naming the trial; a posterior uploaded with
+ * pgpfa_set_posterior (only its blocks are known: it has no square root); a variational posterior of a trial shorter than T.
+ * Leaves untouched what pgpfa_posterior_sample leaves untouched: post_mean, post_vsm, post_vsmGP and their resident marks, the sums
+ * pgpfa_mstep_precomp reads, mode serials, snapshots, log evidence, the resident counts and the three missing-data tables.  Uses the chunk workspace. */
+int pgpfa_posterior_cov_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                           int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
+                           double* mean /* [n][p][S] or NULL */, double* cov /* [n][S][p][p] or NULL */,
+                           double* eta /* [n][q][S] or NULL */, double* var /* [n][q][S] or NULL */);
 
 /* Posterior-predictive spike counts from the two moments of the log rate.  The reference has no counterpart: it stops at the latent posterior, and
  * its only count-like outputs are exp(C x + d) at a held-out mode (util.py:289-334).  With eta ~ N(m, v) the count of an entry is the

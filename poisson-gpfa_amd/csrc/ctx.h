@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, workspace, copies; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -123,6 +123,7 @@ struct pgpfa_ctx {
   // sum_r Sigma_r^{kk} here instead of storing R x p blocks of T x T; per-trial blocks are rebuilt on request
   double* Pacc = nullptr;                        // [p][Tp][Tp]
   double* gemm_part = nullptr; size_t gemm_part_len = 0;   // split-K partial products of the thin GEMMs
+  bool no_splitk = false;                        // while set gemm() never cuts k: a product's bits then follow neither the batch nor the tile count (covat.hip)
   double *CCu = nullptr, *C16 = nullptr;         // zero-padded pair-product / loading tables of the MFMA Poisson pass
   int qpad = 0, ccu_cols = 0;
   double* ppart = nullptr;                       // [p][PACC_SPLITS + 1][T x T] split-K partial products
@@ -326,6 +327,8 @@ struct pgpfa_ctx {
   int rates_chunk = 0;                            // trials per chunk of a call (0: from the 256 MiB bound on the staging of the per-trial planes)
   int sample_chunk = 0;                           // option sample_chunk_trials: the same for pgpfa_posterior_sample (psample.hip); no output depends on it
   int interp_chunk = 0;                           // option interp_chunk_trials: the same for pgpfa_posterior_at (interp.hip); no output depends on it
+  int covat_chunk = 0;                            // option covat_chunk_trials: the same for pgpfa_posterior_cov_at (covat.hip); no output depends on it
+  int covat_block = 0;                            // option covat_block_times: query times per block of that call's right-hand sides (0: from the same bound); no output depends on it
   // predictive counts (pgpfa_count_probabilities / pgpfa_posterior_counts, rates.hip): the Gauss-Hermite nodes and log weights of the rule, computed on
   // the host and uploaded on first use and again when option counts_nodes has changed (counts_nodes_Q: the node count the device copy holds)
   int counts_chunk = 0;                           // option counts_chunk_trials: the same for pgpfa_posterior_counts; no output depends on it
@@ -580,6 +583,10 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
 int var_offsets(pgpfa_ctx* c, int nb, double* out);
 int check_distinct(const std::vector<int>& v);
 int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out);
+// interp.hip: kx and A = Kinv kx of `grids` time grids whose times are on the device ([grid][p][T16][Spad], interp.h), as pgpfa_posterior_at forms them
+int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A);
+// rates.hip: rates_kernel on staged planes (pgpfa_posterior_cov_at)
+int rates_staged_planes(pgpfa_ctx* c, const char* entry, const double* mean, const double* cov, int Tplane, int nslots, double* eta, double* var);
 // misc.hip
 int allreduce_dev(pgpfa_ctx* c, double* buf, size_t count);
 

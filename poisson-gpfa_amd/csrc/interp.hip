@@ -134,6 +134,10 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
 
 }  // namespace
 
+int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A) {
+  return weights(c, d_times, grids, S, Spad, T16, kx, A);
+}
+
 int pgpfa_posterior_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, const double* times_ms, int per_trial, double* mean, double* var) {
   if (!c) return fail("null context");
   if (S < 1) return fail("pgpfa_posterior_at: S = %d, at least one query time is needed", S);

@@ -62,7 +62,7 @@ int gemm(pgpfa_ctx* c, bool transb, GemmP g, bool f32) {
   const double k_eff = g.k_loop_hint > 0 ? (double)g.k_loop_hint
                        : (g.flops_hint > 0.0 && g.M > 0 && g.N > 0) ? g.flops_hint / (2.0 * g.M * g.N * std::max(g.nbatch, 1)) : (double)g.K;
   const int split_below = g.bm == 64 ? c->splitk_below64 : 384;
-  if (!f32 && c->gemm_part && g.mode == GEMM_FULL && g.kflags == 0 && g.nb_lo == 0 && g.kseg == 0 && tiles > 0 && tiles < split_below && k_eff >= 128.0) {
+  if (!f32 && c->gemm_part && !c->no_splitk && g.mode == GEMM_FULL && g.kflags == 0 && g.nb_lo == 0 && g.kseg == 0 && tiles > 0 && tiles < split_below && k_eff >= 128.0) {
     // (a lone workgroup per CU walks its k loop at the latency of one global load per 16-wide step: with a handful of
     // tiles even a 128-long loop is worth cutting, down to parts of two steps)
     ksplit = std::min(std::min(8, (int)(k_eff / (tiles < 64 ? 32.0 : 64.0))), (c->splitk_target + tiles - 1) / tiles);

@@ -78,6 +78,18 @@ int rates_launch_chunk(pgpfa_ctx* c, const RatesP& a, const RatesGeom& g, bool g
 
 }  // namespace
 
+// eta / var of `nslots` staged planes - mean [nslots][p][Tplane], cov [nslots][Tplane][p][p], device - into eta / var [nslots][q][Tplane] (either may be
+// NULL): rates_kernel with the planes in place of Xmode / vsm, Tplane bins, every bin live, slot z the item z (pgpfa_posterior_cov_at, covat.hip)
+int rates_staged_planes(pgpfa_ctx* c, const char* entry, const double* mean, const double* cov, int Tplane, int nslots, double* eta, double* var) {
+  RatesGeom geo = rates_geom(c);
+  geo.nbt = (Tplane + 16 * geo.nbt_w - 1) / (16 * geo.nbt_w);
+  CHK(rates_table(c, geo, entry));
+  RatesP a = rates_args(c, geo, c->ident);
+  a.Xmode = mean; a.vsm = cov; a.len = nullptr; a.T = Tplane;
+  a.eta = eta; a.var = var; a.c0 = 0;
+  return rates_launch_chunk(c, a, geo, false, nslots);
+}
+
 // Host side of the group table: positions of every group in list order, as CSR (start[g] .. start[g + 1] into pos).  first / last bound the positions
 // taken (a chunk of the list).  Exported for the host tests: no device is touched.
 extern "C" int pgpfa_rates_group_csr(int n, const int32_t* group, int n_groups, int first, int last, int32_t* start /* [n_groups + 1] */, int32_t* pos /* [last - first] */) {

@@ -402,7 +402,7 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
     return out
 
 
-_AT_KEYS = ('mean', 'var', 'lower', 'upper')
+_AT_KEYS = ('mean', 'var', 'lower', 'upper', 'cov')
 
 
 def _condition_means_at(mean, times, group, n_groups, spans):
@@ -434,9 +434,11 @@ def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=
     the resident ones: that posterior, evaluated under the timescales of the E-step that produced it.  Anything else raises ValueError.
     trials: positions in experiment.data (None: all; repeats allowed).  conditions: one integer label per listed trial.
     want: any of 'mean', 'var' (marginal posterior mean and variance of every latent), 'lower' / 'upper' (mean -+ z sqrt(var), the central
-    `level` band).  Returns a dict of the asked keys as (n, xdim, S) arrays plus 'times'; with `conditions` also 'condition_mean' (G, xdim, S) -
-    the mean over the condition's trials of the posterior mean, a trial entering at s only inside its own recorded span 0 <= s <= (T_r - 1)
-    binSize; 0 where no trial has the time -, 'condition_count' (G, S) and 'condition_labels' (G)."""
+    `level` band) - (n, xdim, S) arrays - and 'cov', the joint (xdim, xdim) covariance of the latents at every time, (n, S, xdim, xdim)
+    (pgpfa_posterior_cov_at; it needs a posterior an E-step of this session wrote).  Returns a dict of the asked keys plus 'times'; with
+    `conditions` also 'condition_mean' (G, xdim, S) - the mean over the condition's trials of the posterior mean, a trial entering at s only
+    inside its own recorded span 0 <= s <= (T_r - 1) binSize; 0 where no trial has the time -, 'condition_count' (G, S) and
+    'condition_labels' (G)."""
     from . import _session, inference
     want = tuple(want)
     unknown = [k for k in want if k not in _AT_KEYS]
@@ -457,16 +459,71 @@ def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=
         raise ValueError('nothing asked for: want is empty and there are no conditions')
     need_var = any(k in want for k in ('var', 'lower', 'upper'))
     need_mean = labels is not None or any(k in want for k in ('mean', 'lower', 'upper'))
-    dev = sess.ctx.posterior_at(tt, idx, want=(('mean',) if need_mean else ()) + (('var',) if need_var else ()))
+    dev = {}
+    if need_mean or need_var:
+        dev = sess.ctx.posterior_at(tt, idx, want=(('mean',) if need_mean else ()) + (('var',) if need_var else ()))
+    if 'cov' in want:
+        dev['cov'] = sess.ctx.posterior_cov_at(tt, idx, want=('cov',))['cov']
     out = {'times': tt}
     sd = np.sqrt(dev['var']) if ('lower' in want or 'upper' in want) else None
-    made = {'mean': lambda: dev['mean'], 'var': lambda: dev['var'], 'lower': lambda: dev['mean'] - z * sd, 'upper': lambda: dev['mean'] + z * sd}
+    made = {'mean': lambda: dev['mean'], 'var': lambda: dev['var'], 'lower': lambda: dev['mean'] - z * sd, 'upper': lambda: dev['mean'] + z * sd,
+            'cov': lambda: dev['cov']}
     for k in want:
         out[k] = made[k]()
     if labels is not None:
         binSize = float(experiment.binSize)
         spans = [((sess.T if sess.lengths is None else int(sess.lengths[int(t)])) - 1) * binSize for t in idx]
         out['condition_mean'], out['condition_count'] = _condition_means_at(dev['mean'], tt, group, len(labels), spans)
+        out['condition_labels'] = labels
+    return out
+
+
+_RATE_AT_KEYS = ('rate', 'lower', 'upper', 'median', 'eta', 'var')
+
+
+def posteriorRatesAt(params, experiment, times, infRes=None, trials=None, conditions=None, level=0.95, want=('rate', 'lower', 'upper')):
+    """Single-trial firing rates of the listed trials at arbitrary time points, with a credible band, and their condition averages on a common
+    axis: posteriorRates off the bin grid.  The log rate of neuron n at time s is Gaussian with eta = d_n + c_n . mean(s) and var = c_n^T
+    Cov(x(s)) c_n, where mean(s) and the joint covariance Cov(x(s)) of the latents are those of posteriorAt (pgpfa_posterior_cov_at); neither the
+    covariance nor post_vsmGP comes to the host.
+
+    times, infRes, trials, conditions: as for posteriorAt; the posterior has to be one an E-step of this session wrote, and C, d and the
+    timescales are those of that E-step (restored around the call when the session has moved on).
+    want: any of 'rate' (exp(eta + var/2)), 'lower' / 'upper' (the central `level` band exp(eta -+ z sqrt(var))), 'median' (exp(eta)) - in spikes
+    per SECOND, the definitions of posteriorRates - and 'eta' / 'var'.  Returns a dict of the asked keys as (n, ydim, S) arrays plus 'times'; with
+    `conditions` also 'condition_mean' (G, ydim, S) - the mean of 'rate' over the condition's trials, a trial entering at s only inside its own
+    recorded span 0 <= s <= (T_r - 1) binSize; 0 where no trial has the time -, 'condition_count' (G, S) and 'condition_labels' (G)."""
+    want = tuple(want)
+    unknown = [k for k in want if k not in _RATE_AT_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_RATE_AT_KEYS)))
+    z = _band_z(level)
+    tt = np.asarray(times, dtype=np.float64)
+    tt = np.ascontiguousarray(tt) if tt.ndim else tt
+    if tt.ndim not in (1, 2) or tt.shape[-1] < 1:
+        raise ValueError('times: shape (S,) or (n, S) with S >= 1 expected, got %s' % (tt.shape,))
+    if not np.all(np.isfinite(tt)):                    # (before the session is touched: nothing reaches the device)
+        raise ValueError('times: entry %s is not finite' % (tuple(int(i) for i in np.argwhere(~np.isfinite(tt))[0]),))
+    if not want and conditions is None:
+        raise ValueError('nothing asked for: want is empty and there are no conditions')
+    sess, idx = _resident_posterior('posteriorRatesAt', params, experiment, infRes, trials, set_params=True)
+    if tt.ndim == 2 and tt.shape[0] != idx.size:
+        raise ValueError('times: one grid per listed trial expected, (%d, S), got %s' % (idx.size, tt.shape))
+    labels, group = (None, None) if conditions is None else _condition_groups(conditions, idx.size)
+    dev = sess.ctx.posterior_cov_at(tt, idx, want=('eta', 'var'))
+    eta, var = dev['eta'], dev['var']
+    per_s = 1000.0 / float(experiment.binSize)
+    sd = np.sqrt(var) if ('lower' in want or 'upper' in want) else None
+    made = {'eta': lambda: eta, 'var': lambda: var, 'median': lambda: np.exp(eta) * per_s, 'rate': lambda: np.exp(eta + 0.5 * var) * per_s,
+            'lower': lambda: np.exp(eta - z * sd) * per_s, 'upper': lambda: np.exp(eta + z * sd) * per_s}
+    out = {'times': tt}
+    for k in want:
+        out[k] = made[k]()
+    if labels is not None:
+        binSize = float(experiment.binSize)
+        spans = [((sess.T if sess.lengths is None else int(sess.lengths[int(t)])) - 1) * binSize for t in idx]
+        rate = out['rate'] if 'rate' in out else made['rate']()
+        out['condition_mean'], out['condition_count'] = _condition_means_at(rate, tt, group, len(labels), spans)
         out['condition_labels'] = labels
     return out
 

@@ -175,6 +175,7 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
  * "interp_chunk_trials" (0 - the default: pgpfa_posterior_at walks its list in chunks whose device staging stays within 256 MiB; > 0: that many
  * trials per chunk.  No output depends on it, bit for bit; it exists for the test of exactly that),
+ * "velat_chunk_trials" (0 - the default; the same for pgpfa_posterior_velocity_at),
  * "covat_chunk_trials" (0 - the default; the same for pgpfa_posterior_cov_at), "covat_block_times" (0 - the default: pgpfa_posterior_cov_at walks
  * its query times in blocks sized so that the right-hand sides of a block stay within that bound; > 0: that many times per block, rounded up to 16.
  * No output depends on it, bit for bit),
@@ -403,6 +404,30 @@ int pgpfa_posterior_cov_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
                            int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
                            double* mean /* [n][p][S] or NULL */, double* cov /* [n][S][p][p] or NULL */,
                            double* eta /* [n][q][S] or NULL */, double* var /* [n][q][S] or NULL */);
+
+/* Value and velocity of every latent at arbitrary time points, with their joint 2 x 2 posterior per latent.  Under the prior the time derivative
+ * xdot_k(s) is jointly Gaussian with the grid values, so its posterior follows by the prior conditional of pgpfa_posterior_at with the cross Gram
+ * differentiated.  With kx_k(s), a_k(s), m_k, V_k as there, l_k = 1000 tau_k ms:
+ *   kd_k(s)[j]       = -1000 (s - j bin) / l_k^2 (1 - eps) exp(-1/2 (s - j bin)^2 / l_k^2)      (Cov(xdot_k(s), x_k(j bin)), per SECOND)
+ *   b_k(s)           = K_k^-1 kd_k(s),   kappa_k = (1 - eps) / tau_k^2                            (the prior variance of the velocity, 1/s^2)
+ *   mean[i][k][s]    = a . m_k                          vel[i][k][s]     = b . m_k
+ *   var[i][k][s]     = 1 - a . kx + a^T V_k a           vel_var[i][k][s] = kappa_k - b . kd + b^T V_k b         (both stored as max(., 0))
+ *   cross[i][k][s]   =   - a . kd + a^T V_k b           (the posterior Cov(x_k(s), xdot_k(s)); 0 under the prior)
+ * The velocity is that of the smooth component of the latent - the white eps part has no derivative, so kd has no nugget term even at a grid time -
+ * in latent units per second.  mean has the bits of pgpfa_posterior_at.  var, vel_var and cross come from ONE pass over the T x T blocks, on the FP64
+ * matrix cores (csrc/velat.h).  Far from the trial vel -> 0, cross -> 0, var -> 1, vel_var -> kappa_k.  times_ms, per_trial, parameter snapshots,
+ * uploaded posteriors, trials of unequal length and the sum-only plan: as for pgpfa_posterior_at.
+ * A plane's bits do not depend on which other planes are asked for, on the trial's position in the list, on which other trials are listed, on how
+ * the list is cut into chunks (option "velat_chunk_trials") or on shared against per-trial grids, given the same blocks: under the sum-only plan
+ * every call rebuilds the blocks of its list, and the last bits of a rebuilt block follow the number of trials rebuilt together, as for
+ * pgpfa_posterior_at (var, vel_var and cross then move in the last digits with the SET of listed trials; mean and vel never).  No floating-point atomics.
+ * Not given: the cross-latent covariance of the velocities (hence velocities in orthonormalised coordinates and the variance of the speed),
+ * derivatives of firing rates, sharded sessions.
+ * Fails and leaves untouched what pgpfa_posterior_at does, in the same words under this entry point's name; all five outputs NULL is refused. */
+int pgpfa_posterior_velocity_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                                int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
+                                double* mean /* [n][p][S] or NULL */, double* var /* [n][p][S] or NULL */, double* vel /* [n][p][S] or NULL */,
+                                double* vel_var /* [n][p][S] or NULL */, double* cross /* [n][p][S] or NULL */);
 
 /* Posterior-predictive spike counts from the two moments of the log rate.  The reference has no counterpart: it stops at the latent posterior, and
  * its only count-like outputs are exp(C x + d) at a held-out mode (util.py:289-334).  With eta ~ N(m, v) the count of an entry is the

@@ -1300,6 +1300,7 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "sample_chunk_trials") CHK(chunk_trials(&c->sample_chunk));
   else if (k == "interp_chunk_trials") CHK(chunk_trials(&c->interp_chunk));
   else if (k == "covat_chunk_trials") CHK(chunk_trials(&c->covat_chunk));
+  else if (k == "velat_chunk_trials") CHK(chunk_trials(&c->velat_chunk));
   else if (k == "covat_block_times") { if (v < 0.0 || v != std::floor(v)) return fail("covat_block_times is a count of query times, or 0"); c->covat_block = (int)v; }
   else if (k == "rates_chunk_trials") CHK(chunk_trials(&c->rates_chunk));
   else if (k == "counts_chunk_trials") CHK(chunk_trials(&c->counts_chunk));

@@ -328,6 +328,7 @@ struct pgpfa_ctx {
   int sample_chunk = 0;                           // option sample_chunk_trials: the same for pgpfa_posterior_sample (psample.hip); no output depends on it
   int interp_chunk = 0;                           // option interp_chunk_trials: the same for pgpfa_posterior_at (interp.hip); no output depends on it
   int covat_chunk = 0;                            // option covat_chunk_trials: the same for pgpfa_posterior_cov_at (covat.hip); no output depends on it
+  int velat_chunk = 0;                            // option velat_chunk_trials: the same for pgpfa_posterior_velocity_at (velat.hip); no output depends on it
   int covat_block = 0;                            // option covat_block_times: query times per block of that call's right-hand sides (0: from the same bound); no output depends on it
   // predictive counts (pgpfa_count_probabilities / pgpfa_posterior_counts, rates.hip): the Gauss-Hermite nodes and log weights of the rule, computed on
   // the host and uploaded on first use and again when option counts_nodes has changed (counts_nodes_Q: the node count the device copy holds)
@@ -585,6 +586,16 @@ int check_distinct(const std::vector<int>& v);
 int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out);
 // interp.hip: kx and A = Kinv kx of `grids` time grids whose times are on the device ([grid][p][T16][Spad], interp.h), as pgpfa_posterior_at forms them
 int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A);
+// the GEMM half of interp_weights: A = Kinv rhs for `grids` right-hand sides in the layout of kx (two-level batch, fixed 64-tile, off split-K)
+int interp_solve(pgpfa_ctx* c, const double* rhs, int grids, int Spad, int T16, double* A);
+struct MarkKeeper {                                           // the resident marks of post_vsmGP are what they were when the call returns
+  pgpfa_ctx* c;
+  std::vector<std::pair<int, char>> saved;
+  ~MarkKeeper() { for (auto& kv : saved) c->vsmgp_ok[kv.first] = kv.second; }
+};
+// the T x T blocks of the trials `tos` (one snapshot) made resident for a query: the buffer, blocks rebuilt on demand under the sum-only plan with
+// post_vsm of the rebuilt trials set aside (scratch from `dev`) and put back, the marks restored when `keep` goes out of scope
+int interp_blocks_resident(pgpfa_ctx* c, DevBufs& dev, MarkKeeper& keep, const std::vector<int>& tos);
 // rates.hip: rates_kernel on staged planes (pgpfa_posterior_cov_at)
 int rates_staged_planes(pgpfa_ctx* c, const char* entry, const double* mean, const double* cov, int Tplane, int nslots, double* eta, double* var);
 // misc.hip

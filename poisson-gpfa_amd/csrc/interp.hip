@@ -10,12 +10,6 @@ namespace {
 constexpr size_t INTERP_LDS_MAX = (size_t)160 << 10;          // LDS of a CU: the row panel of interp_var_kernel has to fit
 constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
 
-struct MarkKeeper {                                           // the resident marks of post_vsmGP are what they were when the call returns
-  pgpfa_ctx* c;
-  std::vector<std::pair<int, char>> saved;
-  ~MarkKeeper() { for (auto& kv : saved) c->vsmgp_ok[kv.first] = kv.second; }
-};
-
 struct AtArgs {
   const std::vector<int>* trials;     // trial of every list position
   int S; const double* times; bool per_trial;
@@ -27,12 +21,19 @@ int weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int
   const int p = c->p, T = c->T;
   hipLaunchKernelGGL(interp_cross_kernel, dim3(T16, p, grids), dim3(256), 0, c->st, d_times, c->tau, c->bin, c->eps, T, T16, S, Spad, p, kx);
   HIPC(hipGetLastError());
+  return interp_solve(c, kx, grids, Spad, T16, A);
+}
+
+}  // namespace
+
+int interp_solve(pgpfa_ctx* c, const double* rhs, int grids, int Spad, int T16, double* A) {
+  const int p = c->p, T = c->T;
   // A[t][s] = sum_u Kinv[t][u] kx[u][s]: column-major C (Spad x T, ld Spad) = kx (Spad x T16) Kinv^T.  Kinv is the identity in its padding and the
   // rows u >= T of kx are zero.  The batch is declared as the low half of a two-level one (latents below, grids above) and the tile is fixed, which
   // keeps the launch off the split-K path: the bits of a trial's weights must not follow the number of grids in a chunk.
   const long long slab = (long long)T16 * Spad;
   GemmP g{};
-  g.A = kx; g.sA = slab; g.lda = Spad;
+  g.A = rhs; g.sA = slab; g.lda = Spad;
   g.B = c->Kinv; g.sB = (long long)c->Tp * c->Tp; g.ldb = c->Tp;
   g.C = A; g.sC = slab; g.ldc = Spad;
   g.M = Spad; g.N = T; g.K = T16; g.alpha = 1.0; g.beta = 0.0;
@@ -40,6 +41,32 @@ int weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int
   g.mode = GEMM_FULL; g.kflags = 0; g.bm = 64;
   return gemm(c, false, g);
 }
+
+int interp_blocks_resident(pgpfa_ctx* c, DevBufs& dev, MarkKeeper& keep, const std::vector<int>& tos) {
+  const int p = c->p, T = c->T;
+  CHK(ensure_vsmgp_buffer(c));
+  // blocks rebuilt on demand under the sum-only plan (same snapshot, so no parameter switch).  The rebuild also rewrites post_vsm of those trials
+  // - by another kernel than the sum-only E-step, so not to the bit: their post_vsm is set aside and put back, and so are the resident marks
+  std::vector<int> rebuilt;
+  for (int t : tos) {
+    keep.saved.emplace_back(t, c->vsmgp_ok[t]);
+    if (!c->vsmgp_ok[t] && std::find(rebuilt.begin(), rebuilt.end(), t) == rebuilt.end()) rebuilt.push_back(t);
+  }
+  if (!rebuilt.empty()) {
+    const size_t lv = (size_t)T * p * p;
+    double* d_vsm = nullptr;
+    CHK(dev.get(&d_vsm, rebuilt.size() * lv));
+    for (size_t i = 0; i < rebuilt.size(); ++i)
+      HIPC(hipMemcpyAsync(d_vsm + i * lv, c->vsm + (size_t)rebuilt[i] * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+    const int rc = ensure_trial_vsmgp(c, tos);
+    for (size_t i = 0; i < rebuilt.size(); ++i)
+      HIPC(hipMemcpyAsync(c->vsm + (size_t)rebuilt[i] * lv, d_vsm + i * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
+    CHK(rc);
+  }
+  return 0;
+}
+
+namespace {
 
 // the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
 int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
@@ -53,27 +80,7 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
 
   DevBufs dev("pgpfa_posterior_at");
   MarkKeeper keep{c, {}};
-  if (a.var) {
-    CHK(ensure_vsmgp_buffer(c));
-    // blocks rebuilt on demand under the sum-only plan (same snapshot, so no parameter switch).  The rebuild also rewrites post_vsm of those trials
-    // - by another kernel than the sum-only E-step, so not to the bit: their post_vsm is set aside and put back, and so are the resident marks
-    std::vector<int> rebuilt;
-    for (int t : tos) {
-      keep.saved.emplace_back(t, c->vsmgp_ok[t]);
-      if (!c->vsmgp_ok[t] && std::find(rebuilt.begin(), rebuilt.end(), t) == rebuilt.end()) rebuilt.push_back(t);
-    }
-    if (!rebuilt.empty()) {
-      const size_t lv = (size_t)T * p * p;
-      double* d_vsm = nullptr;
-      CHK(dev.get(&d_vsm, rebuilt.size() * lv));
-      for (size_t i = 0; i < rebuilt.size(); ++i)
-        HIPC(hipMemcpyAsync(d_vsm + i * lv, c->vsm + (size_t)rebuilt[i] * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
-      const int rc = ensure_trial_vsmgp(c, tos);
-      for (size_t i = 0; i < rebuilt.size(); ++i)
-        HIPC(hipMemcpyAsync(c->vsm + (size_t)rebuilt[i] * lv, d_vsm + i * lv, lv * sizeof(double), hipMemcpyDeviceToDevice, c->st));
-      CHK(rc);
-    }
-  }
+  if (a.var) CHK(interp_blocks_resident(c, dev, keep, tos));
 
   // chunks of the group: device staging per trial (per-trial cross Grams, weights, results)
   const size_t slab = (size_t)p * T16 * Spad;

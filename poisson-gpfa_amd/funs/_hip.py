@@ -49,6 +49,7 @@ _SIGNATURES = {
     'pgpfa_posterior_sample': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p, ct.POINTER(ct.c_uint16), c_int32_p],
     'pgpfa_posterior_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p],
     'pgpfa_posterior_cov_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p],
+    'pgpfa_posterior_velocity_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int] + [c_double_p] * 5,
     'pgpfa_count_probabilities': [ct.c_void_p, ct.c_longlong, c_double_p, c_double_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p,
                                   c_int32_p, c_double_p, c_double_p],
     'pgpfa_posterior_counts': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p,
@@ -463,6 +464,25 @@ class Context:
         out = {k: np.empty(shapes[k]) for k in shapes if k in want}
         ptr = lambda k: dptr(out[k]) if k in out else None
         check(self.lib.pgpfa_posterior_cov_at(self.h, n, iptr(ii), S, dptr(tt), per_trial, ptr('mean'), ptr('cov'), ptr('eta'), ptr('var')))
+        return out
+
+    def posterior_velocity_at(self, times, idx=None, want=('mean', 'vel')):
+        """Value and velocity of every latent of the listed trials (repeats allowed) at arbitrary times, with their joint 2 x 2 posterior per latent
+        (include/pgpfa.h: pgpfa_posterior_velocity_at).  times: as for posterior_at.  want: any of 'mean', 'var' (of the value), 'vel', 'vel_var'
+        (latent units per second, and its square) and 'cross' (Cov(value, velocity)), each [n][p][S].  Returns a dict of exactly the arrays asked for."""
+        n, ii = self._n_idx(idx)
+        keys = ('mean', 'var', 'vel', 'vel_var', 'cross')
+        _check_outputs(want, keys)
+        tt = as_f64(times)
+        if tt.ndim == 1:
+            per_trial = 0
+        elif tt.ndim == 2 and tt.shape[0] == n:
+            per_trial = 1
+        else:
+            raise ValueError('times must have shape (S,) or (n, S) = (%d, S), got %s' % (n, tt.shape))
+        S = tt.shape[-1]
+        out = {k: np.empty((n, self.p, S)) for k in keys if k in want}
+        check(self.lib.pgpfa_posterior_velocity_at(self.h, n, iptr(ii), S, dptr(tt), per_trial, *[dptr(out[k]) if k in out else None for k in keys]))
         return out
 
     def _count_outputs(self, shape, counts, K, level, k_cap, want):

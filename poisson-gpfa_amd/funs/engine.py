@@ -333,6 +333,15 @@ class PPGPFAfit():
         self.trajectoriesAt = util.posteriorAt(self.optimParams, self.experiment, times, **kw)
         return self.trajectoriesAt
 
+    def posteriorVelocityAt(self, **kw):
+        """util.posteriorVelocityAt at the fitted parameters -> self.velocitiesAt (a dict; keywords as there: times, infRes, trials, conditions,
+        level, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        times = kw.pop('times')
+        self.velocitiesAt = util.posteriorVelocityAt(self.optimParams, self.experiment, times, **kw)
+        return self.velocitiesAt
+
     def posteriorRatesAt(self, **kw):
         """util.posteriorRatesAt at the fitted parameters -> self.ratesAt (a dict; keywords as there: times, infRes, trials, conditions, level,
         want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""

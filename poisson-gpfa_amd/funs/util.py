@@ -478,6 +478,60 @@ def posteriorAt(params, experiment, times, infRes=None, trials=None, conditions=
     return out
 
 
+_VEL_AT_KEYS = ('vel', 'var', 'lower', 'upper', 'value', 'value_var', 'cross', 'speed2')
+
+
+def posteriorVelocityAt(params, experiment, times, infRes=None, trials=None, conditions=None, level=0.95, want=('vel', 'lower', 'upper')):
+    """The time derivative of the latent trajectories of the listed trials at arbitrary time points, with a credible band, jointly with the value:
+    phase portraits (x_k, xdot_k), speed profiles around an event, condition-averaged velocities on a common axis.  The GP gives the derivative
+    exactly - xdot_k(s) is jointly Gaussian with the grid values under the prior - so nothing is differenced (pgpfa_posterior_velocity_at).  The
+    velocity is that of the smooth component of the latent, in latent units per SECOND.
+
+    times, infRes, trials, conditions: as for posteriorAt.
+    want: any of 'vel', 'var' (posterior mean and variance of the velocity of every latent), 'lower' / 'upper' (vel -+ z sqrt(var), the central
+    `level` band), 'value' / 'value_var' (mean and variance of the latent itself: the 'mean' / 'var' of posteriorAt), 'cross' (the posterior
+    covariance of value and velocity of the same latent) - (n, xdim, S) arrays - and 'speed2' (n, S): sum_k (vel_k^2 + var_k), the posterior
+    expectation of the squared speed in the model's latent coordinates.  Returns a dict of the asked keys plus 'times'; with `conditions` also
+    'condition_mean' (G, xdim, S) - the mean of 'vel' over the condition's trials, a trial entering at s only inside its own recorded span -,
+    'condition_count' (G, S) and 'condition_labels' (G).
+    Not given: the covariance of the velocities ACROSS latents - hence velocities in orthonormalised coordinates and the variance of the speed -,
+    derivatives of firing rates, sharded sessions."""
+    want = tuple(want)
+    unknown = [k for k in want if k not in _VEL_AT_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_VEL_AT_KEYS)))
+    z = _band_z(level)
+    tt = np.asarray(times, dtype=np.float64)
+    tt = np.ascontiguousarray(tt) if tt.ndim else tt
+    if tt.ndim not in (1, 2) or tt.shape[-1] < 1:
+        raise ValueError('times: shape (S,) or (n, S) with S >= 1 expected, got %s' % (tt.shape,))
+    if not np.all(np.isfinite(tt)):                    # (before the session is touched: nothing reaches the device)
+        raise ValueError('times: entry %s is not finite' % (tuple(int(i) for i in np.argwhere(~np.isfinite(tt))[0]),))
+    if not want and conditions is None:
+        raise ValueError('nothing asked for: want is empty and there are no conditions')
+    sess, idx = _resident_posterior('posteriorVelocityAt', params, experiment, infRes, trials, set_params=True)
+    if tt.ndim == 2 and tt.shape[0] != idx.size:
+        raise ValueError('times: one grid per listed trial expected, (%d, S), got %s' % (idx.size, tt.shape))
+    labels, group = (None, None) if conditions is None else _condition_groups(conditions, idx.size)
+    needs = {'vel': labels is not None or any(k in want for k in ('vel', 'lower', 'upper', 'speed2')),
+             'vel_var': any(k in want for k in ('var', 'lower', 'upper', 'speed2')),
+             'mean': 'value' in want, 'var': 'value_var' in want, 'cross': 'cross' in want}
+    dev = sess.ctx.posterior_velocity_at(tt, idx, want=tuple(k for k in ('mean', 'var', 'vel', 'vel_var', 'cross') if needs[k]))
+    sd = np.sqrt(dev['vel_var']) if ('lower' in want or 'upper' in want) else None
+    made = {'vel': lambda: dev['vel'], 'var': lambda: dev['vel_var'], 'lower': lambda: dev['vel'] - z * sd, 'upper': lambda: dev['vel'] + z * sd,
+            'value': lambda: dev['mean'], 'value_var': lambda: dev['var'], 'cross': lambda: dev['cross'],
+            'speed2': lambda: (dev['vel'] * dev['vel'] + dev['vel_var']).sum(axis=1)}
+    out = {'times': tt}
+    for k in want:
+        out[k] = made[k]()
+    if labels is not None:
+        binSize = float(experiment.binSize)
+        spans = [((sess.T if sess.lengths is None else int(sess.lengths[int(t)])) - 1) * binSize for t in idx]
+        out['condition_mean'], out['condition_count'] = _condition_means_at(dev['vel'], tt, group, len(labels), spans)
+        out['condition_labels'] = labels
+    return out
+
+
 _RATE_AT_KEYS = ('rate', 'lower', 'upper', 'median', 'eta', 'var')
 
 

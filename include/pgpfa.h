@@ -644,6 +644,58 @@ enum {
 int pgpfa_test_thin(pgpfa_ctx* ctx, int kind, int p, int T, int Tf, const int32_t* ranks, int gran, long long ldx, long long ldy, int Tx, int vec_f32,
                     int nslots, int ncols, const int32_t* cols, int live, int stop, double fill, const double* F, const double* Sb, const void* X, void* Y,
                     int32_t* geom /* [3 p + 3] */, int tab_cap, int32_t* tab_ft, int32_t* tab_f, int32_t* tab_s, int32_t* ntab /* [3] */);
+/* pgpfa_test_pivchol: the pivoted Cholesky of (1 - eps) RBF_k, k < p (rbf_pivchol_kernel<256,1>, <512,2>, rbf_pivchol2_kernel<256,4>) for caller
+ * timescales tau[p] (seconds; bin in milliseconds), through the three-way choice of the engine (pivchol_launch): up to 256 bins the first form, beyond
+ * them the third with `pairs` (and an even Tf), else the second.  Slabs of its own, prefilled with `fill`, the band of 1024 doubles behind them and behind
+ * the ranks; the context only lends its stream.  F: [p][Tf][Tf] out, element (t, j) of latent k at k Tf Tf + j Tf + t; rank[p] out; *form out: 0, 1, 2 in
+ * the order above.  Impossible geometry is refused before anything is allocated or launched, with a code of its own. */
+enum {
+  PGPFA_PIVCHOL_BAD_ARG = 120,      /* null pointer, p outside 1..32, Tf above 4096, bin or a timescale not positive */
+  PGPFA_PIVCHOL_REFUSED_T = 121,    /* T < 1 */
+  PGPFA_PIVCHOL_REFUSED_TF = 122,   /* Tf < T */
+  PGPFA_PIVCHOL_REFUSED_ODD = 123,  /* pairs with an odd Tf */
+  PGPFA_PIVCHOL_REFUSED_LDS = 124   /* dynamic LDS above 64 KiB, what a launch may ask for without opting in */
+};
+int pgpfa_test_pivchol(pgpfa_ctx* ctx, int p, int T, int Tf, const double* tau, double bin, double eps, double tol, int pairs, double fill, double* F,
+                       int32_t* rank, int32_t* form);
+/* pgpfa_test_bin_blocks: G_t = (I + eps W_t)^-1, Wt_t = W_t G_t and log det(I + eps W_t) of the listed slots (bin_blocks_reg_kernel up to 10 latents,
+ * bin_blocks_coop_kernel up to 32) on caller data, through the launch code of the engine (bin_blocks_launch); device buffers of its own, the context only
+ * lends its stream.  W: [nslots][sW], bin t of slot s at s sW + t p p, row-major p x p, symmetric positive semi-definite; sW = 0: one shared slot
+ * (nslots must be 1; sO alike).  list: nlist slot numbers.  G, Wt: [nslots][sO] out, uploaded before the launch - what no kernel stores comes back as it
+ * went in -; ldet (may be NULL: not computed): [nlist][T], indexed by LIST POSITION.  A band of 1024 doubles sits behind each; the call fails if one
+ * changed.  W has 128 elements of `fill` behind it.  *per_block out: matrices per workgroup of the form that ran.
+ * Impossible geometry is refused before anything is allocated or launched, with a code of its own. */
+enum {
+  PGPFA_BINB_BAD_ARG = 130,         /* null pointer, sizes below 1 */
+  PGPFA_BINB_REFUSED_P = 131,       /* p above 32 */
+  PGPFA_BINB_REFUSED_LIST = 132,    /* list entry outside the slots, or a slot twice */
+  PGPFA_BINB_REFUSED_STRIDE = 133   /* sW or sO below T p^2 (0 with more than one slot) */
+};
+int pgpfa_test_bin_blocks(pgpfa_ctx* ctx, int p, int T, double eps, int nslots, int nlist, const int32_t* list, long long sW, long long sO, double fill,
+                          const double* W, double* G, double* Wt, double* ldet, int32_t* per_block);
+/* pgpfa_test_assemble_b: B = I + F^T Wt F of the low-rank engine (assemble_b_kernel_t<double | float> and pad_identity_kernel) on caller data, through the
+ * rank tables' builder (rank_layout, b_layout_of) and the launch code of the covariance pass (assemble_rxr_launch); device buffers of its own, the context
+ * only lends its stream.  Geometry by the rule of the rank tables (see pgpfa_test_thin); it comes back in
+ * geom = [rr (p), rk (p), roff (p + 1), roff16 (p + 1), rtot, rtot16, rpad, compact, nblk64, npairs, nact], the tables in blk_lat / blk_col (ntab[0] entries)
+ * and cmap (ntab[1] entries; none with gran 16), at most tab_cap ints each.
+ * F: slabs [p][Tf][Tf], element (t, j) of latent l at l Tf Tf + j Tf + t; columns [ranks[l], rk_l) must hold zeros, rows t >= T any finite value (they are
+ *   read up to round_up(T, 32) - 1 and meet zero weights).  With f32 the slabs are converted by cvt_f32_kernel, as the covariance pass converts them.
+ * Wt: [nslots][sW] doubles, bin t of slot s at s sW + t p p, entry (ka, kb) at ka p + kb, symmetric per bin (the kernel's contract); sW = 0: one shared
+ *   slot (nslots must be 1).  Only the listed slots are read.
+ * list: nlist slot numbers; B: [nslots][rpad][rpad] doubles (floats with f32), entry (row, col) of a slot at col rpad + row, uploaded before the launch -
+ *   what no kernel stores comes back as it went in - with a band of 1024 doubles behind it; the call fails if the band changed.  rpad_expected: the rpad
+ *   the caller sized B for.  F and Wt have 128 elements of `fill` behind them.
+ * Impossible geometry is refused before anything is allocated or launched, with a code of its own (the text is in pgpfa_last_error). */
+enum {
+  PGPFA_ASMB_BAD_ARG = 110,         /* null pointer, sizes below 1, p above 32, unknown granularity, rpad_expected or tab_cap that do not fit */
+  PGPFA_ASMB_REFUSED_TF = 111,      /* Tf below round_up(T, 32) */
+  PGPFA_ASMB_REFUSED_RANK = 112,    /* a rank outside 1..T */
+  PGPFA_ASMB_REFUSED_LIST = 113,    /* list entry outside the slots, or a slot twice */
+  PGPFA_ASMB_REFUSED_STRIDE = 114   /* sW below T p^2 (sW = 0 with more than one slot) */
+};
+int pgpfa_test_assemble_b(pgpfa_ctx* ctx, int p, int T, int Tf, const int32_t* ranks, int gran, int f32, int nslots, int nlist, const int32_t* list,
+                          long long sW, double fill, const double* F, const double* Wt, void* B, int rpad_expected, int32_t* geom /* [4 p + 9] */,
+                          int tab_cap, int32_t* blk_lat, int32_t* blk_col, int32_t* cmap, int32_t* ntab /* [2] */);
 /* Times `reps` launches of the dominant kernel (batched trailing SYRK update, K=512) with HIP
  * events on the context stream; returns average ms per launch and the flops of one launch. */
 int pgpfa_bench_syrk(pgpfa_ctx* ctx, int batch, int n, int k, int reps, double* ms_per_launch,

@@ -721,17 +721,26 @@ int build_kinv(pgpfa_ctx* c) {
 
 // pivoted-Cholesky factors of the RBF part of every Gram matrix and the block tables of the r x r system
 // (the pivoted Cholesky itself - p workgroups, a chain of r_k dependent steps each: 1-2 ms with the chip empty - on stream `st`)
-int launch_pivchol(pgpfa_ctx* c, hipStream_t st) {
-  const int p = c->p, T = c->T, Tp = c->Tp;
-  const int rmax = std::min(T, Tp);
+// (the three-way choice from explicit arguments: launch_pivchol passes the context's, pgpfa_test_pivchol buffers of its own; lds, optional: the
+//  dynamic LDS the form asks for - with run = false nothing is launched, only the form and its LDS are told)
+int pivchol_launch(double* F, int Tf, int T, int p, const double* tau, double bin, double eps, double tol, bool pairs, int* rank, hipStream_t st, size_t* lds,
+                   bool run) {
+  const int rmax = std::min(T, Tf);
   const size_t shm = ((size_t)2 * T + rmax + 16) * sizeof(double) + 16 * sizeof(int);
-  if (T > 256 && c->pivchol_pairs && Tp % 2 == 0)
-    hipLaunchKernelGGL((rbf_pivchol2_kernel<256, 4>), dim3(p), dim3(1024), pivchol2_lds(T, rmax, 1024, 4), st, c->Flr, Tp, T, c->tau, c->bin, c->eps, c->lr_tol, rmax,
-                       c->d_rank);
-  else if (T > 256)
-    hipLaunchKernelGGL((rbf_pivchol_kernel<512, 2>), dim3(p), dim3(1024), shm, st, c->Flr, Tp, T, c->tau, c->bin, c->eps, c->lr_tol, rmax, c->d_rank);
+  const int form = (T > 256 && pairs && Tf % 2 == 0) ? PIVCHOL_PAIRS : T > 256 ? PIVCHOL_512_2 : PIVCHOL_256_1;
+  if (lds) *lds = form == PIVCHOL_PAIRS ? pivchol2_lds(T, rmax, 1024, 4) : shm;
+  if (!run) return form;
+  if (form == PIVCHOL_PAIRS)
+    hipLaunchKernelGGL((rbf_pivchol2_kernel<256, 4>), dim3(p), dim3(1024), pivchol2_lds(T, rmax, 1024, 4), st, F, Tf, T, tau, bin, eps, tol, rmax, rank);
+  else if (form == PIVCHOL_512_2)
+    hipLaunchKernelGGL((rbf_pivchol_kernel<512, 2>), dim3(p), dim3(1024), shm, st, F, Tf, T, tau, bin, eps, tol, rmax, rank);
   else
-    hipLaunchKernelGGL((rbf_pivchol_kernel<256, 1>), dim3(p), dim3(256), shm, st, c->Flr, Tp, T, c->tau, c->bin, c->eps, c->lr_tol, rmax, c->d_rank);
+    hipLaunchKernelGGL((rbf_pivchol_kernel<256, 1>), dim3(p), dim3(256), shm, st, F, Tf, T, tau, bin, eps, tol, rmax, rank);
+  return form;
+}
+
+int launch_pivchol(pgpfa_ctx* c, hipStream_t st) {
+  (void)pivchol_launch(c->Flr, c->Tp, c->T, c->p, c->tau, c->bin, c->eps, c->lr_tol, c->pivchol_pairs != 0, c->d_rank, st);
   HIPC(hipGetLastError());
   return 0;
 }
@@ -758,6 +767,52 @@ ThinTables thin_tables(int p, int T, const int* rr, const int* rk, const int* ro
   return tt;
 }
 
+// The rank tables of the r x r system (ctx.h; build_lowrank describes the rule and stores what this returns).
+RankLayout rank_layout(int p, const int* ranks, int gran, bool thin_all) {
+  RankLayout L;
+  const int G = ((gran == 4 || gran == 8) && thin_all) ? gran : 16;
+  L.rk.assign(p, 0);
+  L.roff.assign(p + 1, 0);
+  L.rr.assign(p, 0);
+  L.roff16.assign(p + 1, 0);
+  int extent = 0;
+  for (int k = 0; k < p; ++k) {
+    L.rr[k] = round_up(std::max(ranks[k], 1), G);
+    L.rk[k] = round_up(L.rr[k], 16);
+    L.roff[k + 1] = L.roff[k] + L.rr[k];
+    L.roff16[k + 1] = L.roff16[k] + L.rk[k];
+    extent = std::max(extent, L.roff[k] + L.rk[k]);
+  }
+  L.rtot = L.roff[p];
+  L.rtot16 = L.roff16[p];
+  L.rank_compact = (G != 16);
+  L.rpad = round_up(std::max(L.rtot, extent), NB);
+  const int nblk = round_up(L.rtot16, NB) / 16;
+  L.blk_lat.assign(nblk, -1);
+  L.blk_col.assign(nblk, 0);
+  for (int k = 0; k < p; ++k)
+    for (int b = L.roff16[k] / 16; b < L.roff16[k + 1] / 16; ++b) { L.blk_lat[b] = k; L.blk_col[b] = b * 16 - L.roff16[k]; }
+  if (L.rank_compact) {
+    // padded index -> compact index (-1: a padding row); nrtab[b]: padded rows that can hold something in the 16-column block b of L^-T (it is upper
+    // triangular in the compact order: rows up to compact index 16 b + 15), rounded up to a whole 16-row group of the latent that holds the last one
+    const int n16 = round_up(L.rtot16, NB);
+    std::vector<int> pmap(round_up(L.rtot, 16) + 16, 0);
+    L.cmap.assign(n16, -1);
+    for (int k = 0; k < p; ++k)
+      for (int j = 0; j < L.rr[k]; ++j) { L.cmap[L.roff16[k] + j] = L.roff[k] + j; pmap[L.roff[k] + j] = L.roff16[k] + j; }
+    L.nrtab.assign((round_up(L.rtot, 16)) / 16, 0);
+    for (size_t b = 0; b < L.nrtab.size(); ++b) {
+      const int last = std::min((int)b * 16 + 15, L.rtot - 1);
+      L.nrtab[b] = std::min(L.rtot16, round_up(pmap[last] + 1, 16));
+    }
+    // The DMA form of yt_mix's panel staging (ytmix.h) moves whole row PAIRS, 16 bytes from a 16-byte aligned address: a pair is padding as a
+    // whole or two consecutive slab rows from an even one (real rows come in multiples of 4 from a multiple of 4).
+    for (int i = 0; i + 1 < n16 && L.bad_pair < 0; i += 2)
+      if (L.cmap[i] < 0 ? L.cmap[i + 1] >= 0 : ((L.cmap[i] & 1) != 0 || L.cmap[i + 1] != L.cmap[i] + 1)) L.bad_pair = i;
+  }
+  return L;
+}
+
 // (pivchol_launched: the kernel is already running on the side stream and c->ev_join marks its end)
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   const int p = c->p, T = c->T, Tp = c->Tp;
@@ -776,50 +831,27 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
   // compact place (cmap), and the panel of L^-T that yt_mix stages keeps padded rows (gathered through the same map).
   // (compact offsets need the preconditioner's three products as thin.h's kernels: the general GEMM's row-tile tables start tiles on multiples of 16)
   const bool thin_all = thin_possible(c) && c->thin_products >= 2;
-  const int G = ((c->rank_gran == 4 || c->rank_gran == 8) && thin_all) ? c->rank_gran : 16;
-  c->rk.assign(p, 0);
-  c->roff.assign(p + 1, 0);
-  c->rr.assign(p, 0);
-  c->roff16.assign(p + 1, 0);
-  int extent = 0;
-  for (int k = 0; k < p; ++k) {
-    c->rr[k] = round_up(std::max(r[k], 1), G);
-    c->rk[k] = round_up(c->rr[k], 16);
-    c->roff[k + 1] = c->roff[k] + c->rr[k];
-    c->roff16[k + 1] = c->roff16[k] + c->rk[k];
-    extent = std::max(extent, c->roff[k] + c->rk[k]);
-  }
-  c->rtot = c->roff[p];
-  c->rtot16 = c->roff16[p];
-  c->rank_compact = (G != 16);
-  c->rpad = round_up(std::max(c->rtot, extent), NB);
-  const int nblk = round_up(c->rtot16, NB) / 16;
-  std::vector<int> lat(nblk, -1), col(nblk, 0);
-  for (int k = 0; k < p; ++k)
-    for (int b = c->roff16[k] / 16; b < c->roff16[k + 1] / 16; ++b) { lat[b] = k; col[b] = b * 16 - c->roff16[k]; }
-  CHK(upload_list(c, c->d_blk_lat, lat));
-  CHK(upload_list(c, c->d_blk_col, col));
+  RankLayout rl = rank_layout(p, r.data(), c->rank_gran, thin_all);
+  c->rk = rl.rk;
+  c->roff = rl.roff;
+  c->rr = rl.rr;
+  c->roff16 = rl.roff16;
+  c->rtot = rl.rtot;
+  c->rtot16 = rl.rtot16;
+  c->rank_compact = rl.rank_compact;
+  c->rpad = rl.rpad;
+  CHK(upload_list(c, c->d_blk_lat, rl.blk_lat));
+  CHK(upload_list(c, c->d_blk_col, rl.blk_col));
   CHK(upload_list(c, c->d_roff, c->roff));
   CHK(upload_list(c, c->d_roff16, c->roff16));
   if (c->rank_compact) {
-    // padded index -> compact index (-1: a padding row); nrtab[b]: padded rows that can hold something in the 16-column block b of L^-T (it is upper
-    // triangular in the compact order: rows up to compact index 16 b + 15), rounded up to a whole 16-row group of the latent that holds the last one
-    const int n16 = round_up(c->rtot16, NB);
-    std::vector<int> cmap(n16, -1), pmap(round_up(c->rtot, 16) + 16, 0);
-    for (int k = 0; k < p; ++k)
-      for (int j = 0; j < c->rr[k]; ++j) { cmap[c->roff16[k] + j] = c->roff[k] + j; pmap[c->roff[k] + j] = c->roff16[k] + j; }
-    std::vector<int> nrtab((round_up(c->rtot, 16)) / 16, 0);
-    for (size_t b = 0; b < nrtab.size(); ++b) {
-      const int last = std::min((int)b * 16 + 15, c->rtot - 1);
-      nrtab[b] = std::min(c->rtot16, round_up(pmap[last] + 1, 16));
+    // A table that breaks the row-pair rule of the panel staging (rank_layout) is an error.
+    if (rl.bad_pair >= 0) {
+      const int i = rl.bad_pair;
+      return fail("rank tables: padded rows %d, %d map to slab rows %d, %d - not a pair the panel staging can move whole", i, i + 1, rl.cmap[i], rl.cmap[i + 1]);
     }
-    // The DMA form of yt_mix's panel staging (ytmix.h) moves whole row PAIRS, 16 bytes from a 16-byte aligned address: a pair is padding as a
-    // whole or two consecutive slab rows from an even one (real rows come in multiples of 4 from a multiple of 4).  A table that breaks this is an error.
-    for (int i = 0; i + 1 < n16; i += 2)
-      if (cmap[i] < 0 ? cmap[i + 1] >= 0 : ((cmap[i] & 1) != 0 || cmap[i + 1] != cmap[i] + 1))
-        return fail("rank tables: padded rows %d, %d map to slab rows %d, %d - not a pair the panel staging can move whole", i, i + 1, cmap[i], cmap[i + 1]);
-    CHK(upload_list(c, c->d_cmap, cmap));
-    CHK(upload_list(c, c->d_nrtab, nrtab));
+    CHK(upload_list(c, c->d_cmap, rl.cmap));
+    CHK(upload_list(c, c->d_nrtab, rl.nrtab));
   }
   {
     // Row-tile tables of the two block-diagonal products of the low-rank preconditioner, 64 rows per tile, one latent per tile:
@@ -865,10 +897,13 @@ int build_lowrank(pgpfa_ctx* c, bool pivchol_launched) {
 }
 
 // what the kernels that know the compact offsets are told of the tables above (ctx.h)
+BLayout b_layout_of(bool compact, int rtot16, int rpad, const int* cmap, const int* roff_padded, const int* nrtab) {
+  const int n64 = round_up(rtot16, 64) / 64, d64 = rpad / 64;
+  return compact ? BLayout{n64, n64 * (n64 + 1) / 2, cmap, roff_padded, nrtab, round_up(rtot16, (int)NB)}
+                 : BLayout{d64, d64 * (d64 + 1) / 2, nullptr, roff_padded, nullptr, 0};
+}
 BLayout b_layout(const pgpfa_ctx* c) {
-  const int n64 = round_up(c->rtot16, 64) / 64, d64 = c->rpad / 64;
-  return c->rank_compact ? BLayout{n64, n64 * (n64 + 1) / 2, c->d_cmap, c->d_roff16, c->d_nrtab, round_up(c->rtot16, (int)NB)}
-                         : BLayout{d64, d64 * (d64 + 1) / 2, nullptr, c->d_roff, nullptr, 0};
+  return b_layout_of(c->rank_compact, c->rtot16, c->rpad, c->d_cmap, c->rank_compact ? c->d_roff16 : c->d_roff, c->d_nrtab);
 }
 
 // ---- test hook: the three thin products of the low-rank preconditioner on caller data, through thin_tables and the launches of shared_solve ---------
@@ -1037,6 +1072,68 @@ int pgpfa_test_thin(pgpfa_ctx* c, int kind, int p, int T, int Tf, const int32_t*
     CHK(hook_collect("pgpfa_test_thin (Sb u)", dV, nullptr, mid));
   }
   return hook_collect_bytes("pgpfa_test_thin", dY, Y, ybytes);
+}
+
+// ---- test hook: the pivoted Cholesky of the RBF part on caller timescales, through pivchol_launch ----------------------------------------------------
+// The kernels read nothing but tau[p] and their own slab; they write all Tf x Tf entries of each slab (zeros first), column j < min(T, Tf) rows t < T -
+// the pair form with 16-byte loads and stores of rows (t, t + 1), t even, t + 1 <= round_up(T, 2) - 1 < Tf for an even Tf >= T - and rank[p].
+// Dynamic LDS: what pivchol_launch asks for, refused above the 64 KiB a launch may ask for without opting in (production does not opt in).
+namespace {
+int pivchol_refuse(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  (void)fail("pgpfa_test_pivchol refuses: %s", buf);
+  return code;
+}
+}  // namespace
+
+int pgpfa_test_pivchol(pgpfa_ctx* c, int p, int T, int Tf, const double* tau, double bin, double eps, double tol, int pairs, double fill, double* F,
+                       int32_t* rank, int32_t* form) {
+  using namespace hook;
+  if (!c || !tau || !F || !rank || !form) return pivchol_refuse(PGPFA_PIVCHOL_BAD_ARG, "null argument");
+  if (p < 1 || p > 32 || Tf > 4096 || !(bin > 0.0)) return pivchol_refuse(PGPFA_PIVCHOL_BAD_ARG, "invalid sizes");
+  for (int k = 0; k < p; ++k)
+    if (!(tau[k] > 0.0)) return pivchol_refuse(PGPFA_PIVCHOL_BAD_ARG, "timescale %d is not positive", k);
+  if (T < 1) return pivchol_refuse(PGPFA_PIVCHOL_REFUSED_T, "T = %d below 1", T);
+  if (Tf < T) return pivchol_refuse(PGPFA_PIVCHOL_REFUSED_TF, "slab size Tf = %d below T = %d", Tf, T);
+  if (pairs && Tf % 2 != 0) return pivchol_refuse(PGPFA_PIVCHOL_REFUSED_ODD, "slab size Tf = %d is odd (the pair form moves aligned row pairs)", Tf);
+  size_t lds = 0;
+  const int f = pivchol_launch(nullptr, Tf, T, p, nullptr, bin, eps, tol, pairs != 0, nullptr, c->st, &lds, false);
+  if (lds > (size_t)64 * 1024) return pivchol_refuse(PGPFA_PIVCHOL_REFUSED_LDS, "%zu bytes of dynamic LDS, above the 65536 a launch may ask for", lds);
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  double *dF = nullptr, *dtau = nullptr, *drank = nullptr;
+  const size_t nf = (size_t)p * Tf * Tf;
+  CHK(hb.get(&dtau, (size_t)p, 0));
+  HIPC(hipMemcpy(dtau, tau, p * sizeof(double), hipMemcpyHostToDevice));
+  {
+    const std::vector<double> h(nf, fill);
+    CHK(hook_output(hb, &dF, h.data(), nf));
+  }
+  // (the ranks: p ints in a buffer of doubles of their own, prefilled with -1, the band behind them)
+  const size_t rd = ((size_t)p + 1) / 2;
+  {
+    std::vector<double> h(rd);
+    std::vector<int32_t> m(2 * rd, -1);
+    std::memcpy(h.data(), m.data(), rd * sizeof(double));
+    CHK(hook_output(hb, &drank, h.data(), rd));
+  }
+  HIPC(hipDeviceSynchronize());
+  const int ran = pivchol_launch(dF, Tf, T, p, dtau, bin, eps, tol, pairs != 0, reinterpret_cast<int*>(drank), c->st);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  if (ran != f) return fail("internal: the pivoted Cholesky took form %d, not %d", ran, f);
+  *form = ran;
+  {
+    std::vector<double> h(rd);
+    CHK(hook_collect("pgpfa_test_pivchol (ranks)", drank, h.data(), rd));
+    std::memcpy(rank, h.data(), p * sizeof(int32_t));
+  }
+  return hook_collect("pgpfa_test_pivchol", dF, F, nf);
 }
 
 

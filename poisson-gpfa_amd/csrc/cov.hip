@@ -232,15 +232,21 @@ static int split_latent_sums(pgpfa_ctx* c, const double* A0, long long sM, int l
 }
 
 // B = I + F^T Wt F (ctx.h).  The shared preconditioner's one slot gives the grid (npairs, (1 + AB_SLOTS - 1) / AB_SLOTS) = (npairs, 1) it has always had.
+// The two launches from explicit arguments (assemble_rxr passes the context's, pgpfa_test_assemble_b buffers and tables of its own): Bm with slot
+// stride sB and leading dimension rpad, L and blk_lat / blk_col from the rank tables, F the slabs [p][Tf][Tf].
+template <typename TB>
+void assemble_rxr_launch(TB* Bm, long long sB, int rpad, int rtot, int nact, const BLayout& L, const TB* F, int Tf, int T, int p, const int* blk_lat,
+                         const int* blk_col, const double* Wt, long long sW, const int* slots, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(assemble_b_kernel_t<TB>, dim3(L.npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, st, Bm, sB, rpad, L.nblk64, F, Tf, T, p,
+                     blk_lat, blk_col, Wt, sW, slots, nb, L.cmap);
+  if (L.cmap && rpad > rtot)
+    hipLaunchKernelGGL(pad_identity_kernel<TB>, dim3((rpad + 3) / 4, nb), dim3(256), 0, st, Bm, sB, rpad, rtot, rpad, nact, (int)NB, slots);
+}
+
 template <typename TB>
 int assemble_rxr(pgpfa_ctx* c, const CholWS& view, int nb, const TB* F, const double* Wt, long long sW, const int* slots) {
-  const int rpad = c->rpad;
-  const BLayout L = b_layout(c);
   TB* Bm = reinterpret_cast<TB*>(view.H);                  // (a single-precision view carries its strides in floats)
-  hipLaunchKernelGGL(assemble_b_kernel_t<TB>, dim3(L.npairs, (nb + AB_SLOTS - 1) / AB_SLOTS), dim3(256), 0, c->st, Bm, view.sH, rpad, L.nblk64, F, c->Tp, c->T, c->p,
-                     c->d_blk_lat, c->d_blk_col, Wt, sW, slots, nb, L.cmap);
-  if (L.cmap && rpad > c->rtot)
-    hipLaunchKernelGGL(pad_identity_kernel<TB>, dim3((rpad + 3) / 4, nb), dim3(256), 0, c->st, Bm, view.sH, rpad, c->rtot, rpad, view.nact, (int)NB, slots);
+  assemble_rxr_launch<TB>(Bm, view.sH, c->rpad, c->rtot, view.nact, b_layout(c), F, c->Tp, c->T, c->p, c->d_blk_lat, c->d_blk_col, Wt, sW, slots, nb, c->st);
   HIPC(hipGetLastError());
   return 0;
 }
@@ -1062,4 +1068,111 @@ int pgpfa_test_split_latent_sums(pgpfa_ctx* c, int nslots, int rk, int kw, int T
   if ((cross_kernel != 0) != (cross_used != 0)) return fail("internal: the cross term did not take the requested form");
   CHK(hook_collect("pgpfa_test_split_latent_sums (S)", dS, Ssum, (size_t)rk * rk));
   return hook_collect("pgpfa_test_split_latent_sums (X)", dX, Xsum, (size_t)rk * T);
+}
+
+// ---- test hook: B = I + F^T Wt F on caller data, through rank_layout, b_layout_of and assemble_rxr_launch ------------------------------------------
+// What the kernels read past their logical inputs (assemble_b_kernel_t walks the bins in chunks of 32, a thread per bin of the chunk):
+//  * F: rows up to round_up(T, 32) - 1 of every column [0, rk_l) of a latent's slab - unguarded loads, met by weights that the guard `bin < T` made
+//    zero.  With Tf >= round_up(T, 32) (refused otherwise) and rk_l <= round_up(T, 16) <= Tf (a rank above T is refused) they stay inside the slab;
+//    the slabs still get 128 elements of `fill` behind them.  Rows [T, Tf) of a column hold what the caller put there: any FINITE value.
+//  * Wt: bins < T of the listed slots only (guarded), block (la, lb) of the p x p matrix of a bin; nothing behind it.  128 elements of `fill` behind it.
+//  * the tables: blk_lat / blk_col entries [0, 4 nblk64), cmap entries [0, 64 nblk64) - both at most round_up(rtot16, 128), their lengths.
+// What they write: assemble_b_kernel_t entries (row >= col) < rtot of the compact space (without cmap: < rpad), pad_identity_kernel rows [rtot, rpad).
+namespace {
+int asmb_refuse(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  (void)fail("pgpfa_test_assemble_b refuses: %s", buf);
+  return code;
+}
+}  // namespace
+
+int pgpfa_test_assemble_b(pgpfa_ctx* c, int p, int T, int Tf, const int32_t* ranks, int gran, int f32, int nslots, int nlist, const int32_t* list, long long sW,
+                          double fill, const double* F, const double* Wt, void* B, int rpad_expected, int32_t* geom, int tab_cap, int32_t* blk_lat,
+                          int32_t* blk_col, int32_t* cmap, int32_t* ntab) {
+  if (!c || !ranks || !list || !F || !Wt || !B || !geom || !blk_lat || !blk_col || !cmap || !ntab) return asmb_refuse(PGPFA_ASMB_BAD_ARG, "null argument");
+  if (p < 1 || p > 32 || T < 1 || nslots < 1 || nlist < 1 || tab_cap < 1) return asmb_refuse(PGPFA_ASMB_BAD_ARG, "invalid sizes");
+  if (gran != 4 && gran != 8 && gran != 16) return asmb_refuse(PGPFA_ASMB_BAD_ARG, "rank granularity %d (4, 8 or 16)", gran);
+  if (Tf < round_up(T, AB_TK) || Tf > 4096)
+    return asmb_refuse(PGPFA_ASMB_REFUSED_TF, "slab size Tf = %d below round_up(T, %d) = %d (the bins are read in whole chunks), or above 4096", Tf, AB_TK, round_up(T, AB_TK));
+  for (int k = 0; k < p; ++k)
+    if (ranks[k] < 1 || ranks[k] > T) return asmb_refuse(PGPFA_ASMB_REFUSED_RANK, "rank %d of latent %d outside 1..T = %d", ranks[k], k, T);
+  {
+    std::vector<char> seen(nslots, 0);
+    for (int i = 0; i < nlist; ++i) {
+      if (list[i] < 0 || list[i] >= nslots) return asmb_refuse(PGPFA_ASMB_REFUSED_LIST, "slot list entry %d = %d outside the %d slots", i, list[i], nslots);
+      if (seen[list[i]]) return asmb_refuse(PGPFA_ASMB_REFUSED_LIST, "slot list names slot %d twice", list[i]);
+      seen[list[i]] = 1;
+    }
+  }
+  const long long wbin = (long long)T * p * p;
+  if (sW == 0 ? nslots != 1 : sW < wbin)
+    return asmb_refuse(PGPFA_ASMB_REFUSED_STRIDE, "weight stride sW = %lld below T p^2 = %lld (0: one shared slot, with nslots = 1)", sW, wbin);
+  std::vector<int> r(ranks, ranks + p);
+  const RankLayout rl = rank_layout(p, r.data(), gran, true);
+  if (rl.bad_pair >= 0) return fail("rank tables: padded rows %d, %d are no pair the panel staging can move whole", rl.bad_pair, rl.bad_pair + 1);
+  if (rl.rpad != rpad_expected) return asmb_refuse(PGPFA_ASMB_BAD_ARG, "the output was sized for rpad = %d, the rank tables give %d", rpad_expected, rl.rpad);
+  if ((int)rl.blk_lat.size() > tab_cap || (int)rl.cmap.size() > tab_cap) return asmb_refuse(PGPFA_ASMB_BAD_ARG, "tables exceed tab_cap = %d", tab_cap);
+  const int rpad = rl.rpad, nact = round_up(rl.rtot, 64);        // (nact: lowrank_view)
+  // (the tiles walked must lie inside the tables and the output)
+  const int n64 = rl.rank_compact ? round_up(rl.rtot16, 64) / 64 : rpad / 64;
+  if (4 * n64 > (int)rl.blk_lat.size() || (rl.rank_compact && 64 * n64 > (int)rl.cmap.size()) || (!rl.rank_compact && 64 * n64 > rpad))
+    return fail("internal: the rank tables are shorter than the tiles the assembly walks");
+
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  constexpr size_t SLACK = 128;
+  auto input = [&](double** dev, const double* host, size_t count) -> int {
+    CHK(hb.get(dev, count + SLACK, 0));
+    const std::vector<double> h(SLACK, fill);
+    HIPC(hipMemcpy(*dev, host, count * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(*dev + count, h.data(), SLACK * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto ints = [&](int** dev, const std::vector<int>& v) -> int {
+    CHK(hb.get(dev, std::max<size_t>(v.size(), 1), 0));
+    if (!v.empty()) HIPC(hipMemcpy(*dev, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+  };
+  double *dF = nullptr, *dWt = nullptr;
+  float* dF32 = nullptr;
+  int *d_lat = nullptr, *d_col = nullptr, *d_cmap = nullptr, *d_roff = nullptr, *d_nrtab = nullptr, *d_list = nullptr;
+  const size_t nf = (size_t)p * Tf * Tf;
+  CHK(input(&dF, F, nf));
+  CHK(input(&dWt, Wt, sW == 0 ? (size_t)wbin : (size_t)nslots * sW));
+  CHK(ints(&d_lat, rl.blk_lat));
+  CHK(ints(&d_col, rl.blk_col));
+  CHK(ints(&d_roff, rl.rank_compact ? rl.roff16 : rl.roff));
+  if (rl.rank_compact) { CHK(ints(&d_cmap, rl.cmap)); CHK(ints(&d_nrtab, rl.nrtab)); }
+  CHK(ints(&d_list, std::vector<int>(list, list + nlist)));
+  if (f32) {
+    // the single-precision copy of the slabs, as ensure_f32_factors makes it (the slack too)
+    CHK(hb.get(&dF32, nf + SLACK, 0));
+    HIPC(hipDeviceSynchronize());
+    hipLaunchKernelGGL(cvt_f32_kernel, dim3((unsigned)((nf + SLACK + 255) / 256)), dim3(256), 0, c->st, dF, dF32, nf + SLACK);
+    HIPC(hipGetLastError());
+  }
+  void* dB = nullptr;
+  const size_t bbytes = (size_t)nslots * rpad * rpad * (f32 ? sizeof(float) : sizeof(double));
+  CHK(hook_output_bytes(hb, &dB, B, bbytes));
+  HIPC(hipDeviceSynchronize());
+  const BLayout L = b_layout_of(rl.rank_compact, rl.rtot16, rpad, d_cmap, d_roff, d_nrtab);
+  const long long sB = (long long)rpad * rpad;
+  if (f32) assemble_rxr_launch<float>(static_cast<float*>(dB), sB, rpad, rl.rtot, nact, L, dF32, Tf, T, p, d_lat, d_col, dWt, sW, d_list, nlist, c->st);
+  else assemble_rxr_launch<double>(static_cast<double*>(dB), sB, rpad, rl.rtot, nact, L, dF, Tf, T, p, d_lat, d_col, dWt, sW, d_list, nlist, c->st);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  for (int k = 0; k < p; ++k) { geom[k] = rl.rr[k]; geom[p + k] = rl.rk[k]; }
+  for (int k = 0; k <= p; ++k) { geom[2 * p + k] = rl.roff[k]; geom[3 * p + 1 + k] = rl.roff16[k]; }
+  int32_t* g = geom + 4 * p + 2;
+  g[0] = rl.rtot; g[1] = rl.rtot16; g[2] = rpad; g[3] = rl.rank_compact ? 1 : 0; g[4] = L.nblk64; g[5] = L.npairs; g[6] = nact;
+  std::copy(rl.blk_lat.begin(), rl.blk_lat.end(), blk_lat);
+  std::copy(rl.blk_col.begin(), rl.blk_col.end(), blk_col);
+  std::copy(rl.cmap.begin(), rl.cmap.end(), cmap);
+  ntab[0] = (int)rl.blk_lat.size(); ntab[1] = (int)rl.cmap.size();
+  return hook_collect_bytes("pgpfa_test_assemble_b", dB, B, bbytes);
 }

@@ -351,6 +351,21 @@ struct BLayout {
   int ncmap_rows;                                // entries of cmap (0 without)
 };
 BLayout b_layout(const pgpfa_ctx* c);            // core.hip
+// the same from the numbers and the device tables alone (b_layout passes the context's; pgpfa_test_assemble_b its own); roff_padded: roff16 under
+// compact offsets, roff otherwise
+BLayout b_layout_of(bool compact, int rtot16, int rpad, const int* cmap, const int* roff_padded, const int* nrtab);
+// Rank tables of the r x r system from the ranks the pivoted Cholesky returned (core.hip; the rule is described in build_lowrank, which stores and
+// uploads what this returns): gran 4 / 8 give compact offsets where every product of the preconditioner runs as a thin.h kernel (thin_all), 16 otherwise.
+// bad_pair >= 0: padded rows bad_pair, bad_pair + 1 are no pair the panel staging of yt_mix can move whole (build_lowrank fails).
+struct RankLayout {
+  std::vector<int> rr, rk, roff, roff16;         // ranks rounded to the granularity / to 16; offsets, compact and padded to 16 (p + 1 entries)
+  int rtot = 0, rtot16 = 0, rpad = 0;
+  bool rank_compact = false;
+  std::vector<int> blk_lat, blk_col;             // per 16-block of the padded space: latent (-1: behind the last) and first column inside its slab
+  std::vector<int> cmap, nrtab;                  // compact offsets only: padded index -> compact index (-1: padding); padded rows per 16-column block of L^-T
+  int bad_pair = -1;
+};
+RankLayout rank_layout(int p, const int* ranks, int gran, bool thin_all);
 // the factor slabs `ws` as the r x r system sees them
 inline CholWS lowrank_view(const pgpfa_ctx* c, const CholWS& ws) {
   CholWS lw = ws;
@@ -518,6 +533,11 @@ int upload(pgpfa_ctx* c, double* dev, const double* host, size_t n);
 int upload_nosync(pgpfa_ctx* c, void* dev, const void* host, size_t bytes);
 int build_kinv(pgpfa_ctx* c);
 int launch_pivchol(pgpfa_ctx* c, hipStream_t st);
+// The pivoted Cholesky of p latents into the slabs F [p][Tf x Tf] on `st`; returns the form that ran: one bin per row thread up to 256 bins, beyond
+// them two column groups over 512 row threads, or - pairs, Tf even - two bins per row thread and four column groups (core.hip)
+enum { PIVCHOL_256_1 = 0, PIVCHOL_512_2 = 1, PIVCHOL_PAIRS = 2 };
+int pivchol_launch(double* F, int Tf, int T, int p, const double* tau, double bin, double eps, double tol, bool pairs, int* rank, hipStream_t st,
+                   size_t* lds = nullptr, bool run = true);
 int build_lowrank(pgpfa_ctx* c, bool pivchol_launched = false);
 // work tables of thin.h's kernels, four ints per entry: ft (latent, first rank row, rank rows, rank offset), f (latent, first bin, rk, rank offset),
 // s (0, first row, rows, 0) - a function of the rank tables alone (build_lowrank uploads them; pgpfa_test_thin returns them)
@@ -547,6 +567,9 @@ int prior_mv_all(pgpfa_ctx* c, int nb, const double* in, double* out, const doub
                  const int* cols = nullptr, int ncols = 0);
 int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale = 1.0);
 int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* Wt, long long sO, int nslots, double* ldet);
+// (the launch itself: the kernel by latent width - registers up to 10, 32 lanes per matrix up to 32 - for the nslots entries of `slots`)
+void bin_blocks_launch(const double* W, long long sW, double* G, double* Wt, long long sO, int T, int p, double eps, const int* slots, int nslots, double* ldet,
+                       hipStream_t st);
 // the launches of the preconditioner's three thin products (thin.h), shared by shared_solve and pgpfa_test_thin
 void thin_launch_ft(const pgpfa::ThinP& tp, int ntab, int ncols, bool vec_f32, hipStream_t st);
 void thin_launch_s(const pgpfa::ThinP& ts, int ntab, int ncols, hipStream_t st);

@@ -5,6 +5,7 @@
 #include "pcg.h"
 #include "thin.h"
 #include "dual.h"
+#include "hook.h"
 
 using namespace pgpfa;
 
@@ -299,17 +300,25 @@ static int shared_solve(pgpfa_ctx* c, int nb, const double* R, double* Z, const 
   return gemm(c, true, g);
 }
 
+// waves (pairs of matrices) per workgroup of bin_blocks_coop_kernel: as many as 64 KB of LDS hold, four at most
+static int bin_blocks_coop_waves(int p) {
+  const size_t per = bin_blocks_coop_doubles(p) * sizeof(double);
+  return (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / (2 * per)));
+}
+
 // per (slot, bin) blocks G = (I + eps W)^-1, Wt = W G [, log det]: register kernel up to 10 latents, LDS kernel beyond
-int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* Wt, long long sO, int nslots, double* ldet) {
-  const int T = c->T, p = c->p, pp = p * p;
+// (from explicit arguments: bin_blocks passes the context's and its identity list, pgpfa_test_bin_blocks buffers and a list of its own)
+void bin_blocks_launch(const double* W, long long sW, double* G, double* Wt, long long sO, int T, int p, double eps, const int* slots, int nslots, double* ldet,
+                       hipStream_t st) {
+  const int pp = p * p;
   const long long items = (long long)nslots * T;
   bool done = false;
   if (p <= 10) {
     dispatch_pw(p, [&](auto pw) {
       constexpr int PW = decltype(pw)::value;
       if constexpr (PW <= 10) {
-        hipLaunchKernelGGL(bin_blocks_reg_kernel<PW>, dim3((unsigned)((items + BBR_MPB - 1) / BBR_MPB)), dim3(BBR_TPB), 0, c->st, W, sW, G, Wt, sO, T, p, c->eps,
-                           c->ident, nslots, ldet);
+        hipLaunchKernelGGL(bin_blocks_reg_kernel<PW>, dim3((unsigned)((items + BBR_MPB - 1) / BBR_MPB)), dim3(BBR_TPB), 0, st, W, sW, G, Wt, sO, T, p, eps,
+                           slots, nslots, ldet);
         done = true;
       }
     });
@@ -317,22 +326,26 @@ int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* W
   if (!done && p <= 32) {
     // 32 lanes per matrix; as many pairs of matrices (waves) per block as 64 KB of LDS hold, four at most
     const size_t per = bin_blocks_coop_doubles(p) * sizeof(double);
-    const int nw = (int)std::max<size_t>(1, std::min<size_t>(4, (64 * 1024) / (2 * per)));
+    const int nw = bin_blocks_coop_waves(p);
     const int per_block = 2 * nw;
     dispatch_pmax(p, [&](auto pm) {
       constexpr int PM = decltype(pm)::value;
       if constexpr (PM >= 16)
-        hipLaunchKernelGGL(bin_blocks_coop_kernel<PM>, dim3((unsigned)((items + per_block - 1) / per_block)), dim3(64 * nw), per_block * per, c->st, W,
-                           sW, G, Wt, sO, T, p, c->eps, c->ident, nslots, ldet);
+        hipLaunchKernelGGL(bin_blocks_coop_kernel<PM>, dim3((unsigned)((items + per_block - 1) / per_block)), dim3(64 * nw), per_block * per, st, W,
+                           sW, G, Wt, sO, T, p, eps, slots, nslots, ldet);
     });
     done = true;
   }
   if (!done) {
     int th = (int)(48 * 1024 / ((2 * pp + 1) * sizeof(double)));
     th = std::max(1, std::min(64, th));
-    hipLaunchKernelGGL(bin_blocks_kernel, dim3((unsigned)((items + th - 1) / th)), dim3(th), (size_t)th * (2 * pp + 1) * sizeof(double), c->st, W, sW, G,
-                       Wt, sO, T, p, c->eps, c->ident, nslots, ldet);
+    hipLaunchKernelGGL(bin_blocks_kernel, dim3((unsigned)((items + th - 1) / th)), dim3(th), (size_t)th * (2 * pp + 1) * sizeof(double), st, W, sW, G,
+                       Wt, sO, T, p, eps, slots, nslots, ldet);
   }
+}
+
+int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* Wt, long long sO, int nslots, double* ldet) {
+  bin_blocks_launch(W, sW, G, Wt, sO, c->T, c->p, c->eps, c->ident, nslots, ldet, c->st);
   HIPC(hipGetLastError());
   return 0;
 }
@@ -1582,3 +1595,65 @@ int pgpfa_loo_predict(pgpfa_ctx* c, int n, const int32_t* idx, double* y_pred, d
 }
 
 
+// ---- test hook: the per-bin blocks G = (I + eps W)^-1, Wt = W G, log det(I + eps W) on caller data, through bin_blocks_launch ---------------------------
+// What the kernels read: W, p^2 doubles at slot sW + t p^2 for the listed slots and bins t < T - the register form copies exactly these runs, the
+// cooperative form reads the run of item 0 (the first list entry, bin 0) once more in every lane of a partly filled last workgroup - and the list.
+// Nothing past the logical inputs; W still gets 128 elements of `fill` behind it.  What they write: the same runs of G and Wt at slot sO + t p^2, and
+// ldet[list position T + t].
+namespace {
+int binb_refuse(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  (void)fail("pgpfa_test_bin_blocks refuses: %s", buf);
+  return code;
+}
+}  // namespace
+
+int pgpfa_test_bin_blocks(pgpfa_ctx* c, int p, int T, double eps, int nslots, int nlist, const int32_t* list, long long sW, long long sO, double fill,
+                          const double* W, double* G, double* Wt, double* ldet, int32_t* per_block) {
+  using namespace hook;
+  if (!c || !list || !W || !G || !Wt || !per_block) return binb_refuse(PGPFA_BINB_BAD_ARG, "null argument");
+  if (p < 1 || T < 1 || nslots < 1 || nlist < 1 || T > (1 << 20) || nslots > (1 << 20)) return binb_refuse(PGPFA_BINB_BAD_ARG, "invalid sizes");
+  if (p > 32) return binb_refuse(PGPFA_BINB_REFUSED_P, "p = %d above 32 (the widest form the engine launches)", p);
+  {
+    std::vector<char> seen(nslots, 0);
+    for (int i = 0; i < nlist; ++i) {
+      if (list[i] < 0 || list[i] >= nslots) return binb_refuse(PGPFA_BINB_REFUSED_LIST, "slot list entry %d = %d outside the %d slots", i, list[i], nslots);
+      if (seen[list[i]]) return binb_refuse(PGPFA_BINB_REFUSED_LIST, "slot list names slot %d twice", list[i]);
+      seen[list[i]] = 1;
+    }
+  }
+  const long long run = (long long)T * p * p;
+  if ((sW == 0 ? nslots != 1 : sW < run) || (sO == 0 ? nslots != 1 : sO < run))
+    return binb_refuse(PGPFA_BINB_REFUSED_STRIDE, "strides sW = %lld, sO = %lld below T p^2 = %lld (0: one shared slot, with nslots = 1)", sW, sO, run);
+  *per_block = p <= 10 ? BBR_MPB : 2 * bin_blocks_coop_waves(p);
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipStreamSynchronize(c->st));
+  HookBuffers hb;
+  constexpr size_t SLACK = 128;
+  double *dW = nullptr, *dG = nullptr, *dWt = nullptr, *dl = nullptr;
+  int* d_list = nullptr;
+  const size_t nw = sW == 0 ? (size_t)run : (size_t)nslots * sW, no = sO == 0 ? (size_t)run : (size_t)nslots * sO;
+  CHK(hb.get(&dW, nw + SLACK, 0));
+  {
+    const std::vector<double> h(SLACK, fill);
+    HIPC(hipMemcpy(dW, W, nw * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(dW + nw, h.data(), SLACK * sizeof(double), hipMemcpyHostToDevice));
+  }
+  CHK(hb.get(&d_list, (size_t)nlist, 0));
+  HIPC(hipMemcpy(d_list, list, nlist * sizeof(int), hipMemcpyHostToDevice));
+  CHK(hook_output(hb, &dG, G, no));
+  CHK(hook_output(hb, &dWt, Wt, no));
+  if (ldet) CHK(hook_output(hb, &dl, ldet, (size_t)nlist * T));
+  HIPC(hipDeviceSynchronize());
+  bin_blocks_launch(dW, sW, dG, dWt, sO, T, p, eps, d_list, nlist, dl, c->st);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c->st));
+  CHK(hook_collect("pgpfa_test_bin_blocks (G)", dG, G, no));
+  CHK(hook_collect("pgpfa_test_bin_blocks (Wt)", dWt, Wt, no));
+  if (ldet) CHK(hook_collect("pgpfa_test_bin_blocks (ldet)", dl, ldet, (size_t)nlist * T));
+  return 0;
+}

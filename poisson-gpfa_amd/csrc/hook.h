@@ -1,4 +1,5 @@
-// hook.h - device buffers of the test hooks (pgpfa_test_split_*: cov.hip, pgpfa_test_thin: core.hip): allocations of one call, output buffers that
+// hook.h - device buffers of the test hooks (pgpfa_test_split_*, pgpfa_test_assemble_b: cov.hip; pgpfa_test_thin, pgpfa_test_pivchol: core.hip;
+// pgpfa_test_bin_blocks: estep.hip): allocations of one call, output buffers that
 // hold the caller's prefill in front of a band no kernel may touch.
 #pragma once
 #include "ctx.h"

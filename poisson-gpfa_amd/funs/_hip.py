@@ -93,6 +93,12 @@ _SIGNATURES = {
     'pgpfa_test_thin': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_int32_p, ct.c_int, ct.c_longlong, ct.c_longlong, ct.c_int, ct.c_int, ct.c_int,
                         ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_double, c_double_p, c_double_p, ct.c_void_p, ct.c_void_p, c_int32_p, ct.c_int,
                         c_int32_p, c_int32_p, c_int32_p, c_int32_p],
+    'pgpfa_test_pivchol': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, c_double_p, ct.c_double, ct.c_double, ct.c_double, ct.c_int, ct.c_double, c_double_p,
+                           c_int32_p, c_int32_p],
+    'pgpfa_test_bin_blocks': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_int, ct.c_int, c_int32_p, ct.c_longlong, ct.c_longlong, ct.c_double, c_double_p,
+                              c_double_p, c_double_p, c_double_p, c_int32_p],
+    'pgpfa_test_assemble_b': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, c_int32_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_int32_p, ct.c_longlong, ct.c_double,
+                              c_double_p, c_double_p, ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_int32_p, c_int32_p, c_int32_p, c_int32_p],
     'pgpfa_bench_syrk': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, c_double_p, c_double_p],
     'pgpfa_bench_potrf_diag': [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, c_double_p],
     'pgpfa_gemm_shape_report': [ct.c_void_p, ct.c_char_p, ct.c_int],
@@ -805,6 +811,91 @@ class Context:
             raise err
         info = dict(rr=geom[:p].copy(), rk=geom[p:2 * p].copy(), roff=geom[2 * p:3 * p + 1].copy(), rtot=int(geom[3 * p + 1]), rpad=int(geom[3 * p + 2]),
                     ft=tabs[0][:4 * ntab[0]].reshape(-1, 4).copy(), f=tabs[1][:4 * ntab[1]].reshape(-1, 4).copy(), s=tabs[2][:4 * ntab[2]].reshape(-1, 4).copy())
+        return out, info
+
+    PIVCHOL_REFUSALS = {120: 'bad_arg', 121: 'T', 122: 'Tf', 123: 'odd', 124: 'lds'}      # PGPFA_PIVCHOL_* of pgpfa.h
+    PIVCHOL_FORMS = ('256_1', '512_2', 'pairs')
+
+    def test_pivchol(self, T, Tf, tau, bin_ms, eps, tol, pairs=True, fill=0.0):
+        """The pivoted Cholesky of (1 - eps) RBF for the timescales tau (seconds) on slabs prefilled with `fill` (pgpfa_test_pivchol).
+        Returns (F (p, Tf, Tf) indexed [latent, column, bin], ranks (p,), form - one of PIVCHOL_FORMS).
+        A refused geometry raises HipBackendError with .rc and .refusal (its name in PIVCHOL_REFUSALS)."""
+        tau = as_f64(np.atleast_1d(tau))
+        p = len(tau)
+        ok = 0 < int(Tf) <= 4096
+        F = np.empty((p, int(Tf), int(Tf)) if ok else (1,))
+        rank = np.zeros(p, dtype=np.int32)
+        form = np.zeros(1, dtype=np.int32)
+        rc = self.lib.pgpfa_test_pivchol(self.h, p, int(T), int(Tf), dptr(tau), float(bin_ms), float(eps), float(tol), int(bool(pairs)), float(fill), dptr(F),
+                                         iptr(rank), iptr(form))
+        if rc != 0:
+            err = HipBackendError(self.lib.pgpfa_last_error().decode('utf-8', 'replace'))
+            err.rc = rc
+            err.refusal = self.PIVCHOL_REFUSALS.get(rc)
+            raise err
+        return F, rank, self.PIVCHOL_FORMS[int(form[0])]
+
+    BINB_REFUSALS = {130: 'bad_arg', 131: 'p', 132: 'list', 133: 'stride'}      # PGPFA_BINB_* of pgpfa.h
+
+    def test_bin_blocks(self, p, T, eps, W, G, Wt, slots=None, sW=None, sO=None, want_ldet=True, ldet_fill=0.0, fill=0.0):
+        """The per-bin blocks G = (I + eps W)^-1, Wt = W G, log det(I + eps W) (pgpfa_test_bin_blocks) on caller data.  W (nslots, sW) float64, bin t of a
+        slot at t p p (row-major p x p); G, Wt (nslots, sO): the output buffers with the caller's prefill; slots: the slot list (None: all, in order).
+        sW / sO default to the row lengths; 0: one shared slot.  Returns (G, Wt, ldet (len(slots), T) or None - prefilled with ldet_fill -, per_block).
+        A refused geometry raises HipBackendError with .rc and .refusal (its name in BINB_REFUSALS)."""
+        W = as_f64(np.atleast_2d(W))
+        Go = np.array(np.atleast_2d(G), dtype=np.float64, order='C', copy=True)
+        Wo = np.array(np.atleast_2d(Wt), dtype=np.float64, order='C', copy=True)
+        nslots = Go.shape[0]
+        assert W.shape[0] == nslots and Wo.shape == Go.shape
+        sl = np.ascontiguousarray(np.arange(nslots) if slots is None else slots, dtype=np.int32)
+        ld = np.full((len(sl), max(int(T), 1)), float(ldet_fill)) if want_ldet else None
+        per_block = np.zeros(1, dtype=np.int32)
+        rc = self.lib.pgpfa_test_bin_blocks(self.h, int(p), int(T), float(eps), nslots, len(sl), iptr(sl), int(W.shape[1] if sW is None else sW),
+                                            int(Go.shape[1] if sO is None else sO), float(fill), dptr(W), dptr(Go), dptr(Wo), dptr(ld) if want_ldet else None,
+                                            iptr(per_block))
+        if rc != 0:
+            err = HipBackendError(self.lib.pgpfa_last_error().decode('utf-8', 'replace'))
+            err.rc = rc
+            err.refusal = self.BINB_REFUSALS.get(rc)
+            raise err
+        return Go, Wo, ld, int(per_block[0])
+
+    ASMB_REFUSALS = {110: 'bad_arg', 111: 'Tf', 112: 'rank', 113: 'list', 114: 'stride'}      # PGPFA_ASMB_* of pgpfa.h
+
+    def test_assemble_b(self, T, Tf, ranks, gran, F, Wt, B, slots=None, sW=None, f32=False, fill=0.0):
+        """B = I + F^T Wt F of the low-rank engine (pgpfa_test_assemble_b) on caller data.  F (p, Tf, Tf) indexed [latent, column, bin]; Wt (nslots, sW)
+        float64, bin t of a slot at t p p, or (T p p,) / (1, T p p) with sW = 0 (one shared slot); B (nslots, rpad, rpad) indexed [slot, column, row], the
+        output buffer with the caller's prefill, float32 with f32.  slots: the slot list (None: all, in order).
+        Returns (B as the device left it, info): info holds rr, rk, roff, roff16, rtot, rtot16, rpad, compact, nblk64, npairs, nact, blk_lat, blk_col, cmap.
+        A refused geometry raises HipBackendError with .rc and .refusal (its name in ASMB_REFUSALS)."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int32)
+        p = len(ranks)
+        F = as_f64(F)
+        assert F.shape == (p, int(Tf), int(Tf))
+        out = np.array(B, dtype=np.float32 if f32 else np.float64, order='C', copy=True)
+        assert out.ndim == 3 and out.shape[1] == out.shape[2]
+        nslots = out.shape[0]
+        Wt = as_f64(Wt)
+        if sW is None:
+            sW = Wt.shape[1] if Wt.ndim == 2 else 0
+        assert Wt.size >= (int(sW) * nslots if sW else 1)
+        sl = np.ascontiguousarray(np.arange(nslots) if slots is None else slots, dtype=np.int32)
+        geom = np.zeros(4 * p + 9, dtype=np.int32)
+        cap = 16 * (16 * p + 256) + 1024
+        tabs = [np.zeros(cap, dtype=np.int32) for _ in range(3)]
+        ntab = np.zeros(2, dtype=np.int32)
+        rc = self.lib.pgpfa_test_assemble_b(self.h, p, int(T), int(Tf), iptr(ranks), int(gran), int(bool(f32)), nslots, len(sl), iptr(sl), int(sW), float(fill),
+                                            dptr(F), dptr(Wt), out.ctypes.data_as(ct.c_void_p), out.shape[1], iptr(geom), cap, iptr(tabs[0]), iptr(tabs[1]),
+                                            iptr(tabs[2]), iptr(ntab))
+        if rc != 0:
+            err = HipBackendError(self.lib.pgpfa_last_error().decode('utf-8', 'replace'))
+            err.rc = rc
+            err.refusal = self.ASMB_REFUSALS.get(rc)
+            raise err
+        g = geom[4 * p + 2:]
+        info = dict(rr=geom[:p].copy(), rk=geom[p:2 * p].copy(), roff=geom[2 * p:3 * p + 1].copy(), roff16=geom[3 * p + 1:4 * p + 2].copy(), rtot=int(g[0]),
+                    rtot16=int(g[1]), rpad=int(g[2]), compact=bool(g[3]), nblk64=int(g[4]), npairs=int(g[5]), nact=int(g[6]),
+                    blk_lat=tabs[0][:ntab[0]].copy(), blk_col=tabs[1][:ntab[0]].copy(), cmap=tabs[2][:ntab[1]].copy())
         return out, info
 
     def bench_mfma_peak(self, iters=20000):

@@ -355,6 +355,34 @@ int pgpfa_posterior_sample(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
                            uint16_t* Y         /* [n][S][q][T] or NULL */,
                            int32_t*  count_sum /* [n][S][q]    or NULL */);
 
+/* Importance weights of the Laplace posterior's own draws: how far the Gaussian at the mode is from the true posterior of a trial, and the correction
+ * of its log evidence.  With f = negLogPosteriorUnNorm (inference.py:12-32), x* the resident mode of trial r = idx[i], H the Hessian there and
+ * x_s = x* + delta_s draw s of pgpfa_posterior_sample under `seed` - bit for bit the X[i][s] that call returns for the same (seed, trial, s) -,
+ *   log p(y, x_s) - log N(x_s; x*, H^-1) = log Z_Laplace + log w_s,        log w_s = - [ f(x_s) - f(x*) - 1/2 delta_s^T H delta_s ].
+ * The prior is quadratic and cancels; at a stationary mode what is left of it cancels the first-order likelihood term, counts included, so that
+ *   log_w[i][s]  = - sum_{(n,t) live} lambda*_nt phi(c_n . delta_st),   lambda*_nt = exp(d_n + c_n . x*_t),   phi(a) = e^a - 1 - a - a^2 / 2
+ *   log_ratio[i] = log (1/S) sum_s w_s        log Z_Laplace + log_ratio estimates the trial's true log evidence: (1/S) sum_s w_s is unbiased for
+ *                                              Z / Z_Laplace (log Z_Laplace: pgpfa_get_log_evidence, same normalisation)
+ *   ess[i]       = (sum_s w_s)^2 / sum_s w_s^2 effective sample size, 1 .. S: near S where the Laplace posterior can be trusted
+ * and the w_s, self-normalised, turn the draws of pgpfa_posterior_sample with the same seed into an importance sampler of the true posterior.  The
+ * only approximation is that the gradient g at x* is zero: a residual one adds - g . delta_s to log w_s, which is ignored (the E-step's stopping
+ * rule bounds it).  The sum runs over the entries that carry a likelihood term under the three missing-data tables; every other entry adds exactly
+ * 0, whatever C and d hold there.  K is the prior the covariance engine in use is exact for - the sum needs no K^-1, no counts and no pT x pT
+ * object: one pass over the draws on the FP64 matrix cores (csrc/impw.h) behind the sampler, whose engine follows the plan as there; the list is
+ * walked in chunks (option "sample_chunk_trials") and no X plane goes to the host.  No floating-point atomics: the tiles of a draw and the draws of
+ * a trial are added in index order (log_ratio max-shifted), so log_w[i][s] is a function of the draw and the trial alone - the trial's position in the
+ * list, the chunks and n_samples enter no sum -, and log_ratio and ess depend on n_samples besides; a trial listed twice gets the same numbers twice.  An overflowing e^a gives
+ * log_w = -inf (weight 0).
+ * Fails, naming what is wrong: n_samples < 1; every output NULL; set_params not called; no counts table; an asynchronous timescale pass in flight;
+ * a trial without a posterior that can be sampled (as pgpfa_posterior_sample), naming the trial; a trial whose posterior is variational
+ * (pgpfa_dual_finalize), naming the trial - the identity is the Laplace approximation's -; a log weight that is NaN, naming the trial.
+ * Leaves untouched what pgpfa_posterior_sample leaves untouched. */
+int pgpfa_importance_weights(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                             int n_samples, unsigned long long seed,
+                             double* log_ratio /* [n]    log mean_s w_s, or NULL */,
+                             double* ess       /* [n]    or NULL */,
+                             double* log_w     /* [n][S] or NULL */);
+
 /* The latent posterior at arbitrary time points.  The Gaussian posterior N(m, Sigma) over the T grid times t_j = j bin_ms resident for trial
  * r = idx[i] - the posterior being whatever is resident for the trial, as pgpfa_posterior_rates defines it - extends to any time s (ms from the
  * trial's first bin) by the prior conditional of the GP.  Per latent k, with K_k the Gram matrix of pgpfa_get_gram and V_k = post_vsmGP[:, :, k]:

@@ -1,9 +1,10 @@
 // libpgpfa_hip.so - psample.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): joint posterior samples of the latents and
-// posterior-predictive spike counts (pgpfa_posterior_sample)
+// posterior-predictive spike counts (pgpfa_posterior_sample); importance weights of the Laplace posterior's draws (pgpfa_importance_weights)
 #include "ctx.h"
 #include "model.h"
 #include "sample.h"
 #include "psample.h"
+#include "impw.h"
 
 using namespace pgpfa;
 
@@ -17,6 +18,9 @@ struct SampleArgs {
   const double* noise_in; double* noise_out; double* X; uint16_t* Y; int32_t* count_sum;
   bool lowrank;                       // engine the call's noise dimension was sized for
   int nz;
+  // step 6, pgpfa_importance_weights (all NULL: not asked for - the call path is the one it was): per list position
+  double* log_ratio; double* ess; double* log_w;
+  const char* entry;                  // the entry point, for its messages (NULL: pgpfa_posterior_sample)
 };
 
 // the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
@@ -34,17 +38,24 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
     return fail("the posterior of trial %d was computed under timescales whose low-rank system has %d rows, the noise of this call has %d (the rank under the current "
                 "parameters): set the parameters of that E-step before sampling it", t_first, rz, nz - n);
   const bool want_counts = a.Y || a.count_sum;
+  const bool want_weights = a.log_ratio || a.ess || a.log_w;
+  const char* entry = a.entry ? a.entry : "pgpfa_posterior_sample";
+  const int ntile = (T + 15) / 16;                             // bin tiles of impw_kernel
 
   // chunks of the group: device staging per trial (noise, U, trajectories, count planes)
   const size_t ldz = lr ? (size_t)rpad : (size_t)npad;       // leading dimension of the GEMM's noise operand (z2 panel / dense z), zero below the rows in use
-  const size_t per_trial = (size_t)S * (((lr ? 2 * ldz + n : ldz) + n) * sizeof(double) + (a.Y ? (size_t)q * T * sizeof(uint16_t) : 0) + (want_counts ? (size_t)q * sizeof(int) : 0));
+  const size_t per_trial = (size_t)S * (((lr ? 2 * ldz + n : ldz) + n) * sizeof(double) + (a.Y ? (size_t)q * T * sizeof(uint16_t) : 0) + (want_counts ? (size_t)q * sizeof(int) : 0) +
+                                              (want_weights ? (size_t)(ntile + 1) * sizeof(double) : 0));
   const int chunk = query_chunk(pos.size(), c->sample_chunk, per_trial, (size_t)c->B);
-  if ((long long)chunk * S > (1LL << 30)) return fail("pgpfa_posterior_sample: %d samples of %d trials exceed one chunk's columns", S, chunk);
+  if ((long long)chunk * S > (1LL << 30)) return fail("%s: %d samples of %d trials exceed one chunk's columns", entry, S, chunk);
+  if (want_weights && (chunk > 65535 || (S + IMPW_NS - 1) / IMPW_NS > 65535))
+    return fail("%s: %d samples of %d trials per chunk exceed the weight kernel's grid (65535 trials, %d samples)", entry, S, chunk, 65535 * IMPW_NS);
 
-  DevBufs dev("pgpfa_posterior_sample");
+  DevBufs dev(entry);
   double *dX = nullptr, *dZ1 = nullptr, *dZ = nullptr, *dU = nullptr;
   uint16_t* dY = nullptr;
-  int *dCs = nullptr, *dOver = nullptr;
+  int *dCs = nullptr, *dOver = nullptr, *dBad = nullptr;
+  double *dPart = nullptr, *dLw = nullptr, *dLr = nullptr, *dEss = nullptr;
   const size_t cols = (size_t)chunk * S;
   CHK(dev.get(&dX, cols * n));
   CHK(dev.get(&dZ, (cols + GEMM_COL_SLACK) * ldz));
@@ -56,10 +67,15 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
   }
   if (a.Y) CHK(dev.get(&dY, cols * q * T));
   if (want_counts) { CHK(dev.get(&dCs, cols * q)); CHK(dev.get(&dOver, (size_t)chunk)); }
+  if (want_weights) {
+    CHK(dev.get(&dPart, cols * ntile)); CHK(dev.get(&dLw, cols));
+    CHK(dev.get(&dLr, (size_t)chunk)); CHK(dev.get(&dEss, (size_t)chunk)); CHK(dev.get(&dBad, (size_t)chunk));
+  }
   const int zused = lr ? rz : n;                               // rows of dZ a draw fills: z2, or the dense z
   const size_t zoff = lr ? (size_t)n : 0;                      // where they sit in a draw's nz normals
 
-  std::vector<int> over(chunk), tos;
+  std::vector<int> over(chunk), bad(want_weights ? chunk : 0), tos;
+  std::vector<double> lr_h(want_weights ? chunk : 0), ess_h(want_weights ? chunk : 0);
   const size_t m = (size_t)q * T;
   for (size_t c0 = 0; c0 < pos.size(); c0 += chunk) {
     const int nb = (int)std::min<size_t>((size_t)chunk, pos.size() - c0);
@@ -120,7 +136,7 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&psample_mix_kernel<PW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { rc = 1; return; }
         hipLaunchKernelGGL(psample_mix_kernel<PW>, dim3((T + psample_bt(PW) - 1) / psample_bt(PW), nb), dim3(256), lds, c->st, mx);
       });
-      if (rc) { (void)hipGetLastError(); return fail("pgpfa_posterior_sample: the mixing kernel's LDS size was refused"); }
+      if (rc) { (void)hipGetLastError(); return fail("%s: the mixing kernel's LDS size was refused", entry); }
     } else {
       // 5. dense engine: X = m + L^-T Z
       GemmP g{};
@@ -145,6 +161,24 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
       HIPC(hipGetLastError());
       HIPC(hipMemcpyAsync(over.data(), dOver, sizeof(int) * nb, hipMemcpyDeviceToHost, c->st));
     }
+    // 6. importance weights of the draws (impw.h): partial sums per (slot, draw, bin tile), then the tiles of a draw and the draws of a slot in order
+    if (want_weights) {
+      ImpwP ip{};
+      ip.X = dX; ip.Xmode = c->Xmode; ip.C = c->C; ip.d = c->d; ip.trial_of_slot = c->trial_of_slot; ip.part = dPart;
+      ip.S = S; ip.q = q; ip.p = p; ip.T = T; ip.ntile = ntile;
+      c->live.fill(ip);
+      const dim3 grid((unsigned)ntile, (unsigned)((S + IMPW_NS - 1) / IMPW_NS), (unsigned)nb);
+      dispatch_obs(c->live.state(), [&](auto ob) { hipLaunchKernelGGL((impw_kernel<decltype(ob)::value>), grid, dim3(256), impw_lds(p), c->st, ip); });
+      HIPC(hipGetLastError());
+      hipLaunchKernelGGL(impw_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, c->st, dPart, S, ntile, dLw, dLr, dEss, dBad);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(bad.data(), dBad, sizeof(int) * nb, hipMemcpyDeviceToHost, c->st));
+      HIPC(hipMemcpyAsync(lr_h.data(), dLr, sizeof(double) * nb, hipMemcpyDeviceToHost, c->st));
+      HIPC(hipMemcpyAsync(ess_h.data(), dEss, sizeof(double) * nb, hipMemcpyDeviceToHost, c->st));
+      if (a.log_w)
+        for (int s = 0; s < nb; ++s)
+          HIPC(hipMemcpyAsync(a.log_w + (size_t)pos[c0 + s] * S, dLw + (size_t)s * S, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    }
     // results of the chunk, by list position
     for (int s = 0; s < nb; ++s) {
       const size_t ps = (size_t)pos[c0 + s];
@@ -166,6 +200,12 @@ int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos,
           double* dst = a.noise_out + ((size_t)pos[c0 + s] * S + j) * nz;
           std::fill(dst + zoff + zused, dst + nz, 0.0);
         }
+    if (want_weights)
+      for (int s = 0; s < nb; ++s) {
+        if (bad[s]) return fail("%s: a log weight of trial %d is not a number: its mode, its draws or the parameters of its E-step are not finite", entry, tos[s]);
+        if (a.log_ratio) a.log_ratio[pos[c0 + s]] = lr_h[s];
+        if (a.ess) a.ess[pos[c0 + s]] = ess_h[s];
+      }
     if (want_counts)
       for (int s = 0; s < nb; ++s)
         if (over[s]) return fail("a predictive count of trial %d exceeds 65535: the rates exp(d + C x) of its draws do not fit the uint16 output", tos[s]);
@@ -194,6 +234,29 @@ int pgpfa_posterior_sample(pgpfa_ctx* c, int n, const int32_t* idx, int n_sample
   bool any_laplace = false;
   for (int t : tr.v) any_laplace = any_laplace || !c->trial_dual[t];
   a.lowrank = want_lowrank(c) && (any_laplace || c->dual_lowrank);
+  a.nz = c->n + (a.lowrank ? c->rtot : 0);
+  return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool dual) { return sample_group(c, a, pos, dual); });
+}
+
+int pgpfa_importance_weights(pgpfa_ctx* c, int n, const int32_t* idx, int n_samples, unsigned long long seed, double* log_ratio, double* ess, double* log_w) {
+  if (!c) return fail("null context");
+  if (n_samples < 1) return fail("pgpfa_importance_weights: n_samples = %d, at least one draw per trial is needed", n_samples);
+  if (!log_ratio && !ess && !log_w) return fail("pgpfa_importance_weights: no output asked for (log_ratio, ess and log_w are all NULL)");
+  if (!c->have_params) return fail("set_params has not been called");
+  if (!c->have_counts)
+    return fail("spike counts have not been uploaded: the weights sum over every trial's live entries, which are unknown without the counts table");
+  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
+  HIPC(hipSetDevice(c->device));
+  Trials tr;
+  CHK(resolve_trials(c, n, idx, &tr));
+  CHK(require_resident(c, tr.v, RESIDENT_SAMPLABLE));
+  for (int t : tr.v)
+    if (c->trial_dual[t])
+      return fail("pgpfa_importance_weights: the posterior of trial %d is variational (pgpfa_dual_finalize): the identity behind the weights is the Laplace "
+                  "approximation's - the Gaussian at a stationary mode with the Hessian as precision - and does not hold for it", t);
+  SampleArgs a{};
+  a.trials = &tr.v; a.S = n_samples; a.seed = seed; a.log_ratio = log_ratio; a.ess = ess; a.log_w = log_w; a.entry = "pgpfa_importance_weights";
+  a.lowrank = want_lowrank(c);                                 // (every listed trial is a Laplace one: the engine of pgpfa_posterior_sample's draws)
   a.nz = c->n + (a.lowrank ? c->rtot : 0);
   return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool dual) { return sample_group(c, a, pos, dual); });
 }

@@ -47,6 +47,7 @@ _SIGNATURES = {
     'pgpfa_set_posterior': [ct.c_void_p, ct.c_int, c_int32_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_rates': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p],
     'pgpfa_posterior_sample': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p, ct.POINTER(ct.c_uint16), c_int32_p],
+    'pgpfa_importance_weights': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, ct.c_ulonglong, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p],
     'pgpfa_posterior_cov_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_velocity_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int] + [c_double_p] * 5,
@@ -431,6 +432,22 @@ class Context:
         check(self.lib.pgpfa_posterior_sample(self.h, n, iptr(ii), S, ct.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), None if zin is None else dptr(zin),
                                               dptr(out['noise']) if 'noise' in out else None, dptr(out['x']) if 'x' in out else None,
                                               None if y is None else y.ctypes.data_as(ct.POINTER(ct.c_uint16)), iptr(out.get('count_sum'))))
+        return out
+
+    def importance_weights(self, idx=None, n_samples=256, seed=0, want=('log_ratio', 'ess')):
+        """Importance weights of the Laplace posterior's own draws for the listed trials (repeats allowed; include/pgpfa.h:
+        pgpfa_importance_weights).  want: any of 'log_ratio' [n] - log of the mean weight, the correction log Z - log Z_Laplace of the trial's log
+        evidence -, 'ess' [n] - the effective sample size - and 'log_w' [n][S], the log weight of draw s of posterior_sample under the same seed.
+        Returns a dict of exactly the arrays asked for; the draws themselves stay on the device."""
+        n, ii = self._n_idx(idx)
+        S = int(n_samples)
+        _check_outputs(want, ('log_ratio', 'ess', 'log_w'), may_be_empty=S < 1)
+        if S < 1:
+            raise ValueError('n_samples = %d: at least one draw per trial is needed' % S)
+        shapes = {'log_ratio': (n,), 'ess': (n,), 'log_w': (n, S)}
+        out = {k: np.empty(shapes[k]) for k in shapes if k in want}
+        ptr = lambda k: dptr(out[k]) if k in out else None
+        check(self.lib.pgpfa_importance_weights(self.h, n, iptr(ii), S, ct.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ptr('log_ratio'), ptr('ess'), ptr('log_w')))
         return out
 
     def posterior_at(self, times, idx=None, want=('mean', 'var')):

@@ -316,6 +316,14 @@ class PPGPFAfit():
         self.samples = util.posteriorSamples(self.optimParams, self.experiment, **kw)
         return self.samples
 
+    def importanceEvidence(self, **kw):
+        """util.importanceEvidence at the fitted parameters -> self.importance (a dict; keywords as there: infRes, trials, nSamples, seed, want).
+        Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.importance = util.importanceEvidence(self.optimParams, self.experiment, **kw)
+        return self.importance
+
     def posteriorCounts(self, **kw):
         """util.posteriorCounts at the fitted parameters -> self.counts (a dict; keywords as there: infRes, trials, counts, maxCount, level,
         forecast, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""

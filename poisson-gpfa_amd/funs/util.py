@@ -365,7 +365,7 @@ def _predictive_keys(truth, logp, scored):
             'bitsPerSpikePredictivePerNeuron': per_row}
 
 
-_SAMPLE_KEYS = ('x', 'y', 'count_sum', 'noise')
+_SAMPLE_KEYS = ('x', 'y', 'count_sum', 'noise', 'logWeights')
 
 
 def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100, seed=0, want=('x',)):
@@ -380,7 +380,9 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
     raises ValueError.  trials: positions in experiment.data (None: all; repeats allowed - a repeated trial gets the same draws).
     want: any of 'x' [n][nSamples][xdim][T], 'y' [n][nSamples][ydim][T] (uint16: y ~ Poisson(exp(d + C x)) per bin), 'count_sum'
     [n][nSamples][ydim] (the counts of a draw summed over the trial's bins) and 'noise' (the standard normals used).  With trials of unequal
-    length 'x' and 'y' are lists of arrays cut to each trial's own T_r bins.  Draw s of a trial is a pure function of (seed, trial, s)."""
+    length 'x' and 'y' are lists of arrays cut to each trial's own T_r bins.  Draw s of a trial is a pure function of (seed, trial, s).
+    'logWeights' [n][nSamples] (Laplace posteriors only): the log importance weights of exactly these draws (importanceEvidence, same seed) -
+    exp(logWeights), normalised per trial, re-weights any function of 'x' from the Laplace posterior to the true one."""
     want = tuple(want)
     unknown = [k for k in want if k not in _SAMPLE_KEYS]
     if unknown:
@@ -390,7 +392,11 @@ def posteriorSamples(params, experiment, infRes=None, trials=None, nSamples=100,
     if int(nSamples) != nSamples or int(nSamples) < 1:
         raise ValueError('nSamples = %r: a count of draws per trial, at least 1' % (nSamples,))
     sess, idx = _resident_posterior('posteriorSamples', params, experiment, infRes, trials, set_params=False)
-    dev = sess.ctx.posterior_sample(idx, n_samples=int(nSamples), seed=int(seed), want=want)
+    dev = {}
+    if any(k != 'logWeights' for k in want):
+        dev = sess.ctx.posterior_sample(idx, n_samples=int(nSamples), seed=int(seed), want=tuple(k for k in want if k != 'logWeights'))
+    if 'logWeights' in want:
+        dev['logWeights'] = sess.ctx.importance_weights(idx, n_samples=int(nSamples), seed=int(seed), want=('log_w',))['log_w']
     out = {}
     for k in want:
         arr = dev[k]
@@ -856,19 +862,67 @@ def negLogEvidencePerBin(params, experiment):
     return -float(infRes.mean_log_evidence) * len(experiment.data) / bins
 
 
+_IMPORTANCE_KEYS = ('logEvidence', 'laplace', 'logRatio', 'ess', 'logWeights')
+
+
+def importanceEvidence(params, experiment, infRes=None, trials=None, nSamples=256, seed=0, want=('logEvidence', 'ess')):
+    """The Laplace log evidence of every listed trial corrected by importance sampling from the Laplace posterior itself, and how far that
+    Gaussian is from the trial's true posterior.  With w_s the importance weights of nSamples draws (pgpfa_importance_weights; the draws are
+    those of posteriorSamples under the same seed and never leave the device):
+      'logEvidence' [n]  log Z_Laplace + log mean_s w_s - mean_s w_s is an unbiased estimator of Z / Z_Laplace, so this estimates the trial's
+                         true log marginal likelihood (normalisation of the Laplace value: sum log y! dropped)
+      'laplace'     [n]  log Z_Laplace itself          'logRatio' [n]  the correction, log mean_s w_s
+      'ess'         [n]  effective sample size (sum w)^2 / sum w^2, between 1 and nSamples: near nSamples where Laplace can be trusted
+      'logWeights'  [n][nSamples]  log w_s (with posteriorSamples(..., seed=seed): a self-normalised importance sampler of the true posterior)
+    The dict holds the keys of `want`.  infRes None: one Laplace E-step at `params` over the experiment with inference.LAPLACE_EVIDENCE on (the
+    switch is restored).  A DeviceInfRes of this experiment's session whose entries are still the resident ones: that posterior - it must come
+    from a Laplace E-step that computed the evidence, the library's error comes through otherwise.  trials: positions in experiment.data (None:
+    all; repeats allowed).  The weights assume a stationary mode; nothing here acts on a low ess - it is reported."""
+    from . import inference
+    want = tuple(want)
+    unknown = [k for k in want if k not in _IMPORTANCE_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_IMPORTANCE_KEYS)))
+    if not want:
+        raise ValueError('nothing asked for: want is empty')
+    if int(nSamples) != nSamples or int(nSamples) < 1:
+        raise ValueError('nSamples = %r: a count of draws per trial, at least 1' % (nSamples,))
+    switch = inference.LAPLACE_EVIDENCE
+    if infRes is None:
+        inference.LAPLACE_EVIDENCE = True
+    try:
+        sess, idx = _resident_posterior('importanceEvidence', params, experiment, infRes, trials, set_params=False)
+    finally:
+        inference.LAPLACE_EVIDENCE = switch
+    laplace = sess.ctx.log_evidence(idx)
+    dev = sess.ctx.importance_weights(idx, n_samples=int(nSamples), seed=int(seed), want=('log_ratio', 'ess') + (('log_w',) if 'logWeights' in want else ()))
+    full = {'logEvidence': laplace + dev['log_ratio'], 'laplace': laplace, 'logRatio': dev['log_ratio'], 'ess': dev['ess'], 'logWeights': dev.get('log_w')}
+    return {k: full[k] for k in want}
+
+
+def negLogImportanceEvidencePerBin(params, experiment, nSamples, seed=0):
+    """- sum_r (log Z_Laplace,r + logRatio_r) / sum_r T_r over the experiment's trials: negLogEvidencePerBin with every trial's log evidence
+    corrected by importanceEvidence(nSamples, seed) - one Laplace E-step at `params` and one pass of weights."""
+    res = importanceEvidence(params, experiment, nSamples=nSamples, seed=seed, want=('logEvidence',))
+    bins = sum(int(np.shape(tr['Y'])[1]) for tr in experiment.data)
+    return -float(np.sum(res['logEvidence'])) / bins
+
+
 class crossValidation:
     """reference util.py:180-249: for xdim = 1..maxXdim fit on the training split and score the leave-one-neuron-out
     prediction error on the test split; optimXdim is the arg-min.  learningMethod: 'batch', 'diag', 'hess' or 'grad'.
     score='evidence' (an addition; Laplace only) scores a fit by ONE Laplace E-step of its parameters on the test split instead of the
     numTestTrials * ydim held-out mode searches: errs[i] = - sum_r log Z_r / sum_r T_r, the negative Laplace log evidence per bin (lower is
     better, so optimXdim stays the arg-min).  It also takes test trials of unequal length, which the leave-one-out score refuses.
+    importance=S (with score='evidence'; None - the default - is the Laplace score itself) corrects every test trial's log evidence by
+    importance sampling with S draws under `seed` (importanceEvidence): errs[i] = - sum_r (log Z_Laplace,r + logRatio_r) / sum_r T_r.
     score='speckled' (an addition; Laplace only) hides a seeded random subset of the TRAINING trials' live entries (speckledHoldout: each with
     probability holdoutFraction, numpy.random.default_rng(seed), the same subset for every width), fits on the rest and scores the fit by
     binHoldout at the hidden entries: errs[i] = - bitsPerSpike (lower is better); the test split is not used.  predictive=True (with
     score='speckled') scores by the predictive distribution of the counts instead: errs[i] = - bitsPerSpikePredictive."""
 
     def __init__(self, experiment, numTrainingTrials=10, numTestTrials=2, maxXdim=6, maxEMiter=3, batchSize=5,
-                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo', holdoutFraction=0.1, seed=0, predictive=False):
+                 inferenceMethod='laplace', learningMethod='batch', quiet=True, score='loo', holdoutFraction=0.1, seed=0, predictive=False, importance=None):
         from . import engine
         if learningMethod not in ('batch', 'diag', 'hess', 'grad'):
             raise ValueError("learningMethod must be 'batch', 'diag', 'hess' or 'grad'")
@@ -880,6 +934,10 @@ class crossValidation:
             raise ValueError("score='speckled' fits and scores under a per-bin table: it needs inferenceMethod='laplace'")
         if predictive and score != 'speckled':
             raise ValueError("predictive=True is the predictive score of binHoldout: it needs score='speckled'")
+        if importance is not None and score != 'evidence':
+            raise ValueError("importance=S corrects the Laplace log evidence: it needs score='evidence'")
+        if importance is not None and (int(importance) != importance or int(importance) < 1):
+            raise ValueError('importance = %r: a count of draws per trial, at least 1 (None: the Laplace score)' % (importance,))
         trainingSet, testSet = splitTrainingTestDataset(experiment, numTrainingTrials, numTestTrials)
         if score == 'speckled':
             scoredSet = trainingSet                       # (the hidden entries are scored against the training trials' true counts)
@@ -898,12 +956,13 @@ class crossValidation:
             if score == 'speckled':
                 predErr = -binHoldout(fit.optimParams, scoredSet, self.heldOut, predictive=predictive)['bitsPerSpikePredictive' if predictive else 'bitsPerSpike']
             elif score == 'evidence':
-                predErr = negLogEvidencePerBin(fit.optimParams, testSet)
+                predErr = (negLogEvidencePerBin(fit.optimParams, testSet) if importance is None
+                           else negLogImportanceEvidencePerBin(fit.optimParams, testSet, int(importance), seed))
             else:
                 _, predErr = leaveOneOutPrediction(fit.optimParams, testSet)
             self.errs.append(predErr)
             self.fits.append(fit)
-        self.inferenceMethod, self.learningMethod, self.score = inferenceMethod, learningMethod, score
+        self.inferenceMethod, self.learningMethod, self.score, self.importance = inferenceMethod, learningMethod, score, importance
         self.optimXdim = int(np.argmin(self.errs)) + 1
         self.maxXdim = maxXdim
 

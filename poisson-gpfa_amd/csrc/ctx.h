@@ -1,6 +1,6 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
-// the ones it launches (core.hip: context, workspace, copies; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
+// the ones it launches (core.hip: context, copies; workspace.hip: arena and workspace plans, no kernel; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
 // covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -506,7 +506,15 @@ struct VarJob {
 
 
 // ---- shared host-side helpers (definitions: the translation unit named in the comment) ---------------------------------------
-// core.hip: staging, copies, workspace plans, parameter-derived operators, trial lists, snapshots
+// workspace.hip: factor workspaces, the arena and its pool, workspace plans, the engine choice (arithmetic and rules: plan.h)
+int alloc_cholws(pgpfa_ctx* c, pgpfa::CholWS* w, int nslots, int npad, bool with_mt, size_t slab_elems = 0, bool zero_mt = true, size_t mt_elems = 0);
+bool lowrank_pays(const pgpfa_ctx* c);
+bool want_lowrank(const pgpfa_ctx* c);
+int free_workspace(pgpfa_ctx* c);
+int arena_grow(pgpfa_ctx* c, size_t need, double budget_ms = 0.0, size_t must = 0);
+void arena_release(pgpfa_ctx* c, bool unmap = false);
+int ensure_workspace(pgpfa_ctx* c, bool plan_lr);
+// core.hip: staging, copies, parameter-derived operators, trial lists, snapshots
 int ensure_hbuf(pgpfa_ctx* c, size_t len);
 int ensure_hibuf(pgpfa_ctx* c, size_t len);
 void prof_harvest(Prof& P, bool all);
@@ -514,16 +522,6 @@ hipEvent_t prof_event(Prof& P);
 void prof_begin(pgpfa_ctx* c, int tag, double flops);
 void prof_end(pgpfa_ctx* c);
 void prof_collect(pgpfa_ctx* c);
-int alloc_cholws(pgpfa_ctx* c, pgpfa::CholWS* w, int nslots, int npad, bool with_mt, size_t slab_elems = 0, bool zero_mt = true, size_t mt_elems = 0);
-size_t lowrank_slab_elems(const pgpfa_ctx* c);
-bool lowrank_pays(const pgpfa_ctx* c);
-bool want_lowrank(const pgpfa_ctx* c);
-size_t ld_bytes(const pgpfa_ctx* c);
-size_t per_slot_bytes(const pgpfa_ctx* c, size_t slab_elems, size_t mt_elems);
-int free_workspace(pgpfa_ctx* c);
-int arena_grow(pgpfa_ctx* c, size_t need, double budget_ms = 0.0, size_t must = 0);
-void arena_release(pgpfa_ctx* c, bool unmap = false);
-int ensure_workspace(pgpfa_ctx* c, bool plan_lr);
 int upload_list(pgpfa_ctx* c, int* dst, const std::vector<int>& v);
 int copy_dev(pgpfa_ctx* c, void* dst, const void* src, size_t bytes);
 int dl_flush(pgpfa_ctx* c);

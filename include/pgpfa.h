@@ -179,6 +179,9 @@ int pgpfa_destroy(pgpfa_ctx* ctx);
  * "covat_chunk_trials" (0 - the default; the same for pgpfa_posterior_cov_at), "covat_block_times" (0 - the default: pgpfa_posterior_cov_at walks
  * its query times in blocks sized so that the right-hand sides of a block stay within that bound; > 0: that many times per block, rounded up to 16.
  * No output depends on it, bit for bit),
+ * "func_chunk_trials" (0 - the default; the same for pgpfa_posterior_functionals), "func_block_cols" (0 - the default: pgpfa_posterior_functionals
+ * pushes its functionals through the square root in blocks sized so that the staging of a block stays within that bound; > 0: that many functionals
+ * per block, a multiple of 16.  No output depends on it, bit for bit),
  * "counts_chunk_trials" (0 - the default; the same for pgpfa_posterior_counts), "counts_nodes" (32: nodes of the Gauss-Hermite rule of
  * pgpfa_count_probabilities / pgpfa_posterior_counts, 8 .. 64; the rule's error falls with it and the cost grows in proportion). */
 int pgpfa_set_option(pgpfa_ctx* ctx, const char* key, double value);
@@ -432,6 +435,35 @@ int pgpfa_posterior_cov_at(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: al
                            int S, const double* times_ms /* [S], or [n][S] when per_trial != 0 */, int per_trial,
                            double* mean /* [n][p][S] or NULL */, double* cov /* [n][S][p][p] or NULL */,
                            double* eta /* [n][q][S] or NULL */, double* var /* [n][q][S] or NULL */);
+
+/* Joint posterior of linear functionals of a trial's latents: epoch means, contrasts between epochs, projections of a whole trajectory onto a
+ * decoding axis or a temporal template, window-averaged log rates - the questions that span time, which need the covariance BETWEEN bins.  With m
+ * the resident posterior mean of trial r = idx[i] laid out [p][T], Sigma its p T x p T covariance (the layout of pgpfa_get_post_cov) and J weight
+ * vectors u_j laid out [p][T],
+ *   mean[i][j]   = u_j . m
+ *   cov[i][j][l] = u_j^T Sigma u_l,      var[i][j] = cov[i][j][j]
+ * Sigma is never formed: the call builds the square root M (Sigma = M M^T) that pgpfa_posterior_sample draws from and pgpfa_posterior_cov_at uses -
+ * G, F and L as in the comments above those two -, pushes the weights through it and takes the Gram of the results on the FP64 matrix cores
+ * (csrc/pfunc.h):
+ *   dense engine      Sigma = L^-T L^-1                               Q = L^-1 U                cov = Q^T Q
+ *   low-rank engine   Sigma = eps G + (G F L^-T)(G F L^-T)^T          V = G U,  Q = L^-1 F^T V  cov = Q^T Q + eps U^T V
+ * in FP64 whatever "laplace_f32" says.  The engine follows the plan, the parameter snapshots and the three missing-data tables as those two calls do.
+ * A trial shorter than T needs nothing special: its padded bins hold the GP forecast under the square root, so weights there give the forecast's
+ * contribution.  weights: one set [J][p][T] for all listed trials or, with per_trial != 0, one set [n][J][p][T] per list entry (windows aligned
+ * to an event that falls at another bin in every trial).  With cov asked for J <= 1024; without it any J, walked in blocks, and no J x J plane
+ * is formed.
+ * A trial's result does not depend on its position in the list, on which other trials are listed, on how the list is cut into chunks or the
+ * functionals into blocks (options "func_chunk_trials", "func_block_cols"), on shared against per-trial weights, or on which other outputs are asked
+ * for, bit for bit; a trial listed twice gives the same numbers twice; cov is symmetric to the bit, var has the bits of its diagonal, both clamped
+ * at 0.  No floating-point atomics.
+ * Fails, naming what is wrong: J < 1; all three outputs NULL; weights NULL; a weight that is not finite, naming functional, latent and bin (and the
+ * list entry when per_trial; before any device call); cov with J > 1024; set_params not called; an asynchronous timescale pass in flight; a trial
+ * without a posterior, naming the trial; a posterior uploaded with pgpfa_set_posterior (only its blocks are known: it has no square root); a
+ * variational posterior of a trial shorter than T.
+ * Leaves untouched what pgpfa_posterior_sample leaves untouched.  Uses the chunk workspace when var or cov is asked for. */
+int pgpfa_posterior_functionals(pgpfa_ctx* ctx, int n, const int32_t* idx /* NULL: all; repeats allowed */,
+                                int J, const double* weights /* [J][p][T], or [n][J][p][T] when per_trial != 0 */, int per_trial,
+                                double* mean /* [n][J] or NULL */, double* var /* [n][J] or NULL */, double* cov /* [n][J][J] or NULL */);
 
 /* Value and velocity of every latent at arbitrary time points, with their joint 2 x 2 posterior per latent.  Under the prior the time derivative
  * xdot_k(s) is jointly Gaussian with the grid values, so its posterior follows by the prior conditional of pgpfa_posterior_at with the cross Gram

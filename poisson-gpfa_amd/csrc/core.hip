@@ -985,6 +985,11 @@ int pgpfa_set_option(pgpfa_ctx* c, const char* key, double v) {
   else if (k == "covat_chunk_trials") CHK(chunk_trials(&c->covat_chunk));
   else if (k == "velat_chunk_trials") CHK(chunk_trials(&c->velat_chunk));
   else if (k == "covat_block_times") { if (v < 0.0 || v != std::floor(v)) return fail("covat_block_times is a count of query times, or 0"); c->covat_block = (int)v; }
+  else if (k == "func_chunk_trials") CHK(chunk_trials(&c->func_chunk));
+  else if (k == "func_block_cols") {
+    if (v < 0.0 || v != std::floor(v) || std::fmod(v, 16.0) != 0.0) return fail("func_block_cols is a count of functionals that is a multiple of 16, or 0");
+    c->func_block = (int)v;
+  }
   else if (k == "rates_chunk_trials") CHK(chunk_trials(&c->rates_chunk));
   else if (k == "counts_chunk_trials") CHK(chunk_trials(&c->counts_chunk));
   else if (k == "counts_nodes") { if (v < 8.0 || v > 64.0 || v != std::floor(v)) return fail("counts_nodes is a node count in 8 .. 64"); c->counts_Q = (int)v; }

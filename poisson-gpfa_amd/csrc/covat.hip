@@ -8,20 +8,6 @@ using namespace pgpfa;
 
 namespace {
 
-constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
-
-// While it lives the library's GEMM launcher never cuts k (pgpfa_ctx::no_splitk; linalg.hip: gemm).  The number of k parts there follows the number of
-// tiles of a launch, i.e. - in the Poisson pass, the factorisation and the triangular inverse - the number of slots of the chunk: the bits of a trial's
-// square root would follow the chunk it is factored in.
-struct NoSplitK {
-  pgpfa_ctx* c;
-  bool was;
-  explicit NoSplitK(pgpfa_ctx* ctx) : c(ctx), was(ctx->no_splitk) { c->no_splitk = true; }
-  ~NoSplitK() { c->no_splitk = was; }
-  NoSplitK(const NoSplitK&) = delete;
-  NoSplitK& operator=(const NoSplitK&) = delete;
-};
-
 struct CovAtArgs {
   const std::vector<int>* trials;     // trial of every list position
   int S; const double* times; bool per_trial;

@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, copies; workspace.hip: arena and workspace plans, no kernel; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates; pfunc.hip: linear functionals of the latents).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -330,6 +330,8 @@ struct pgpfa_ctx {
   int covat_chunk = 0;                            // option covat_chunk_trials: the same for pgpfa_posterior_cov_at (covat.hip); no output depends on it
   int velat_chunk = 0;                            // option velat_chunk_trials: the same for pgpfa_posterior_velocity_at (velat.hip); no output depends on it
   int covat_block = 0;                            // option covat_block_times: query times per block of that call's right-hand sides (0: from the same bound); no output depends on it
+  int func_chunk = 0;                             // option func_chunk_trials: the same for pgpfa_posterior_functionals (pfunc.hip); no output depends on it
+  int func_block = 0;                             // option func_block_cols: functionals pushed through the square root per pass of that call (0: from the same bound); no output depends on it
   // predictive counts (pgpfa_count_probabilities / pgpfa_posterior_counts, rates.hip): the Gauss-Hermite nodes and log weights of the rule, computed on
   // the host and uploaded on first use and again when option counts_nodes has changed (counts_nodes_Q: the node count the device copy holds)
   int counts_chunk = 0;                           // option counts_chunk_trials: the same for pgpfa_posterior_counts; no output depends on it
@@ -468,6 +470,18 @@ struct DevBufs {                                              // device scratch 
   }
 };
 constexpr size_t QUERY_STAGE_BYTES = (size_t)256 << 20;      // bound on the device staging of one chunk of a query's trial list
+constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
+// While it lives the library's GEMM launcher never cuts k (pgpfa_ctx::no_splitk; linalg.hip: gemm).  The number of k parts there follows the number of
+// tiles of a launch, i.e. - in the Poisson pass, the factorisation and the triangular inverse - the number of slots of the chunk: the bits of a trial's
+// square root would follow the chunk it is factored in (covat.hip, pfunc.hip).
+struct NoSplitK {
+  pgpfa_ctx* c;
+  bool was;
+  explicit NoSplitK(pgpfa_ctx* ctx) : c(ctx), was(ctx->no_splitk) { c->no_splitk = true; }
+  ~NoSplitK() { c->no_splitk = was; }
+  NoSplitK(const NoSplitK&) = delete;
+  NoSplitK& operator=(const NoSplitK&) = delete;
+};
 // Trials per chunk of a list of n: the query's *_chunk_trials option when set, else as many as fit that bound at bytes_per_trial of staging
 // (0 bytes: the whole list), at least one; never more than cap (0: no cap).
 int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap = 0);

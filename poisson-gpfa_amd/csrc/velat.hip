@@ -9,7 +9,6 @@ using namespace pgpfa;
 namespace {
 
 constexpr size_t VELAT_LDS_MAX = (size_t)160 << 10;           // LDS of a CU: the row panel and the three planes of running sums have to fit
-constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
 
 struct VelArgs {
   const std::vector<int>* trials;     // trial of every list position

@@ -51,6 +51,7 @@ _SIGNATURES = {
     'pgpfa_posterior_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p],
     'pgpfa_posterior_cov_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int, c_double_p, c_double_p, c_double_p, c_double_p],
     'pgpfa_posterior_velocity_at': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int] + [c_double_p] * 5,
+    'pgpfa_posterior_functionals': [ct.c_void_p, ct.c_int, c_int32_p, ct.c_int, c_double_p, ct.c_int] + [c_double_p] * 3,
     'pgpfa_count_probabilities': [ct.c_void_p, ct.c_longlong, c_double_p, c_double_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p,
                                   c_int32_p, c_double_p, c_double_p],
     'pgpfa_posterior_counts': [ct.c_void_p, ct.c_int, c_int32_p, c_int32_p, ct.c_int, ct.c_double, ct.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p,
@@ -506,6 +507,27 @@ class Context:
         S = tt.shape[-1]
         out = {k: np.empty((n, self.p, S)) for k in keys if k in want}
         check(self.lib.pgpfa_posterior_velocity_at(self.h, n, iptr(ii), S, dptr(tt), per_trial, *[dptr(out[k]) if k in out else None for k in keys]))
+        return out
+
+    def posterior_functionals(self, weights, trials=None, want=('mean', 'var')):
+        """Joint posterior of linear functionals u_j . x of the latents of the listed trials (repeats allowed; include/pgpfa.h:
+        pgpfa_posterior_functionals).  weights: (J, p, T) - one set for all listed trials - or (n, J, p, T), one set per list entry.  want: any of
+        'mean' [n][J], 'var' [n][J] and 'cov' [n][J][J] (J <= 1024).  Returns a dict of exactly the arrays asked for."""
+        n, ii = self._n_idx(trials)
+        _check_outputs(want, ('mean', 'var', 'cov'))
+        ww = as_f64(weights)
+        if ww.ndim == 3 and ww.shape[1:] == (self.p, self.T):
+            per_trial = 0
+        elif ww.ndim == 4 and ww.shape[0] == n and ww.shape[2:] == (self.p, self.T):
+            per_trial = 1
+        else:
+            raise ValueError('weights must have shape (J, p, T) = (J, %d, %d) or (n, J, p, T) = (%d, J, %d, %d), got %s'
+                             % (self.p, self.T, n, self.p, self.T, ww.shape))
+        J = ww.shape[-3]
+        shapes = {'mean': (n, J), 'var': (n, J), 'cov': (n, J, J)}
+        out = {k: np.empty(shapes[k]) for k in shapes if k in want}
+        ptr = lambda k: dptr(out[k]) if k in out else None
+        check(self.lib.pgpfa_posterior_functionals(self.h, n, iptr(ii), J, dptr(ww), per_trial, ptr('mean'), ptr('var'), ptr('cov')))
         return out
 
     def _count_outputs(self, shape, counts, K, level, k_cap, want):

@@ -359,6 +359,23 @@ class PPGPFAfit():
         self.ratesAt = util.posteriorRatesAt(self.optimParams, self.experiment, times, **kw)
         return self.ratesAt
 
+    def posteriorFunctionals(self, weights, **kw):
+        """util.posteriorFunctionals at the fitted parameters -> self.functionals (a dict; weights and the keywords as there: infRes, trials,
+        level, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.functionals = util.posteriorFunctionals(self.optimParams, self.experiment, weights, **kw)
+        return self.functionals
+
+    def posteriorEpochs(self, epochs, **kw):
+        """util.posteriorEpochs at the fitted parameters -> self.epochs (a dict; epochs and the keywords as there: infRes, trials, align,
+        contrasts, conditions, level, forecast, want).  Without infRes= it runs one more Laplace E-step over all trials, so self.infRes is
+        copied to the host first."""
+        if kw.get('infRes') is None:
+            self._keep_inf_res()
+        self.epochs = util.posteriorEpochs(self.optimParams, self.experiment, epochs, **kw)
+        return self.epochs
+
     def extractTrajectories(self, method='laplace'):
         """One more E-step over all trials with the fitted parameters (reference engine.py:523-532)."""
         self._keep_inf_res()

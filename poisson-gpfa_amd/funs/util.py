@@ -588,6 +588,216 @@ def posteriorRatesAt(params, experiment, times, infRes=None, trials=None, condit
     return out
 
 
+# -- linear functionals of the latents: epoch means, contrasts, projections ------------------------------------
+_FUNC_KEYS = ('mean', 'var', 'sd', 'lower', 'upper', 'cov')
+
+
+def posteriorFunctionals(params, experiment, weights, infRes=None, trials=None, level=0.95, want=('mean', 'lower', 'upper')):
+    """The joint posterior of linear functionals u_j . x of the latents of the listed trials: the mean of a latent over an epoch, a contrast
+    between two epochs, the projection of a whole trajectory onto a decoding axis or a temporal template.  Exact - no samples - and without the
+    p T x p T covariance of a trial ever being formed (pgpfa_posterior_functionals): Cov(U^T x) = (M^T U)^T (M^T U) from the square root M the
+    sampler draws from.
+
+    weights: (J, xdim, T) - one set for all listed trials - or (n, J, xdim, T), one set per listed trial; T is the session's bin count (the
+    longest trial).  Behind a shorter trial's own T_r bins the posterior is the GP's forecast, and weights there count it in.
+    infRes, trials: as for posteriorAt; the posterior has to be one an E-step of this session wrote.
+    want: any of 'mean', 'var', 'sd', 'lower' / 'upper' (mean -+ z sd, the central `level` band) - (n, J) arrays - and 'cov', the joint (n, J, J)
+    covariance of the functionals (J <= 1024; without it J is not limited and no J x J plane is formed).  Returns a dict of the asked keys."""
+    want = tuple(want)
+    unknown = [k for k in want if k not in _FUNC_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_FUNC_KEYS)))
+    if not want:
+        raise ValueError('nothing asked for: want is empty')
+    z = _band_z(level)
+    ww = np.ascontiguousarray(weights, dtype=np.float64)
+    if ww.ndim not in (3, 4) or ww.shape[-3] < 1:
+        raise ValueError('weights: shape (J, xdim, T) or (n, J, xdim, T) with J >= 1 expected, got %s' % (ww.shape,))
+    if not np.all(np.isfinite(ww)):                    # (before the session is touched: nothing reaches the device)
+        raise ValueError('weights: entry %s is not finite' % (tuple(int(i) for i in np.argwhere(~np.isfinite(ww))[0]),))
+    sess, idx = _resident_posterior('posteriorFunctionals', params, experiment, infRes, trials, set_params=True)
+    xdim = int(np.shape(params['C'])[1])
+    if ww.shape[-2:] != (xdim, sess.T) or (ww.ndim == 4 and ww.shape[0] != idx.size):
+        raise ValueError('weights: (J, %d, %d) or one set per listed trial, (%d, J, %d, %d), expected, got %s'
+                         % (xdim, sess.T, idx.size, xdim, sess.T, ww.shape))
+    return _functional_bands(sess.ctx, ww, idx, z, want)
+
+
+def _functional_bands(ctx, ww, idx, z, want):
+    """The asked keys of _FUNC_KEYS from one device call that asks for exactly what they need."""
+    need_var = any(k in want for k in ('var', 'sd', 'lower', 'upper'))
+    need_mean = any(k in want for k in ('mean', 'lower', 'upper'))
+    ask = (('mean',) if need_mean else ()) + (('var',) if need_var else ()) + (('cov',) if 'cov' in want else ())
+    dev = ctx.posterior_functionals(ww, idx, want=ask)
+    sd = np.sqrt(dev['var']) if any(k in want for k in ('sd', 'lower', 'upper')) else None
+    made = {'mean': lambda: dev['mean'], 'var': lambda: dev['var'], 'sd': lambda: sd, 'lower': lambda: dev['mean'] - z * sd,
+            'upper': lambda: dev['mean'] + z * sd, 'cov': lambda: dev['cov']}
+    return {k: made[k]() for k in want}
+
+
+_EPOCH_KEYS = ('mean', 'var', 'lower', 'upper', 'cov', 'contrast', 'contrastVar', 'contrastLower', 'contrastUpper', 'eta', 'etaVar', 'etaLower', 'etaUpper')
+
+
+def _experiment_bins(experiment):
+    """(T, lengths): the bin count of the experiment's session - the longest trial of the experiment, or of the one it was sub-sampled from - and
+    the bin count of every trial of experiment.data.  Host arithmetic only."""
+    root = getattr(experiment, '_pgpfa_parent', None) if hasattr(experiment, 'batchTrIdx') else None
+    root = experiment if root is None else root
+    T = max(int(np.shape(tr['Y'])[1]) for tr in root.data)
+    return T, np.array([int(np.shape(tr['Y'])[1]) for tr in experiment.data], dtype=np.int64)
+
+
+def _epoch_bins(start, stop, binSize):
+    """The grid bins j (any integer) with start <= j binSize < stop, by exactly that comparison."""
+    jj = np.arange(int(np.floor(start / binSize)) - 1, int(np.ceil(stop / binSize)) + 2, dtype=np.int64)
+    tj = jj * binSize
+    return jj[(tj >= start) & (tj < stop)]
+
+
+def _epoch_windows(epochs, binSize, T, lengths, pos, align, forecast):
+    """Window weights of posteriorEpochs: (E, T) without `align`, (n, E, T) with - uniform 1 / |B| over the bins B of every window, 0 elsewhere.
+    lengths: bin count of every listed trial; pos: its position in experiment.data (for the messages).  Raises ValueError on an epoch that is not
+    a (start, stop) pair of finite numbers, an empty window, one that leaves [0, T) and - unless `forecast` - one that passes a listed trial's
+    own length."""
+    ep = np.asarray(epochs, dtype=np.float64)
+    if ep.ndim != 2 or ep.shape[1] != 2 or ep.shape[0] < 1:
+        raise ValueError('epochs: a list of (start_ms, stop_ms) pairs expected, got shape %s' % (ep.shape,))
+    if not np.all(np.isfinite(ep)):
+        raise ValueError('epochs: window %d is not finite' % int(np.argwhere(~np.isfinite(ep))[0][0]))
+    n, E = len(lengths), ep.shape[0]
+    shift = None
+    if align is not None:
+        shift = np.asarray(align, dtype=np.float64).reshape(-1)
+        if shift.shape != (n,):
+            raise ValueError('align: one event time in ms per listed trial expected (%d), got %d' % (n, shift.size))
+        if not np.all(np.isfinite(shift)):
+            raise ValueError('align: the event time of list entry %d is not finite' % int(np.argwhere(~np.isfinite(shift))[0][0]))
+    W = np.zeros((n if shift is not None else 1, E, T))
+    for i in range(W.shape[0]):
+        off = 0.0 if shift is None else float(shift[i])
+        who = '' if shift is None else ' of list entry %d (trial %d, aligned to %g ms)' % (i, int(pos[i]), off)
+        for e in range(E):
+            bins = _epoch_bins(ep[e, 0] + off, ep[e, 1] + off, binSize)
+            if bins.size == 0:
+                raise ValueError('epochs: window %d%s, [%g, %g) ms, holds no bin (bin j sits at j * %g ms)' % (e, who, ep[e, 0] + off, ep[e, 1] + off, binSize))
+            if bins[0] < 0 or bins[-1] >= T:
+                raise ValueError('epochs: window %d%s, bins %d .. %d, leaves the grid [0, %d)' % (e, who, bins[0], bins[-1], T))
+            if not forecast:
+                short = [j for j in (range(n) if shift is None else [i]) if bins[-1] >= lengths[j]]
+                if short:
+                    raise ValueError('epochs: window %d, bins %d .. %d, passes the %d bins of trial %d (list entry %d); forecast=True takes the '
+                                     "GP's forecast there" % (e, bins[0], bins[-1], lengths[short[0]], int(pos[short[0]]), short[0]))
+            W[i, e, bins] = 1.0 / bins.size
+    return W if shift is not None else W[0]
+
+
+def _latent_functionals(W, xdim):
+    """Window weights (..., E, T) as functionals of the latent vector, one per (window, latent): (..., E * xdim, xdim, T), window-major."""
+    eye = np.eye(xdim)
+    U = W[..., :, None, None, :] * eye[:, :, None]                     # (..., E, xdim, xdim, T)
+    return np.ascontiguousarray(U.reshape(W.shape[:-2] + (W.shape[-2] * xdim, xdim, W.shape[-1])))
+
+
+def posteriorEpochs(params, experiment, epochs, infRes=None, trials=None, align=None, contrasts=None, conditions=None, level=0.95, forecast=False,
+                    want=('mean', 'lower', 'upper')):
+    """The mean of every latent over task epochs, with credible bands that account for the correlation between bins, the change between two
+    epochs, and the window-averaged log rate of every neuron: exact posteriors of linear functionals (posteriorFunctionals).
+
+    epochs: a list of (start_ms, stop_ms); the weights of an epoch are uniform 1 / |B| over the grid bins j with start <= j * binSize < stop.
+    align: one event time in ms per listed trial; the windows are then shifted by it, trial by trial.  contrasts: a list of (a, b) epoch indices,
+    for xbar(b) - xbar(a) per latent - functionals of their own, so the band carries the correlation between the two epochs.
+    conditions: one integer label per listed trial.  forecast: allow a window to pass a trial's own T_r bins, where the posterior is the GP's
+    forecast.  infRes, trials: as for posteriorFunctionals.
+    want: any of 'mean', 'var', 'lower', 'upper' - (n, E, xdim) - 'cov', the joint (n, E * xdim, E * xdim) covariance of the epoch means
+    (epoch-major), 'eta', 'etaVar', 'etaLower', 'etaUpper' - (n, E, ydim): the window-averaged log rate d_i + c_i . xbar of every neuron, by the
+    call's diagonal-only path, so no plane over the E * ydim functionals is formed - and, with `contrasts`, 'contrast', 'contrastVar',
+    'contrastLower', 'contrastUpper', (n, len(contrasts), xdim); `contrasts` alone adds the three keys 'contrast', 'contrastLower' and
+    'contrastUpper' to want.  With `conditions` the dict also holds 'condition_mean' (G, E, xdim), 'condition_contrast' (G, len(contrasts),
+    xdim) when there are contrasts, 'condition_count' (G) and 'condition_labels' (G): the plain means over a condition's listed trials.
+    Raises ValueError before anything reaches the device on an empty window, a window that leaves [0, T), one that passes a trial's own length
+    while forecast=False (naming the trial), and on contrast indices out of range."""
+    want = tuple(want)
+    unknown = [k for k in want if k not in _EPOCH_KEYS]
+    if unknown:
+        raise ValueError('want: unknown key(s) %s; known: %s' % (unknown, list(_EPOCH_KEYS)))
+    z = _band_z(level)
+    T, all_lengths = _experiment_bins(experiment)
+    pos = np.arange(len(experiment.data)) if trials is None else np.asarray(trials, dtype=np.int64).reshape(-1)
+    if pos.size == 0:
+        raise ValueError('empty trial list')
+    if np.any(pos < 0) or np.any(pos >= len(experiment.data)):
+        raise ValueError('trials: positions in experiment.data expected (0 .. %d)' % (len(experiment.data) - 1))
+    binSize = float(experiment.binSize)
+    W = _epoch_windows(epochs, binSize, T, all_lengths[pos], pos, align, forecast)
+    E = W.shape[-2]
+    pairs = np.zeros((0, 2), dtype=np.int64)
+    if contrasts is not None:
+        cc = np.asarray(contrasts)
+        if cc.ndim != 2 or cc.shape[1] != 2 or cc.shape[0] < 1 or not np.issubdtype(cc.dtype, np.integer):
+            raise ValueError('contrasts: a list of (a, b) epoch indices expected')
+        pairs = cc.astype(np.int64)
+        if np.any(pairs < 0) or np.any(pairs >= E):
+            bad = pairs[np.argwhere((pairs < 0) | (pairs >= E))[0][0]]
+            raise ValueError('contrasts: (%d, %d) names an epoch outside 0 .. %d' % (bad[0], bad[1], E - 1))
+        want = want + tuple(k for k in ('contrast', 'contrastLower', 'contrastUpper') if k not in want)
+    elif any(k.startswith('contrast') for k in want):
+        raise ValueError("want: %s needs contrasts=[(a, b), ...]" % [k for k in want if k.startswith('contrast')])
+    if not want and conditions is None:
+        raise ValueError('nothing asked for: want is empty and there are no conditions')
+    labels, group = (None, None) if conditions is None else _condition_groups(conditions, pos.size)
+    sess, idx = _resident_posterior('posteriorEpochs', params, experiment, infRes, trials, set_params=True)
+    if sess.T != T:
+        raise ValueError('the session holds %d bins, the experiment %d' % (sess.T, T))
+    C = np.asarray(params['C'], dtype=np.float64)
+    d = np.asarray(params['d'], dtype=np.float64).reshape(-1)
+    ydim, xdim = C.shape
+    nC = pairs.shape[0]
+    out = {}
+    # epoch means and contrasts: one call, the contrasts behind the epochs
+    lat_keys = {'mean': 'mean', 'var': 'var', 'lower': 'lower', 'upper': 'upper', 'cov': 'cov', 'contrast': 'mean', 'contrastVar': 'var',
+                'contrastLower': 'lower', 'contrastUpper': 'upper'}
+    ask = tuple(sorted(set(lat_keys[k] for k in want if k in lat_keys) | ({'mean'} if labels is not None else set())))
+    if ask:
+        Wall = W if nC == 0 else np.concatenate([W, W[..., pairs[:, 1], :] - W[..., pairs[:, 0], :]], axis=-2)
+        got = _functional_bands(sess.ctx, _latent_functionals(Wall, xdim), idx, z, ask)
+        n = idx.size
+        for k in want:
+            if k == 'cov':
+                out[k] = np.ascontiguousarray(got['cov'][:, :E * xdim, :E * xdim])
+            elif k in lat_keys:
+                full = got[lat_keys[k]].reshape(n, E + nC, xdim)
+                out[k] = np.ascontiguousarray(full[:, E:] if k.startswith('contrast') else full[:, :E])
+        if labels is not None:
+            full = got['mean'].reshape(n, E + nC, xdim)
+            cnt = np.bincount(group, minlength=len(labels))
+            tot = np.zeros((len(labels), E + nC, xdim))
+            for i in range(n):                                         # in list order: reproducible
+                tot[group[i]] += full[i]
+            avg = tot / cnt[:, None, None]
+            out['condition_mean'] = avg[:, :E]
+            if nC:
+                out['condition_contrast'] = avg[:, E:]
+            out['condition_count'] = cnt
+            out['condition_labels'] = labels
+    # window-averaged log rates: E * ydim functionals with weights C[i, k] / |B|, variances alone
+    eta_keys = {'eta': 'mean', 'etaVar': 'var', 'etaLower': 'lower', 'etaUpper': 'upper'}
+    ask = tuple(sorted(set(eta_keys[k] for k in want if k in eta_keys)))
+    if ask:
+        U = W[..., :, None, None, :] * C[:, :, None]                   # (..., E, ydim, xdim, T)
+        U = np.ascontiguousarray(U.reshape(W.shape[:-2] + (E * ydim, xdim, T)))
+        need_var = any(k in ask for k in ('var', 'lower', 'upper'))
+        need_mean = any(k in ask for k in ('mean', 'lower', 'upper'))
+        got = sess.ctx.posterior_functionals(U, idx, want=(('mean',) if need_mean else ()) + (('var',) if need_var else ()))
+        eta = got['mean'].reshape(idx.size, E, ydim) + d[None, None, :] if need_mean else None
+        var = got['var'].reshape(idx.size, E, ydim) if need_var else None
+        sd = np.sqrt(var) if ('lower' in ask or 'upper' in ask) else None
+        made = {'eta': lambda: eta, 'etaVar': lambda: var, 'etaLower': lambda: eta - z * sd, 'etaUpper': lambda: eta + z * sd}
+        for k in want:
+            if k in eta_keys:
+                out[k] = made[k]()
+    return out
+
+
 # -- co-smoothing: held-out neurons predicted from the others -------------------------------------------------
 def coSmoothing(params, experiment, heldOut, trials=None, predictive=False):
     """Predict the neurons `heldOut` on the listed trials from the trials' other neurons and score the prediction: the held-out neurons are

@@ -1597,35 +1597,6 @@ int with_snapshot(pgpfa_ctx* c, int id, const std::function<int()>& fn) {
   return rc2;
 }
 
-int for_snapshot_groups(pgpfa_ctx* c, const std::vector<int>& trials, const std::function<int(const std::vector<int>& positions, bool dual)>& fn) {
-  std::map<std::pair<int, int>, std::vector<int>> groups;
-  for (size_t i = 0; i < trials.size(); ++i) groups[std::make_pair(c->trial_snap[trials[i]], (int)c->trial_dual[trials[i]])].push_back((int)i);
-  for (auto& kv : groups) {
-    const std::vector<int>& pos = kv.second;
-    const bool dual = kv.first.second != 0;
-    CHK(with_snapshot(c, kv.first.first, [&]() { return fn(pos, dual); }));
-  }
-  return 0;
-}
-
-int require_resident(const pgpfa_ctx* c, const std::vector<int>& trials, ResidentKind kind) {
-  for (int t : trials) {
-    if (kind == RESIDENT_BLOCKS && c->mode_serial[t] < 0 && c->trial_snap[t] < 0 && !c->vsmgp_ok[t])
-      return fail("no posterior for trial %d: neither an E-step nor pgpfa_set_posterior has written one since its counts were uploaded", t);
-    if (kind == RESIDENT_SAMPLABLE && (c->trial_snap[t] < 0 || (c->trial_dual[t] && !c->lam_keep)))
-      return fail("no posterior to sample for trial %d: no E-step has written one since its counts were uploaded (a posterior given by pgpfa_set_posterior "
-                  "cannot be sampled, only its blocks are known)", t);
-  }
-  return 0;
-}
-
-int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap) {
-  size_t chunk = cap > 0 ? std::min(n, cap) : n;
-  if (option > 0) chunk = std::min(chunk, (size_t)option);
-  else if (bytes_per_trial > 0) chunk = std::min(chunk, std::max<size_t>(1, QUERY_STAGE_BYTES / bytes_per_trial));
-  return (int)chunk;
-}
-
 int remember_trials(pgpfa_ctx* c, const std::vector<int>& v) {
   c->last_trials_h = v;
   CHK(upload_list(c, c->last_trials, v));

@@ -1,5 +1,5 @@
 // libpgpfa_hip.so - cov.hip (one translation unit of the C-ABI library; shared declarations: ctx.h)
-#include "ctx.h"
+#include "query.h"
 #include "model.h"
 #include "split.h"
 #include "ytmix.h"

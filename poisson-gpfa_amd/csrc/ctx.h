@@ -1,7 +1,7 @@
 // Shared declarations of the translation units of libpgpfa_hip.so: the context (one GPU, one stream, all resident state), error / check
 // macros, and the host-side helpers that cross translation units.  Kernels live in the kernel headers; a translation unit includes only
 // the ones it launches (core.hip: context, copies; workspace.hip: arena and workspace plans, no kernel; linalg.hip: GEMM / factor; estep.hip: Newton-PCG E-step; cov.hip:
-// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates; pfunc.hip: linear functionals of the latents).
+// covariance engines; mstep.hip; dual.hip; misc.hip: comm, generator, count moments; query.hip: what the posterior queries share (query.h), no kernel; rates.hip: posterior firing rates; psample.hip: joint posterior samples; interp.hip: the posterior off the bin grid; covat.hip: its cross-latent covariance and rates; pfunc.hip: linear functionals of the latents).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -452,49 +452,6 @@ struct Trials {
   std::vector<int> v;
 };
 
-// ---- what the posterior queries share (pgpfa_posterior_rates / _sample / _at: rates.hip, psample.hip, interp.hip) -------------------------------
-struct DevBufs {                                              // device scratch of one call of `entry`: freed on every way out
-  const char* entry;
-  std::vector<void*> v;
-  explicit DevBufs(const char* entry_point) : entry(entry_point) {}
-  DevBufs(const DevBufs&) = delete;
-  DevBufs& operator=(const DevBufs&) = delete;
-  ~DevBufs() { for (void* p : v) hipFree(p); }
-  template <typename T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail("%s: hipMalloc(%zu bytes) failed: %s", entry, count * sizeof(T), hipGetErrorString(e)); }
-    v.push_back(p);
-    *out = reinterpret_cast<T*>(p);
-    return 0;
-  }
-};
-constexpr size_t QUERY_STAGE_BYTES = (size_t)256 << 20;      // bound on the device staging of one chunk of a query's trial list
-constexpr int GEMM_ROW_SLACK = 128;                          // the GEMM stages whole row tiles of its first operand: rows past M are read, never used
-// While it lives the library's GEMM launcher never cuts k (pgpfa_ctx::no_splitk; linalg.hip: gemm).  The number of k parts there follows the number of
-// tiles of a launch, i.e. - in the Poisson pass, the factorisation and the triangular inverse - the number of slots of the chunk: the bits of a trial's
-// square root would follow the chunk it is factored in (covat.hip, pfunc.hip).
-struct NoSplitK {
-  pgpfa_ctx* c;
-  bool was;
-  explicit NoSplitK(pgpfa_ctx* ctx) : c(ctx), was(ctx->no_splitk) { c->no_splitk = true; }
-  ~NoSplitK() { c->no_splitk = was; }
-  NoSplitK(const NoSplitK&) = delete;
-  NoSplitK& operator=(const NoSplitK&) = delete;
-};
-// Trials per chunk of a list of n: the query's *_chunk_trials option when set, else as many as fit that bound at bytes_per_trial of staging
-// (0 bytes: the whole list), at least one; never more than cap (0: no cap).
-int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap = 0);
-// A posterior is resident for a trial once a Laplace E-step (mode_serial), pgpfa_dual_finalize (its parameter snapshot) or pgpfa_set_posterior (which
-// marks the blocks it uploaded, or left, as the resident ones) has written it; new counts or lengths clear all three: RESIDENT_BLOCKS.  One that can
-// be sampled is one an E-step or pgpfa_dual_finalize of this context wrote - of an uploaded one only blocks are known -, with the kept lambda if it is
-// variational: RESIDENT_SAMPLABLE.  Fails naming the first listed trial that has none.
-enum ResidentKind { RESIDENT_BLOCKS, RESIDENT_SAMPLABLE };
-int require_resident(const pgpfa_ctx* c, const std::vector<int>& trials, ResidentKind kind);
-// fn(positions, dual) for the positions of `trials` that share a (parameter snapshot, Laplace / variational) pair, in the order of the pairs, under that
-// snapshot's parameters (with_snapshot): blocks rebuilt on demand and queries are those of every trial's OWN E-step
-int for_snapshot_groups(pgpfa_ctx* c, const std::vector<int>& trials, const std::function<int(const std::vector<int>& positions, bool dual)>& fn);
-
 // Leave-one-neuron-out job riding on the E-step machinery: item i is (trial tr.v[i], held-out neuron mask[i]); only the
 // mode is found (no covariance blocks, nothing written to the per-trial state), then the held-out neuron is predicted.
 struct LooJob {
@@ -619,20 +576,6 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
 int var_offsets(pgpfa_ctx* c, int nb, double* out);
 int check_distinct(const std::vector<int>& v);
 int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out);
-// interp.hip: kx and A = Kinv kx of `grids` time grids whose times are on the device ([grid][p][T16][Spad], interp.h), as pgpfa_posterior_at forms them
-int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A);
-// the GEMM half of interp_weights: A = Kinv rhs for `grids` right-hand sides in the layout of kx (two-level batch, fixed 64-tile, off split-K)
-int interp_solve(pgpfa_ctx* c, const double* rhs, int grids, int Spad, int T16, double* A);
-struct MarkKeeper {                                           // the resident marks of post_vsmGP are what they were when the call returns
-  pgpfa_ctx* c;
-  std::vector<std::pair<int, char>> saved;
-  ~MarkKeeper() { for (auto& kv : saved) c->vsmgp_ok[kv.first] = kv.second; }
-};
-// the T x T blocks of the trials `tos` (one snapshot) made resident for a query: the buffer, blocks rebuilt on demand under the sum-only plan with
-// post_vsm of the rebuilt trials set aside (scratch from `dev`) and put back, the marks restored when `keep` goes out of scope
-int interp_blocks_resident(pgpfa_ctx* c, DevBufs& dev, MarkKeeper& keep, const std::vector<int>& tos);
-// rates.hip: rates_kernel on staged planes (pgpfa_posterior_cov_at)
-int rates_staged_planes(pgpfa_ctx* c, const char* entry, const double* mean, const double* cov, int Tplane, int nslots, double* eta, double* var);
 // misc.hip
 int allreduce_dev(pgpfa_ctx* c, double* buf, size_t count);
 

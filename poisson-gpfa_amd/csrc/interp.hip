@@ -1,29 +1,16 @@
-// libpgpfa_hip.so - interp.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): the latent posterior at arbitrary time
+// libpgpfa_hip.so - interp.hip (one translation unit of the C-ABI library; shared declarations: ctx.h, query.h): the latent posterior at arbitrary time
 // points (pgpfa_posterior_at)
-#include "ctx.h"
+#include "query.h"
 #include "interp.h"
 
 using namespace pgpfa;
 
-namespace {
-
-constexpr size_t INTERP_LDS_MAX = (size_t)160 << 10;          // LDS of a CU: the row panel of interp_var_kernel has to fit
-
-struct AtArgs {
-  const std::vector<int>* trials;     // trial of every list position
-  int S; const double* times; bool per_trial;
-  double* mean; double* var;
-};
-
-// kx and A = Kinv kx of `grids` time grids whose times are on the device
-int weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A) {
+int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A) {
   const int p = c->p, T = c->T;
   hipLaunchKernelGGL(interp_cross_kernel, dim3(T16, p, grids), dim3(256), 0, c->st, d_times, c->tau, c->bin, c->eps, T, T16, S, Spad, p, kx);
   HIPC(hipGetLastError());
   return interp_solve(c, kx, grids, Spad, T16, A);
 }
-
-}  // namespace
 
 int interp_solve(pgpfa_ctx* c, const double* rhs, int grids, int Spad, int T16, double* A) {
   const int p = c->p, T = c->T;
@@ -67,15 +54,20 @@ int interp_blocks_resident(pgpfa_ctx* c, DevBufs& dev, MarkKeeper& keep, const s
 
 namespace {
 
+struct AtArgs {
+  const std::vector<int>* trials;     // trial of every list position
+  int S; const double* times; bool per_trial;
+  double* mean; double* var;
+};
+
 // the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
 int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
   const int p = c->p, T = c->T, S = a.S;
   const int T4 = round_up(T, 4), T16 = round_up(T, 16), Spad = round_up(S, 16), VS = interp_row_stride(T4);
   const size_t lds = ((size_t)16 * VS + std::min(Spad, INTERP_SBLK)) * sizeof(double);
-  if (a.var && lds > INTERP_LDS_MAX) return fail("pgpfa_posterior_at: a row panel of %d bins does not fit the LDS of a compute unit (%zu bytes)", T, lds);
+  if (a.var && lds > QUERY_LDS_MAX) return fail("pgpfa_posterior_at: a row panel of %d bins does not fit the LDS of a compute unit (%zu bytes)", T, lds);
   const int N = (int)pos.size();
-  std::vector<int> tos(N);
-  for (int i = 0; i < N; ++i) tos[i] = (*a.trials)[pos[i]];
+  const std::vector<int> tos = group_trials(*a.trials, pos);
 
   DevBufs dev("pgpfa_posterior_at");
   MarkKeeper keep{c, {}};
@@ -87,36 +79,30 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
   const int chunk = query_chunk((size_t)N, c->interp_chunk, per_trial);
   const int grids = a.per_trial ? chunk : 1;
 
-  double *d_times = nullptr, *d_kx = nullptr, *d_A = nullptr, *d_mean = nullptr, *d_var = nullptr;
+  TimeGrids tg{c, a.times, S};
+  double *d_kx = nullptr, *d_A = nullptr, *d_mean = nullptr, *d_var = nullptr;
   int* d_trial = nullptr;
-  CHK(dev.get(&d_times, (size_t)grids * S));
-  CHK(dev.get(&d_kx, (size_t)grids * slab + GEMM_ROW_SLACK));
-  CHK(dev.get(&d_A, (size_t)grids * slab + GEMM_ROW_SLACK));
+  CHK(tg.alloc(dev, grids));
+  CHK(weight_slabs(c, dev, (size_t)grids * slab + GEMM_ROW_SLACK, &d_kx, &d_A));
   CHK(dev.get(&d_trial, (size_t)N));
   if (a.mean) CHK(dev.get(&d_mean, (size_t)chunk * p * Spad));
   if (a.var) CHK(dev.get(&d_var, (size_t)chunk * p * Spad));
-  HIPC(hipMemsetAsync(d_kx, 0, ((size_t)grids * slab + GEMM_ROW_SLACK) * sizeof(double), c->st));
-  HIPC(hipMemsetAsync(d_A, 0, ((size_t)grids * slab + GEMM_ROW_SLACK) * sizeof(double), c->st));     // rows t >= T stay zero for the whole call
   HIPC(hipMemcpyAsync(d_trial, tos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->st));
   if (!a.per_trial) {
-    HIPC(hipMemcpyAsync(d_times, a.times, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->st));
-    CHK(weights(c, d_times, 1, S, Spad, T16, d_kx, d_A));   // once per snapshot group, not per trial
+    CHK(tg.upload_shared());
+    CHK(interp_weights(c, tg.d, 1, S, Spad, T16, d_kx, d_A));   // once per snapshot group, not per trial
   }
-  if (a.var && lds > ((size_t)48 << 10))
-    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(interp_var_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (a.var) CHK(lds_opt_in(reinterpret_cast<const void*>(interp_var_kernel), lds));
 
   InterpP k{};
   k.vsmgp = c->vsmgp; k.Xmode = c->Xmode; k.A = d_A; k.kx = d_kx; k.mean = d_mean; k.var = d_var;
   k.sG = a.per_trial ? (long long)slab : 0;
   k.p = p; k.T = T; k.T4 = T4; k.T16 = T16; k.Spad = Spad; k.VS = VS;
-  std::vector<double> h_times;
   for (int c0 = 0; c0 < N; c0 += chunk) {
     const int nc = std::min(chunk, N - c0);
     if (a.per_trial) {
-      h_times.resize((size_t)nc * S);
-      for (int i = 0; i < nc; ++i) std::copy(a.times + (size_t)pos[c0 + i] * S, a.times + (size_t)(pos[c0 + i] + 1) * S, h_times.begin() + (size_t)i * S);
-      HIPC(hipMemcpyAsync(d_times, h_times.data(), h_times.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
-      CHK(weights(c, d_times, nc, S, Spad, T16, d_kx, d_A));
+      CHK(tg.upload_listed(pos.data() + c0, nc));
+      CHK(interp_weights(c, tg.d, nc, S, Spad, T16, d_kx, d_A));
     }
     k.ptrial = d_trial + c0;
     if (a.mean) hipLaunchKernelGGL(interp_mean_kernel, dim3((Spad + 255) / 256, p, nc), dim3(256), 0, c->st, k);
@@ -125,12 +111,8 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
     // results of the chunk, by list position
     for (int i = 0; i < nc; ++i) {
       const size_t ps = (size_t)pos[c0 + i];
-      if (a.mean)
-        HIPC(hipMemcpy2DAsync(a.mean + ps * p * S, (size_t)S * sizeof(double), d_mean + (size_t)i * p * Spad, (size_t)Spad * sizeof(double), (size_t)S * sizeof(double), p,
-                              hipMemcpyDeviceToHost, c->st));
-      if (a.var)
-        HIPC(hipMemcpy2DAsync(a.var + ps * p * S, (size_t)S * sizeof(double), d_var + (size_t)i * p * Spad, (size_t)Spad * sizeof(double), (size_t)S * sizeof(double), p,
-                              hipMemcpyDeviceToHost, c->st));
+      if (a.mean) CHK(download_plane(c, a.mean + ps * p * S, d_mean + (size_t)i * p * Spad, p, S, Spad));
+      if (a.var) CHK(download_plane(c, a.var + ps * p * S, d_var + (size_t)i * p * Spad, p, S, Spad));
     }
     HIPC(hipStreamSynchronize(c->st));                         // the staging is reused by the next chunk
     HIPC(hipGetLastError());
@@ -140,10 +122,6 @@ int at_group(pgpfa_ctx* c, const AtArgs& a, const std::vector<int>& pos) {
 
 }  // namespace
 
-int interp_weights(pgpfa_ctx* c, const double* d_times, int grids, int S, int Spad, int T16, double* kx, double* A) {
-  return weights(c, d_times, grids, S, Spad, T16, kx, A);
-}
-
 int pgpfa_posterior_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, const double* times_ms, int per_trial, double* mean, double* var) {
   if (!c) return fail("null context");
   if (S < 1) return fail("pgpfa_posterior_at: S = %d, at least one query time is needed", S);
@@ -151,21 +129,8 @@ int pgpfa_posterior_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, const dou
   if (!times_ms) return fail("pgpfa_posterior_at: times_ms is NULL");
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
-  const int N = (int)tr.v.size();
-  for (int i = 0; i < (per_trial ? N : 1); ++i)
-    for (int s = 0; s < S; ++s)
-      if (!std::isfinite(times_ms[(size_t)i * S + s])) {
-        if (per_trial) return fail("pgpfa_posterior_at: query time %d of list entry %d (trial %d) is not finite", s, i, tr.v[i]);
-        return fail("pgpfa_posterior_at: query time %d is not finite", s);
-      }
-  if (!c->have_params) return fail("set_params has not been called");
-  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
-  HIPC(hipSetDevice(c->device));
-  CHK(require_resident(c, tr.v, RESIDENT_BLOCKS));
-  for (int t : tr.v)
-    if (c->trial_dual[t] && c->live.length(t) < c->T)
-      return fail("the variational posterior of trial %d covers %d of %d bins: its jitter comes from the trial's own %d-bin Gram inverse, so the padded grid "
-                  "does not carry its prior conditional; pgpfa_posterior_at refuses rather than approximates", t, c->live.length(t), c->T, c->live.length(t));
+  CHK(check_query_times("pgpfa_posterior_at", times_ms, S, per_trial != 0, tr.v));
+  CHK(query_gate(c, "pgpfa_posterior_at", tr.v));
   AtArgs a{};
   a.trials = &tr.v; a.S = S; a.times = times_ms; a.per_trial = per_trial != 0; a.mean = mean; a.var = var;
   return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool) { return at_group(c, a, pos); });

@@ -1,6 +1,6 @@
-// libpgpfa_hip.so - pfunc.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): the joint posterior of linear functionals of a
+// libpgpfa_hip.so - pfunc.hip (one translation unit of the C-ABI library; shared declarations: ctx.h, query.h): the joint posterior of linear functionals of a
 // trial's latents - epoch means, contrasts, projections (pgpfa_posterior_functionals)
-#include "ctx.h"
+#include "query.h"
 #include "pfunc.h"
 
 using namespace pgpfa;
@@ -16,29 +16,21 @@ struct PFuncArgs {
 // the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
 int pfunc_group(pgpfa_ctx* c, const PFuncArgs& a, const std::vector<int>& pos, bool dual) {
   const bool want_root = a.var || a.cov, want_cov = a.cov != nullptr;
-  if (want_root) {
-    CHK(ready_estep(c, dual ? c->dual_lowrank : true));
-    if (dual) CHK(ensure_lambda(c));
-  }
+  if (want_root) CHK(ready_root(c, dual));
   const int p = c->p, T = c->T, J = a.J;
   const bool lr = want_root && c->plan_lowrank;
   const int T16 = round_up(T, 16), Jpad = round_up(J, 16);
   const int N = (int)pos.size();
-  std::vector<int> tos(N);
-  for (int i = 0; i < N; ++i) tos[i] = (*a.trials)[pos[i]];
+  const std::vector<int> tos = group_trials(*a.trials, pos);
 
   // The functionals go through the root in blocks of JB columns.  With the J x J plane asked for the staging holds all Jpad columns of a trial - every
   // pair of columns meets in the Gram - and a block is a column range of it; without, the staging is one block wide and is reused block after block.
-  const int rpad = lr ? c->rpad : 0, npad = c->npad;
+  const int npad = c->npad;
+  RootStage root(c, lr);
   const size_t urows = lr ? (size_t)p * T16 : (size_t)npad;                   // rows of the staged weights
-  const size_t q_rows = !want_root ? 0 : (lr ? (size_t)rpad : (size_t)npad);
-  const size_t rows_stage = urows + (lr ? (size_t)p * T16 + 2 * (size_t)rpad : q_rows);
-  int JB = Jpad;
-  if (c->func_block > 0) JB = std::min(Jpad, round_up(c->func_block, 16));
-  else {
-    const size_t fit = QUERY_STAGE_BYTES / 8 / (rows_stage * sizeof(double));   // columns per block that leave room for eight trials in a chunk
-    JB = (int)std::min<size_t>((size_t)Jpad, std::max<size_t>(16, fit / 16 * 16));
-  }
+  const size_t q_rows = want_root ? root.q_rows : 0;
+  const size_t rows_stage = urows + (lr ? (size_t)p * T16 + 2 * q_rows : q_rows);
+  const int JB = plan::query_block_cols(c->func_block, Jpad, rows_stage * sizeof(double), QUERY_STAGE_BYTES);
   const int JW = want_cov ? Jpad : JB;
   const bool restage = !want_cov && JB < Jpad;                                  // the weights of every block are staged when its turn comes
   const size_t planes = (a.mean ? (size_t)J : 0) + (want_root ? (size_t)J : 0) + (want_cov ? (size_t)J * J : 0);
@@ -47,7 +39,7 @@ int pfunc_group(pgpfa_ctx* c, const PFuncArgs& a, const std::vector<int>& pos, b
   const int sets = a.per_trial ? chunk : 1;
 
   DevBufs dev("pgpfa_posterior_functionals");
-  double *d_U = nullptr, *d_V = nullptr, *d_W = nullptr, *d_Q = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_cov = nullptr;
+  double *d_U = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_cov = nullptr;
   int* d_trial = nullptr;
   const size_t u_len = (size_t)sets * urows * JW + GEMM_ROW_SLACK;
   CHK(dev.get(&d_U, u_len));
@@ -56,21 +48,10 @@ int pfunc_group(pgpfa_ctx* c, const PFuncArgs& a, const std::vector<int>& pos, b
   if (want_root) CHK(dev.get(&d_var, (size_t)chunk * J));
   if (want_cov) CHK(dev.get(&d_cov, (size_t)chunk * J * J));
   HIPC(hipMemsetAsync(d_U, 0, u_len * sizeof(double), c->st));
-  if (want_root) {
-    CHK(dev.get(&d_Q, (size_t)chunk * q_rows * JW));
-    HIPC(hipMemsetAsync(d_Q, 0, (size_t)chunk * q_rows * JW * sizeof(double), c->st));
-    if (lr) {
-      const size_t v_len = (size_t)chunk * p * T16 * JW + GEMM_ROW_SLACK, w_len = (size_t)chunk * rpad * JW + GEMM_ROW_SLACK;
-      CHK(dev.get(&d_V, v_len));
-      CHK(dev.get(&d_W, w_len));
-      HIPC(hipMemsetAsync(d_V, 0, v_len * sizeof(double), c->st));            // rows t >= T stay zero for the whole call
-      HIPC(hipMemsetAsync(d_W, 0, w_len * sizeof(double), c->st));            // so do the rank rows no latent owns
-    }
-  }
+  if (want_root) CHK(root.alloc(dev, (size_t)JW, chunk));
   HIPC(hipMemcpyAsync(d_trial, tos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->st));
   const size_t expand_lds = (size_t)(p * p + p) / 2 * PFUNC_BT * sizeof(double);
-  if (lr && expand_lds > ((size_t)48 << 10))
-    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(pfunc_expand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)expand_lds));
+  if (lr) CHK(lds_opt_in(reinterpret_cast<const void*>(pfunc_expand_kernel), expand_lds));
 
   // The columns jb0 .. jb0 + nj of the weights of `nsets` list positions, transposed into the staging at column col0: [J][p][T] -> [row][JW], every
   // other entry of the image zero.  The image is rebuilt on the host, so the stream is drained before it is touched again.
@@ -92,19 +73,13 @@ int pfunc_group(pgpfa_ctx* c, const PFuncArgs& a, const std::vector<int>& pos, b
   if (!a.per_trial && !restage) CHK(stage(nullptr, 1, 0, Jpad, 0));            // once per snapshot group, not per trial
 
   PFuncP g{};
-  g.U = d_U; g.Xmode = c->Xmode; g.G = lr ? c->Gbin : nullptr; g.V = d_V; g.Q = d_Q; g.mean = d_mean; g.var = d_var; g.cov = d_cov;
-  g.sU = a.per_trial ? (long long)(urows * JW) : 0; g.sQ = (long long)(q_rows * JW);
-  g.rows = !want_root ? 0 : round_up(lr ? c->rtot : c->n, 8); g.erows = lr ? p * T16 : 0; g.lrow = lrow;
+  g.U = d_U; g.Xmode = c->Xmode; g.G = lr ? c->Gbin : nullptr; g.V = root.V; g.Q = root.Q; g.mean = d_mean; g.var = d_var; g.cov = d_cov;
+  g.sU = a.per_trial ? (long long)(urows * JW) : 0; g.sQ = root.sQ();
+  g.rows = want_root ? root.rows : 0; g.erows = lr ? p * T16 : 0; g.lrow = lrow;
   g.p = p; g.T = T; g.T16 = T16; g.JW = JW; g.J = J; g.eps = c->eps;
-  std::vector<int> chunk_trials;
   for (int c0 = 0; c0 < N; c0 += chunk) {
     const int nc = std::min(chunk, N - c0);
-    if (want_root) {
-      // curvature blocks and the factor of the chunk's slots, as the joint sampler forms them (psample.hip) - with every product on one k loop
-      chunk_trials.assign(tos.begin() + c0, tos.begin() + c0 + nc);
-      NoSplitK one_k_loop(c);
-      CHK(resident_curvature(c, chunk_trials, dual, "posterior", [&](double scale) { return posterior_factor_only(c, nc, scale); }));
-    }
+    if (want_root) CHK(root.factor(tos, c0, nc, dual));
     g.ptrial = d_trial + c0;
     if (a.per_trial && !restage) CHK(stage(pos.data() + c0, nc, 0, Jpad, 0));
     for (int jb0 = 0; jb0 < Jpad; jb0 += JB) {
@@ -114,37 +89,17 @@ int pfunc_group(pgpfa_ctx* c, const PFuncArgs& a, const std::vector<int>& pos, b
       if (a.mean) hipLaunchKernelGGL(pfunc_mean_kernel, dim3((nj + 255) / 256, nc), dim3(256), 0, c->st, g);
       HIPC(hipGetLastError());
       if (!want_root) continue;
-      // The products below stay off the split-K path - a fixed 64-tile and a one-level batch declared as the low half of a two-level one -: the number
-      // of k parts there follows the number of tiles, i.e. the chunk and the block, and the bits of a trial's covariance must not.
       if (lr) {
         hipLaunchKernelGGL(pfunc_expand_kernel, dim3((T + PFUNC_BT - 1) / PFUNC_BT, nc), dim3(256), expand_lds, c->st, g);
         HIPC(hipGetLastError());
-        // W^T = V_k^T F_k per latent: the rr[k] rank rows the latent owns (columns of F_k past its rank are zero)
-        for (int k = 0; k < p; ++k) {
-          GemmP f{};
-          f.A = d_V + (size_t)k * T16 * JW + col0; f.sA = (long long)((size_t)p * T16 * JW); f.lda = JW;
-          f.B = c->Flr + (size_t)k * c->Tp * c->Tp; f.sB = 0; f.ldb = c->Tp;
-          f.C = d_W + (size_t)c->roff[k] * JW + col0; f.sC = (long long)((size_t)rpad * JW); f.ldc = JW;
-          f.M = nj; f.N = c->rr[k]; f.K = T16; f.alpha = 1.0; f.beta = 0.0;
-          f.slots = c->ident; f.nbatch = nc; f.nb_lo = nc; f.mode = GEMM_FULL; f.kflags = 0; f.bm = 64;
-          CHK(gemm(c, true, f));
-        }
-        // Q^T = W^T L^-T (the triangle is the second operand's: no k range of the kernel's follows it)
-        GemmP u{};
-        u.A = d_W + col0; u.sA = (long long)((size_t)rpad * JW); u.lda = JW;
-        u.B = c->ws.Mt; u.sB = c->ws.sM; u.ldb = rpad;
-        u.C = d_Q + col0; u.sC = g.sQ; u.ldc = JW;
-        u.M = nj; u.N = rpad; u.K = rpad; u.alpha = 1.0; u.beta = 0.0;
-        u.slots = c->ident; u.nbatch = nc; u.nb_lo = nc; u.mode = GEMM_FULL; u.kflags = 0; u.bm = 64;
-        CHK(gemm(c, true, u));
+        CHK(root.products(nc, (size_t)col0, nj));
       } else {
         // Q^T = U^T L^-T: one product over all npad rows (rows >= p T of U are zero)
-        GemmP e{};
+        GemmP e = root.batch(nc);
         e.A = d_U + col0; e.sA = g.sU; e.lda = JW;
         e.B = c->ws.Mt; e.sB = c->ws.sM; e.ldb = c->ld;
-        e.C = d_Q + col0; e.sC = g.sQ; e.ldc = JW;
-        e.M = nj; e.N = npad; e.K = npad; e.alpha = 1.0; e.beta = 0.0;
-        e.slots = c->ident; e.nbatch = nc; e.nb_lo = nc; e.mode = GEMM_FULL; e.kflags = 0; e.bm = 64;
+        e.C = root.Q + col0; e.sC = g.sQ; e.ldc = JW;
+        e.M = nj; e.N = npad; e.K = npad;
         CHK(gemm(c, true, e));
       }
       if (!want_cov) {
@@ -191,23 +146,7 @@ int pgpfa_posterior_functionals(pgpfa_ctx* c, int n, const int32_t* idx, int J, 
           if (per_trial) return fail("pgpfa_posterior_functionals: the weight of functional %d at latent %d, bin %d of list entry %d (trial %d) is not finite", j, k, t, i, tr.v[i]);
           return fail("pgpfa_posterior_functionals: the weight of functional %d at latent %d, bin %d is not finite", j, k, t);
         }
-  if (!c->have_params) return fail("set_params has not been called");
-  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
-  HIPC(hipSetDevice(c->device));
-  // the sampler's predicate (RESIDENT_SAMPLABLE), with texts of this call's own for the two ways a trial misses it
-  for (int t : tr.v) {
-    if (c->trial_snap[t] >= 0) continue;
-    if (c->mode_serial[t] < 0 && !c->vsmgp_ok[t])
-      return fail("no posterior for trial %d: no E-step has written one since its counts were uploaded", t);
-    return fail("the posterior of trial %d was uploaded with pgpfa_set_posterior: only its blocks are known, it has no square root, and the covariance "
-                "of a functional needs one (a posterior an E-step or pgpfa_dual_finalize of this context wrote)", t);
-  }
-  CHK(require_resident(c, tr.v, RESIDENT_SAMPLABLE));
-  for (int t : tr.v)
-    if (c->trial_dual[t] && c->live.length(t) < c->T)
-      return fail("the variational posterior of trial %d covers %d of %d bins: its jitter comes from the trial's own %d-bin Gram inverse, so the padded grid "
-                  "does not carry its prior conditional; pgpfa_posterior_functionals refuses rather than approximates", t, c->live.length(t), c->T,
-                  c->live.length(t));
+  CHK(query_gate(c, "pgpfa_posterior_functionals", tr.v, "the covariance of a functional"));
   PFuncArgs a{};
   a.trials = &tr.v; a.J = J; a.weights = weights; a.per_trial = per_trial != 0; a.mean = mean; a.var = var; a.cov = cov;
   return for_snapshot_groups(c, tr.v, [&](const std::vector<int>& pos, bool dual) { return pfunc_group(c, a, pos, dual); });

@@ -1,5 +1,5 @@
 // The arithmetic of a workspace plan (workspace.hip: ensure_workspace): slab sizes, bytes per slot, rank head-room, slots per chunk, the fit
-// into an arena whose growth stopped short, and the engine choice.  Pure functions of the dimensions and of byte counts - standard library only,
+// into an arena whose growth stopped short, and the engine choice; and of a posterior query's staging (query.h): trials per chunk, columns per block.  Pure functions of the dimensions and of byte counts - standard library only,
 // no device call, no context - so that every rule stands once and tests/host/plan_check.cpp can run it without a GPU.  The expressions keep
 // the types and the order of operations they had inside ensure_workspace: the integers must not move.
 #pragma once
@@ -132,6 +132,23 @@ Fit fit_slots(size_t need, size_t must, size_t arena_cap, int B_full, int floor_
     B_fit = std::max(floor_slots, B_fit - 8);
   }
   return {B_fit, need, 2 * B_fit >= target, need > arena_cap};
+}
+
+// ---- the posterior queries (query.h): chunks of a trial list and blocks of columns against stage_bytes of device staging --------------------------
+// Trials per chunk of a list of n: the query's *_chunk_trials option when set, else as many as fit stage_bytes at bytes_per_trial of staging
+// (0 bytes: the whole list), at least one; never more than cap (0: no cap).
+inline int query_chunk(size_t n, int option, size_t bytes_per_trial, size_t cap, size_t stage_bytes) {
+  size_t chunk = cap > 0 ? std::min(n, cap) : n;
+  if (option > 0) chunk = std::min(chunk, (size_t)option);
+  else if (bytes_per_trial > 0) chunk = std::min(chunk, std::max<size_t>(1, stage_bytes / bytes_per_trial));
+  return (int)chunk;
+}
+// Columns (query times, functionals) per block through the root, of padded_width (a multiple of 16): the query's block option rounded up to 16 when set,
+// else as many as leave room for eight trials in a chunk at bytes_per_column of staging per trial, a multiple of 16 and at least 16; at most the width.
+inline int query_block_cols(int option, int padded_width, size_t bytes_per_column, size_t stage_bytes) {
+  if (option > 0) return std::min(padded_width, (option + 15) / 16 * 16);
+  const size_t fit = stage_bytes / 8 / bytes_per_column;
+  return (int)std::min<size_t>((size_t)padded_width, std::max<size_t>(16, fit / 16 * 16));
 }
 
 }  // namespace plan

@@ -1,6 +1,6 @@
 // libpgpfa_hip.so - psample.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): joint posterior samples of the latents and
 // posterior-predictive spike counts (pgpfa_posterior_sample); importance weights of the Laplace posterior's draws (pgpfa_importance_weights)
-#include "ctx.h"
+#include "query.h"
 #include "model.h"
 #include "sample.h"
 #include "psample.h"
@@ -25,8 +25,7 @@ struct SampleArgs {
 
 // the positions `pos` of the list (one snapshot, one kind of posterior), under that snapshot's parameters
 int sample_group(pgpfa_ctx* c, const SampleArgs& a, const std::vector<int>& pos, bool dual) {
-  CHK(ready_estep(c, dual ? c->dual_lowrank : true));
-  if (dual) CHK(ensure_lambda(c));
+  CHK(ready_root(c, dual));
   const int n = c->n, q = c->q, p = c->p, T = c->T, S = a.S, nz = a.nz;
   const bool lr = c->plan_lowrank;
   const int t_first = (*a.trials)[pos[0]];

@@ -1,5 +1,5 @@
 // libpgpfa_hip.so - rates.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): posterior firing rates
-#include "ctx.h"
+#include "query.h"
 #include "rates.h"
 #include "counts.h"
 

@@ -1,14 +1,12 @@
-// libpgpfa_hip.so - velat.hip (one translation unit of the C-ABI library; shared declarations: ctx.h): value and velocity of every latent at
+// libpgpfa_hip.so - velat.hip (one translation unit of the C-ABI library; shared declarations: ctx.h, query.h): value and velocity of every latent at
 // arbitrary time points, with their joint 2 x 2 posterior (pgpfa_posterior_velocity_at)
-#include "ctx.h"
+#include "query.h"
 #include "interp.h"
 #include "velat.h"
 
 using namespace pgpfa;
 
 namespace {
-
-constexpr size_t VELAT_LDS_MAX = (size_t)160 << 10;           // LDS of a CU: the row panel and the three planes of running sums have to fit
 
 struct VelArgs {
   const std::vector<int>* trials;     // trial of every list position
@@ -25,13 +23,12 @@ int velat_group(pgpfa_ctx* c, const VelArgs& a, const std::vector<int>& pos) {
   const bool need_A = a.out[O_MEAN] || joint, need_B = a.out[O_VEL] || joint;
   // the time block: as many query times as leave room for the panel, halved from VELAT_SBLK down to one tile (no output depends on it)
   int sblk = VELAT_SBLK;
-  while (sblk > 16 && ((size_t)16 * VS + (size_t)3 * std::min(Spad, sblk)) * sizeof(double) > VELAT_LDS_MAX) sblk /= 2;
+  while (sblk > 16 && ((size_t)16 * VS + (size_t)3 * std::min(Spad, sblk)) * sizeof(double) > QUERY_LDS_MAX) sblk /= 2;
   const size_t lds = ((size_t)16 * VS + (size_t)3 * std::min(Spad, sblk)) * sizeof(double);
-  if (joint && lds > VELAT_LDS_MAX)
+  if (joint && lds > QUERY_LDS_MAX)
     return fail("pgpfa_posterior_velocity_at: a row panel of %d bins does not fit the LDS of a compute unit (%zu bytes)", T, lds);
   const int N = (int)pos.size();
-  std::vector<int> tos(N);
-  for (int i = 0; i < N; ++i) tos[i] = (*a.trials)[pos[i]];
+  const std::vector<int> tos = group_trials(*a.trials, pos);
 
   DevBufs dev("pgpfa_posterior_velocity_at");
   MarkKeeper keep{c, {}};
@@ -47,42 +44,32 @@ int velat_group(pgpfa_ctx* c, const VelArgs& a, const std::vector<int>& pos) {
   const int grids = a.per_trial ? chunk : 1;
   const size_t wlen = (size_t)grids * slab + GEMM_ROW_SLACK;
 
-  double *d_times = nullptr, *d_kx = nullptr, *d_A = nullptr, *d_kd = nullptr, *d_B = nullptr, *d_out[O_COUNT] = {};
+  TimeGrids tg{c, a.times, S};
+  double *d_kx = nullptr, *d_A = nullptr, *d_kd = nullptr, *d_B = nullptr, *d_out[O_COUNT] = {};
   int* d_trial = nullptr;
-  CHK(dev.get(&d_times, (size_t)grids * S));
+  CHK(tg.alloc(dev, grids));
   CHK(dev.get(&d_trial, (size_t)N));
-  if (need_A) {
-    CHK(dev.get(&d_kx, wlen));
-    CHK(dev.get(&d_A, wlen));
-    HIPC(hipMemsetAsync(d_kx, 0, wlen * sizeof(double), c->st));
-    HIPC(hipMemsetAsync(d_A, 0, wlen * sizeof(double), c->st));      // rows t >= T stay zero for the whole call
-  }
-  if (need_B) {
-    CHK(dev.get(&d_kd, wlen));
-    CHK(dev.get(&d_B, wlen));
-    HIPC(hipMemsetAsync(d_kd, 0, wlen * sizeof(double), c->st));
-    HIPC(hipMemsetAsync(d_B, 0, wlen * sizeof(double), c->st));
-  }
+  if (need_A) CHK(weight_slabs(c, dev, wlen, &d_kx, &d_A));
+  if (need_B) CHK(weight_slabs(c, dev, wlen, &d_kd, &d_B));
   for (int o = 0; o < O_COUNT; ++o)
     if (a.out[o]) CHK(dev.get(&d_out[o], (size_t)chunk * p * Spad));
   HIPC(hipMemcpyAsync(d_trial, tos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->st));
 
-  // kx, A and kd, B of `ng` grids whose times are in d_times
+  // kx, A and kd, B of `ng` grids whose times are in tg.d
   auto weights = [&](int ng) -> int {
-    if (need_A) CHK(interp_weights(c, d_times, ng, S, Spad, T16, d_kx, d_A));
+    if (need_A) CHK(interp_weights(c, tg.d, ng, S, Spad, T16, d_kx, d_A));
     if (need_B) {
-      hipLaunchKernelGGL(velat_cross_kernel, dim3(T16, p, ng), dim3(256), 0, c->st, d_times, c->tau, c->bin, c->eps, T, T16, S, Spad, p, d_kd);
+      hipLaunchKernelGGL(velat_cross_kernel, dim3(T16, p, ng), dim3(256), 0, c->st, tg.d, c->tau, c->bin, c->eps, T, T16, S, Spad, p, d_kd);
       HIPC(hipGetLastError());
       CHK(interp_solve(c, d_kd, ng, Spad, T16, d_B));
     }
     return 0;
   };
   if (!a.per_trial) {
-    HIPC(hipMemcpyAsync(d_times, a.times, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c->st));
+    CHK(tg.upload_shared());
     CHK(weights(1));                                          // once per snapshot group, not per trial
   }
-  if (joint && lds > ((size_t)48 << 10))
-    HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(velat_joint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (joint) CHK(lds_opt_in(reinterpret_cast<const void*>(velat_joint_kernel), lds));
 
   const long long sG = a.per_trial ? (long long)slab : 0;
   InterpP km{};                                               // interp_mean_kernel on A (mean) and on B (vel)
@@ -91,13 +78,10 @@ int velat_group(pgpfa_ctx* c, const VelArgs& a, const std::vector<int>& pos) {
   k.vsmgp = c->vsmgp; k.A = d_A; k.B = d_B; k.kx = d_kx; k.kd = d_kd; k.tau = c->tau; k.eps = c->eps;
   k.var = d_out[O_VAR]; k.vel_var = d_out[O_VELVAR]; k.cross = d_out[O_CROSS];
   k.sG = sG; k.p = p; k.T = T; k.T4 = T4; k.T16 = T16; k.Spad = Spad; k.VS = VS; k.sblk = sblk;
-  std::vector<double> h_times;
   for (int c0 = 0; c0 < N; c0 += chunk) {
     const int nc = std::min(chunk, N - c0);
     if (a.per_trial) {
-      h_times.resize((size_t)nc * S);
-      for (int i = 0; i < nc; ++i) std::copy(a.times + (size_t)pos[c0 + i] * S, a.times + (size_t)(pos[c0 + i] + 1) * S, h_times.begin() + (size_t)i * S);
-      HIPC(hipMemcpyAsync(d_times, h_times.data(), h_times.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
+      CHK(tg.upload_listed(pos.data() + c0, nc));
       CHK(weights(nc));
     }
     km.ptrial = k.ptrial = d_trial + c0;
@@ -115,9 +99,7 @@ int velat_group(pgpfa_ctx* c, const VelArgs& a, const std::vector<int>& pos) {
     for (int i = 0; i < nc; ++i) {
       const size_t ps = (size_t)pos[c0 + i];
       for (int o = 0; o < O_COUNT; ++o)
-        if (a.out[o])
-          HIPC(hipMemcpy2DAsync(a.out[o] + ps * p * S, (size_t)S * sizeof(double), d_out[o] + (size_t)i * p * Spad, (size_t)Spad * sizeof(double),
-                                (size_t)S * sizeof(double), p, hipMemcpyDeviceToHost, c->st));
+        if (a.out[o]) CHK(download_plane(c, a.out[o] + ps * p * S, d_out[o] + (size_t)i * p * Spad, p, S, Spad));
     }
     HIPC(hipStreamSynchronize(c->st));                         // the staging is reused by the next chunk
     HIPC(hipGetLastError());
@@ -135,22 +117,8 @@ int pgpfa_posterior_velocity_at(pgpfa_ctx* c, int n, const int32_t* idx, int S, 
   if (!times_ms) return fail("pgpfa_posterior_velocity_at: times_ms is NULL");
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr));
-  const int N = (int)tr.v.size();
-  for (int i = 0; i < (per_trial ? N : 1); ++i)
-    for (int s = 0; s < S; ++s)
-      if (!std::isfinite(times_ms[(size_t)i * S + s])) {
-        if (per_trial) return fail("pgpfa_posterior_velocity_at: query time %d of list entry %d (trial %d) is not finite", s, i, tr.v[i]);
-        return fail("pgpfa_posterior_velocity_at: query time %d is not finite", s);
-      }
-  if (!c->have_params) return fail("set_params has not been called");
-  if (c->tau_inflight) return fail("a timescale pass is in flight (pgpfa_mstep_tau_costgrad_multi_begin): collect it first");
-  HIPC(hipSetDevice(c->device));
-  CHK(require_resident(c, tr.v, RESIDENT_BLOCKS));
-  for (int t : tr.v)
-    if (c->trial_dual[t] && c->live.length(t) < c->T)
-      return fail("the variational posterior of trial %d covers %d of %d bins: its jitter comes from the trial's own %d-bin Gram inverse, so the padded grid "
-                  "does not carry its prior conditional; pgpfa_posterior_velocity_at refuses rather than approximates", t, c->live.length(t), c->T,
-                  c->live.length(t));
+  CHK(check_query_times("pgpfa_posterior_velocity_at", times_ms, S, per_trial != 0, tr.v));
+  CHK(query_gate(c, "pgpfa_posterior_velocity_at", tr.v));
   VelArgs a{};
   a.trials = &tr.v; a.S = S; a.times = times_ms; a.per_trial = per_trial != 0;
   a.out[O_MEAN] = mean; a.out[O_VAR] = var; a.out[O_VEL] = vel; a.out[O_VELVAR] = vel_var; a.out[O_CROSS] = cross;

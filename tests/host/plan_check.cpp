@@ -6,6 +6,8 @@
 //   bytes ld npad n rpad Tp T p slab mt                                   -> per_slot_bytes shared_bytes
 //   headroom ld npad n rpad Tp T p factor arena_cap budget target         -> pick slab mt                      (low-rank plan)
 //   engine ld npad n rpad Tp T p cov_mode                                 -> lowrank_pays want_lowrank
+//   qchunk n option bytes_per_trial cap stage_bytes                       -> trials per chunk of a posterior query
+//   qblock option padded_width bytes_per_column stage_bytes               -> columns per block of a posterior query
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -58,6 +60,14 @@ int main() {
       int cov_mode;
       in >> cov_mode;
       std::printf("%d %d\n", (int)plan::lowrank_pays(d), (int)plan::want_lowrank(d, cov_mode));
+    } else if (what == "qchunk") {
+      size_t n, bytes, cap, stage; int option;
+      in >> n >> option >> bytes >> cap >> stage;
+      std::printf("%d\n", plan::query_chunk(n, option, bytes, cap, stage));
+    } else if (what == "qblock") {
+      int option, width; size_t bytes, stage;
+      in >> option >> width >> bytes >> stage;
+      std::printf("%d\n", plan::query_block_cols(option, width, bytes, stage));
     } else {
       std::fprintf(stderr, "plan_check: unknown case '%s'\n", line.c_str());
       return 2;

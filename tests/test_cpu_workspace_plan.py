@@ -1,7 +1,8 @@
 """The arithmetic of the workspace plan (csrc/plan.h: slots per chunk, the fit into an arena whose growth stopped short, rank head-room) with no GPU.
 tests/host/plan_check.cpp is built against the header with the address and undefined-behaviour sanitizers and run as a child process: cases go in
 on standard input, one line of integers per case comes back, and this file compares.  Nothing is loaded into Python.  The expected values of the
-tables are derived by hand from the rules as ensure_workspace had them (docs/history/workspace_unit.md)."""
+tables are derived by hand from the rules as ensure_workspace had them (docs/history/workspace_unit.md); those of a posterior query's chunks and
+blocks (query_chunk, query_block_cols) from the expressions the query units had (docs/history/query_stages.md)."""
 import os
 import shutil
 import subprocess
@@ -135,6 +136,29 @@ def test_fit_invariants(ask):
         assert short == int(need > cap) and capped == int(2 * B >= target), line
         walked += need <= cap and B + 8 <= B_full and bytes_for(B + 8) > cap
     assert walked > 0
+
+
+# ---- chunks and blocks of a posterior query (csrc/query.h) --------------------------------------------------------------------------------------------
+STAGE = 256 << 20                     # QUERY_STAGE_BYTES
+ANY_BYTES = (0, 1, 181760, 10 ** 12)  # where the option decides, the bytes do not
+QCHUNK_TABLE = [((100, 0, 0, 0), 100), ((100, 0, 26843545, 0), 10), ((100, 0, 300000000, 0), 1), ((100, 0, 0, 40), 40), ((100, 64, 0, 40), 40)] + \
+               [((100, 7, b, 0), 7) for b in ANY_BYTES]            # (n, option, bytes per trial, cap) -> trials per chunk
+# covat, low-rank, p = 10, T16 = 176, rpad = 256: (10 * 176 + 2 * 256) = 2272 staged rows x 10 latents x 8 bytes = 181760 per query time, 184 fit an
+# eighth of the staging -> 176; pfunc at the same shape: (2 * 1760 + 512) = 4032 rows x 8 bytes = 32256 per functional, 1040 fit
+QBLOCK_TABLE = [((0, 512, 181760), 176), ((0, 2048, 32256), 1040), ((0, 512, 4000000), 16), ((0, 48, 8), 48)] + \
+               [((24, 512, b), 32) for b in ANY_BYTES[1:]] + [((24, 16, b), 16) for b in ANY_BYTES[1:]]     # (option, padded width, bytes per column) -> columns
+
+
+def test_query_chunk_table(ask):
+    got = ask(['qchunk %d %d %d %d %d' % (case + (STAGE,)) for case, _ in QCHUNK_TABLE])
+    print(got)
+    assert got == [[want] for _, want in QCHUNK_TABLE]
+
+
+def test_query_block_cols_table(ask):
+    got = ask(['qblock %d %d %d %d' % (case + (STAGE,)) for case, _ in QBLOCK_TABLE])
+    print(got)
+    assert got == [[want] for _, want in QBLOCK_TABLE]
 
 
 # ---- rank head-room ------------------------------------------------------------------------------------------------------------------------------------

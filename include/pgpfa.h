@@ -586,7 +586,11 @@ int pgpfa_loo_predict(pgpfa_ctx* ctx, int n, const int32_t* idx, double* y_pred 
 
 /* ---- dual variational E-step (inference.py:188-432) -------------------------------- */
 /* dualProblem and dualProblem_grad for one trial at lambda[q*T] (structured: never forms
- * C_big or diag(lambda)). */
+ * C_big or diag(lambda)).  pgpfa_dual_costgrad, pgpfa_dual_costgrad_batch, pgpfa_dual_post_mean and pgpfa_dual_post_cov
+ * refuse a lambda that is not finite (the first two also one that is not positive) at a live entry on the host, before
+ * anything is uploaded or launched, naming the trial and the entry.  The check runs right behind the argument and trial-list
+ * checks and ahead of the state checks, so a call that is also made too early (no counts, no parameters) or lists a trial
+ * twice reports its lambda first; it reads only the caller's array and the host copies of the live tables. */
 int pgpfa_dual_costgrad(pgpfa_ctx* ctx, int trial, const double* lam, double* cost,
                         double* grad /* [q*T] or NULL */);
 /* The same for a list of distinct trials at once, each at its own lambda: lam[n][q*T] -> cost[n], grad[n][q*T]

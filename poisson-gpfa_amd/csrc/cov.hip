@@ -103,7 +103,7 @@ static int posterior_blocks_dense(pgpfa_ctx* c, int nb, double diag_scale, bool 
   c->info["last_cov_f32"] = 0.0;                             // (option laplace_f32 is the low-rank engine's)
   CHK(ensure_mt_clean(c));
   c->last_cov_lowrank = false;
-  CHK(assemble(c, c->ident, nb, diag_scale));
+  CHK(assemble(c, c->ident, nb, diag_scale, diag_scale != 1.0 && dual_jitter_per_trial(c)));   // (a scale other than 1: dual_dense_scale ran on these slots)
   CHK(factor(c, c->ws, c->ident, nb));
   // log det H + sum_k log det K_k of the log evidence: from the factor, before the staging of post_vsmGP reuses its slab
   if (ld_dev) {
@@ -827,7 +827,7 @@ int posterior_blocks(pgpfa_ctx* c, int nb, double diag_scale, bool want_vsmgp, b
 int posterior_factor_only(pgpfa_ctx* c, int nb, double diag_scale) {
   if (!c->plan_lowrank) {
     CHK(ensure_mt_clean(c));
-    CHK(assemble(c, c->ident, nb, diag_scale));
+    CHK(assemble(c, c->ident, nb, diag_scale, diag_scale != 1.0 && dual_jitter_per_trial(c)));   // (a scale other than 1: dual_dense_scale ran on these slots)
     CHK(factor(c, c->ws, c->ident, nb));
     CHK(inverse_t(c, c->ws, c->ident, nb));
     HIPC(hipGetLastError());

@@ -534,7 +534,7 @@ int poisson(pgpfa_ctx* c, const int* d_list, int nl, const double* X, double* G,
 int prior_mv(pgpfa_ctx* c, const int* d_list, int nl, const double* in, double* out, const double* mat = nullptr);
 int prior_mv_all(pgpfa_ctx* c, int nb, const double* in, double* out, const double* mat = nullptr, const int* skip = nullptr,
                  const int* cols = nullptr, int ncols = 0);
-int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale = 1.0);
+int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale = 1.0, bool full_len_only = false);   // full_len_only: see dual_jitter_per_trial
 int bin_blocks(pgpfa_ctx* c, const double* W, long long sW, double* G, double* Wt, long long sO, int nslots, double* ldet);
 // (the launch itself: the kernel by latent width - registers up to 10, 32 lanes per matrix up to 32 - for the nslots entries of `slots`)
 void bin_blocks_launch(const double* W, long long sW, double* G, double* Wt, long long sO, int T, int p, double eps, const int* slots, int nslots, double* ldet,
@@ -566,11 +566,13 @@ int resident_curvature(pgpfa_ctx* c, const std::vector<int>& tos, bool dual, con
 // dual.hip
 int ensure_lambda(pgpfa_ctx* c);
 int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<double>* sD, std::vector<double>* vKv);
-int dual_jitter(pgpfa_ctx* c, int nb);
+int dual_jitter(pgpfa_ctx* c, int nb, bool skip_full = false);
 // option dual_masked (see pgpfa_ctx::dual_masked)
 bool dual_masking(const pgpfa_ctx* c);                                // the option is on and a table is set: dual variables carry the live mask
 int dual_mask(pgpfa_ctx* c, int nb, double* buf);                     // zero the entries that are not live of a [slot][q][T] array (no-op unless dual_masking)
-int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale);            // the dense engine's jitter: the diagonal scale of assemble, or in the W blocks (length table)
+bool dual_jitter_per_trial(const pgpfa_ctx* c);                       // dual_masked with a length table: the dense engine's jitter depends on the trial - who assembles behind
+                                                                      // dual_dense_scale passes this as assemble's full_len_only (with the identity slot list that dual_jitter walks)
+int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale);            // the dense engine's jitter: the diagonal scale of assemble; under a length table also in the W blocks of the shorter trials
 int ensure_trunc_prior(pgpfa_ctx* c);
 int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want_grad, double* cost, bool tolerate = false);
 int var_offsets(pgpfa_ctx* c, int nb, double* out);

@@ -203,19 +203,34 @@ inline __global__ void dual_jitter_kernel(double* __restrict__ W, long long sW, 
 // The same for trials of unequal length (option dual_masked with a length table): a trial of L = len[trial] < T bins is the reference's trial of L
 // bins, whose precision is K_L^-1 + scatter(W_t), so its jitter takes (K_{k,L}^-1)_tt = Q[k][L - 1][t] (trunc_prior_kernel) at t < L and the padded
 // bins t >= L get none - marginalising them then returns the reference's jittered posterior of the truncated trial exactly.
-// A trial of all T bins reads the Kinv diagonal with the expression above: the same bits.  grid = (ceil(T*p/256), nslots)
+// A trial of all T bins reads the Kinv diagonal with the expression above: the same bits.  skip_full (the dense engine): a trial of all T bins is left
+// alone - its jitter is the diagonal scale of the assembled precision, as with no table (dual_diag_scale_full_kernel).  grid = (ceil(T*p/256), nslots)
 inline __global__ void dual_jitter_len_kernel(double* __restrict__ W, long long sW, const double* __restrict__ Kinv, int Tp, int T, int p, double jit,
-                                              const int* __restrict__ trial_of_slot, const int* __restrict__ len, const double* __restrict__ Q) {
+                                              const int* __restrict__ trial_of_slot, const int* __restrict__ len, const double* __restrict__ Q,
+                                              int skip_full) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= T * p) return;
   const int t = e / p, k = e - t * p;
   const int L = len[trial_of_slot[blockIdx.y]];
-  if (t >= L) return;
+  if (t >= L || (skip_full && L == T)) return;
   double* w = W + (size_t)blockIdx.y * sW + (size_t)t * p * p + k * p + k;
   const double kd = (L == T) ? Kinv[(size_t)k * Tp * Tp + (size_t)t * Tp + t] : Q[((size_t)k * T + (L - 1)) * T + t];
   // (dual_jitter_kernel's expression compiles to the product jit * (K^-1)_tt rounded once and one fused multiply-add with (1 + jit) W; spelled out here,
   //  because with the select in front the compiler contracts the other product and a trial of all T bins would lose its bits)
   *w = fma(1.0 + jit, *w, jit * kd);
+}
+
+// The dense engine under a length table: the slots whose trial has all T bins get the jitter where a call with no table puts it - the diagonal of the
+// assembled precision (assemble_h_kernel with scale 1: fl(K^-1_tt + W_t[k][k])) times 1 + jit, rounded once more; that is assemble_h_kernel's own
+// sequence with diag_scale = 1 + jit, so such a trial returns the bits it returns with no table.  Shorter trials carry their jitter in W
+// (dual_jitter_len_kernel) and are left alone.  H: lower triangle, column-major, ld; rows >= n are identity padding.  grid = (ceil(n/256), nslots)
+inline __global__ void dual_diag_scale_full_kernel(double* __restrict__ H, long long sH, int ld, int n, int T, double scale,
+                                                   const int* __restrict__ slots, const int* __restrict__ trial_of_slot, const int* __restrict__ len) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t slot = slots[blockIdx.y];
+  if (j >= n || len[trial_of_slot[slot]] != T) return;
+  double* h = H + slot * (size_t)sH + (size_t)j * ld + j;
+  *h = *h * scale;
 }
 
 // Truncated-prior tables of one latent per blockIdx.y from its Cholesky factor Lf (lower, column-major, ld = Tp) and Mt = Lf^-T (upper, column-major:

@@ -55,10 +55,14 @@ static double trunc_logdet_correction(const pgpfa_ctx* c, int trial) {
 }
 
 // The dense engine scales the assembled diagonal by 1 + 1e-6 (inference.py:190).  While a length table is set under the option the jitter depends on the
-// trial and goes into the W blocks of the slots [0, nb) instead (dual_jitter), and the assembly runs with scale 1.
+// trial: the slots [0, nb) whose trial is shorter than T get it in their W blocks here (dual_jitter), and the caller hands the scale to assemble with
+// full_len_only = dual_jitter_per_trial(c), which applies it to the diagonal of the other slots only - so a trial of all T bins keeps the bits it has with
+// no table set.
+bool dual_jitter_per_trial(const pgpfa_ctx* c) { return c->dual_masked && c->live.lengths(); }
+
 int dual_dense_scale(pgpfa_ctx* c, int nb, double* scale) {
   *scale = 1.0 + 1e-6;
-  if (c->dual_masked && c->live.lengths()) { CHK(dual_jitter(c, nb)); *scale = 1.0; }
+  if (dual_jitter_per_trial(c)) CHK(dual_jitter(c, nb, /*skip_full=*/true));
   return 0;
 }
 
@@ -121,6 +125,21 @@ int dual_common(pgpfa_ctx* c, int nb, std::vector<double>* sB, std::vector<doubl
   return 0;
 }
 
+// The dual variables a caller passes for one trial, checked on the host before anything is uploaded or launched: every live entry finite, and positive where
+// the entry point takes its log.  (An Inf passes `lam > 0`.  In the GEMM form Lambda^T is read with K = qpad, so the first qpad - q neuron rows of slot
+// s + 1 meet the zero table rows of slot s: 0 * Inf = NaN in the curvature of the trial in front, and the call then fails naming that one.)
+// live_only: entries that are not live under option dual_masked may hold anything - they are zeroed on the device before any kernel reads them.
+static int check_lambda(const pgpfa_ctx* c, const char* entry, int trial, const double* lam, bool positive, bool live_only) {
+  const size_t m = (size_t)c->q * c->T;
+  for (size_t i = 0; i < m; ++i) {
+    if (std::isfinite(lam[i]) && (!positive || lam[i] > 0.0)) continue;
+    if (live_only && !c->live.entry_live(trial, i)) continue;
+    if (!std::isfinite(lam[i])) return fail("%s: lambda must be finite (trial %d, entry %zu = %g)", entry, trial, i, lam[i]);
+    return fail("%s: lambda must be positive (trial %d, entry %zu = %g)", entry, trial, i, lam[i]);
+  }
+  return 0;
+}
+
 int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost, double* grad) {
   CHK(refuse_tables(c, "pgpfa_dual_costgrad", 0, TBL_LEN | TBL_ROWS));
   // (the low-rank engine, and any evaluation under a table, is the batched evaluation with one trial)
@@ -132,10 +151,9 @@ int pgpfa_dual_costgrad(pgpfa_ctx* c, int trial, const double* lam, double* cost
   CHK(ready(c));
   if (!lam || !cost) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
+  CHK(check_lambda(c, "pgpfa_dual_costgrad", trial, lam, true, false));
   CHK(ensure_lambda(c));
   const int q = c->q, p = c->p, T = c->T;
-  for (size_t i = 0; i < (size_t)q * T; ++i)
-    if (!(lam[i] > 0.0)) return fail("lambda must be positive (entry %zu = %g)", i, lam[i]);
   std::vector<int> tr{trial};
   CHK(upload_list(c, c->trial_of_slot, tr));
   CHK(upload(c, c->lamd, lam, (size_t)q * T));
@@ -171,6 +189,7 @@ int pgpfa_dual_post_mean(pgpfa_ctx* c, int trial, const double* lam, double* mea
   CHK(ready(c));
   if (!lam || !mean) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
+  CHK(check_lambda(c, "pgpfa_dual_post_mean", trial, lam, false, false));   // (the mean is linear in lambda: any finite value has one)
   CHK(ensure_lambda(c));
   const int q = c->q, T = c->T;
   std::vector<int> tr{trial};
@@ -198,7 +217,7 @@ static int dual_post_cov_dev(pgpfa_ctx* c, double* cov, double* prec) {
   CHK(ensure_mt_clean(c));
   double scale = 1.0;
   CHK(dual_dense_scale(c, 1, &scale));
-  CHK(assemble(c, c->ident, 1, scale));
+  CHK(assemble(c, c->ident, 1, scale, dual_jitter_per_trial(c)));
   CHK(factor(c, c->ws, c->ident, 1));
   CHK(inverse_t(c, c->ws, c->ident, 1));
   GemmP g{};
@@ -222,10 +241,9 @@ int pgpfa_dual_post_cov(pgpfa_ctx* c, int trial, const double* lam, double* cov,
   CHK(ready(c));
   if (!lam || !cov) return fail("null argument");
   if (trial < 0 || trial >= c->R) return fail("trial %d out of range", trial);
+  CHK(check_lambda(c, "pgpfa_dual_post_cov", trial, lam, false, false));
   CHK(ensure_lambda(c));
   const int q = c->q, T = c->T;
-  for (size_t i = 0; i < (size_t)q * T; ++i)
-    if (!std::isfinite(lam[i])) return fail("lambda entry %zu is not finite", i);
   std::vector<int> tr{trial};
   CHK(upload_list(c, c->trial_of_slot, tr));
   CHK(upload(c, c->lamd, lam, (size_t)q * T));
@@ -244,11 +262,12 @@ int post_cov_dual_impl(pgpfa_ctx* c, int trial, double* out) {
 }
 
 // the reference's 1e-6 relative jitter on the diagonal of the posterior precision, applied to the W blocks of the slots [0, nb) in place
-int dual_jitter(pgpfa_ctx* c, int nb) {
+// (skip_full: under a length table, not to the slots whose trial has all T bins - the dense engine, dual_dense_scale)
+int dual_jitter(pgpfa_ctx* c, int nb, bool skip_full) {
   if (c->dual_masked && c->live.lengths()) {
     CHK(ensure_trunc_prior(c));
     hipLaunchKernelGGL(dual_jitter_len_kernel, dim3((unsigned)((c->T * c->p + 255) / 256), nb), dim3(256), 0, c->st, c->W, (long long)c->T * c->p * c->p,
-                       c->Kinv, c->Tp, c->T, c->p, 1e-6, c->trial_of_slot, c->live.lengths(), c->trunc_q);
+                       c->Kinv, c->Tp, c->T, c->p, 1e-6, c->trial_of_slot, c->live.lengths(), c->trunc_q, skip_full ? 1 : 0);
     HIPC(hipGetLastError());
     return 0;
   }
@@ -323,7 +342,7 @@ int dual_eval_slots(pgpfa_ctx* c, int nb, const std::vector<int>& tos, bool want
   CHK(ensure_mt_clean(c));
   double scale = 1.0;
   CHK(dual_dense_scale(c, nb, &scale));
-  CHK(assemble(c, c->ident, nb, scale));                                // inference.py:190
+  CHK(assemble(c, c->ident, nb, scale, dual_jitter_per_trial(c)));      // inference.py:190
   CHK(factor(c, c->ws, c->ident, nb));
   hipLaunchKernelGGL(logdet_batch_kernel, dim3(nb), dim3(256), 0, c->st, c->ws.H, (long long)c->ws.sH, c->ld, c->npad, c->sc_f);
   CHK(download(c, logdet.data(), c->sc_f, nb));
@@ -431,13 +450,12 @@ int pgpfa_dual_costgrad_batch(pgpfa_ctx* c, int n, const int32_t* idx, const dou
   Trials tr;
   CHK(resolve_trials(c, n, idx, &tr, true));
   const int N = (int)tr.v.size();
+  const size_t m = (size_t)c->q * c->T;
+  const bool masked = dual_masking(c);                              // (entries that are not live are ignored on input and zeroed on the device)
+  for (int i = 0; i < N; ++i) CHK(check_lambda(c, "pgpfa_dual_costgrad_batch", tr.v[i], lam + (size_t)i * m, true, masked));
   c->want_slots = std::max(c->want_slots, std::min(N, c->R));
   CHK(ready_estep(c, c->dual_lowrank));
   CHK(ensure_lambda(c));
-  const size_t m = (size_t)c->q * c->T;
-  const bool masked = dual_masking(c);                              // (entries that are not live are ignored on input and zeroed on the device)
-  for (size_t i = 0; i < (size_t)N * m; ++i)
-    if (!(lam[i] > 0.0) && !(masked && !c->live.entry_live(tr.v[i / m], i % m))) return fail("lambda must be positive (trial %d, entry %zu = %g)", tr.v[i / m], i % m, lam[i]);
   CHK(check_distinct(tr.v));
   for (int c0 = 0; c0 < N; c0 += c->B) {
     const int nb = std::min(c->B, N - c0);

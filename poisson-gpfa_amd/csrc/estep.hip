@@ -109,10 +109,17 @@ int prior_mv_all(pgpfa_ctx* c, int nb, const double* in, double* out, const doub
   return gemm(c, true, g);
 }
 
-int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale) {
+// full_len_only (the dual evaluation's jitter under a length table, dual_dense_scale): diag_scale applies to the listed slots whose trial has all T bins
+// and to no other - the shorter trials carry their jitter in their W blocks already.  The precision is then assembled with scale 1 and the diagonal of
+// those slots scaled by a pass behind it, which rounds as the assembly with the scale does (dual.h); both launches are timed as the assembly.
+int assemble(pgpfa_ctx* c, const int* d_list, int nl, double diag_scale, bool full_len_only) {
+  if (full_len_only && !c->live.lengths()) return fail("internal: per-trial diagonal scale without a length table");
   prof_begin(c, TAG_ASSEMBLE, 0.0);
   hipLaunchKernelGGL(assemble_h_kernel, dim3(c->npad, nl), dim3(256), 0, c->st, c->ws.H, c->ws.sH, c->ld, c->npad, c->n, c->T, c->Tp,
-                     c->p, c->Kinv, c->W, (long long)c->T * c->p * c->p, d_list, diag_scale);
+                     c->p, c->Kinv, c->W, (long long)c->T * c->p * c->p, d_list, full_len_only ? 1.0 : diag_scale);
+  if (full_len_only)
+    hipLaunchKernelGGL(dual_diag_scale_full_kernel, dim3((unsigned)((c->n + 255) / 256), nl), dim3(256), 0, c->st, c->ws.H, (long long)c->ws.sH, c->ld, c->n, c->T,
+                       diag_scale, d_list, c->trial_of_slot, c->live.lengths());
   prof_end(c);
   HIPC(hipGetLastError());
   return 0;
